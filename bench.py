@@ -7,16 +7,24 @@ aln_batch_optimal_enqueue/_collect (find_max + traceback, per-pair results to th
 before the timed region.  Pairs are independent, so ranks own disjoint batches (weak scaling) and the only collective is ONE
 gather of the fp32 scores per step: aln_gather_scores (RCCL all-gather over xGMI, csrc/aln_comm.hip) — never torch.
 
-Prints ONE JSON line.  Besides the contract's keys:
+Prints ONE JSON line.  A plain run sets up, calibrates the launch pattern, warms up, times --steps steps and prints the line;
+besides the contract's keys it holds:
   roofline      dominant kernel (row-sweep DP).  `achieved` uses the bytes the chosen plane layout MUST write (uint16 score +
                 uint16 pointer word = 4 B per matrix cell in this configuration; `contract_bytes` keeps SURVEY 8(d)'s 8 B/cell for
                 context) over the measured time; `valu` is the second roof (wave-instructions from profiles/ over the measured
                 VALU issue rate); `bound` names the roof with the larger fraction.
+--full adds everything that takes runs of its own or checks the result:
+  parity        every resident copy of a sub-batch re-run and compared, the gathered scores against them, and the pairs the real
+                reference was run on (tests/golden/full_cases.json) against its scores.
+  roofline      + this box's measured fill rate (`measured_fill_GBs_this_box`, `frac_of_measured_fill`).
   kernel_only / end_to_end   SURVEY 8(d): kernel time alone, and a pass that also encodes + uploads the residues, copies every
                 pair list to the host and builds the gapped strings + identities (aln_batch_optimal_strings).
   secondary     driver-timed figures of configs 3, 4 and 5 on this GPU (rank 0, N = 1).
   cpu_baseline  the reference (oracle/_ref, the real christang/alignment-algos DPMatrix) or the oracle port on this box's host
                 cores: one pair alone on an idle core, then one pair per core on all cores.
+--dump-outputs DIR writes what the last timed step handed its caller (rank 0): DIR/scores.npy (float32, the gathered scores of
+all pairs), DIR/list_lengths.npy and DIR/status.npy (float64, rank 0's pairs).  The workload is seeded: the same arguments give
+the same inputs on every run.
 """
 import argparse
 import json
@@ -227,15 +235,19 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--pairs", type=int, default=1024, help="pairs per GPU (config 2: 1024)")
     ap.add_argument("--length", type=int, default=2000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the config 3/4/5 figures and the end-to-end pass")
+    ap.add_argument("--full", action="store_true",
+                    help="also the parity checks, the fill-rate roof, kernel_only, end_to_end, the config 3/4/5 figures and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (scores, list lengths, status) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the config 3/4/5 figures and the end-to-end pass")
     ap.add_argument("--streams", "--batches", dest="batches", type=int, default=0,
                     help="HIP streams (contexts) the launches rotate over (1 = everything on one stream; 0 = calibrate the launch pattern)")
     ap.add_argument("--alt-prio", type=int, default=-1, help="tagged kernel's row-alternating wave priority: -1 = calibrate")
     ap.add_argument("--occupancy", type=int, default=-1, help="tagged kernel's waves per SIMD (2 or 3): -1 = calibrate")
     ap.add_argument("--split", type=int, default=0,
                     help="launches a step's batch is processed in (sub-batches of pairs/split pairs; 1 = one launch per step; 0 = calibrate)")
-    ap.add_argument("--lone-steps", type=int, default=10, help="lone launches (one stream, whole batch) timed after the main region for kernel_only")
+    ap.add_argument("--lone-steps", type=int, default=10, help="with --full: lone launches (one stream, whole batch) timed after the main region for kernel_only")
     ap.add_argument("--trace-steps", action="store_true", help="add the host time stamps of every timed step to the JSON line")
     return ap.parse_args(argv)
 
@@ -413,11 +425,13 @@ def rank_main(args):
             if self.e2e:
                 sc, ident, status, _, _, lens, _ = bt.optimal_strings_collect(decode=False)
                 self.last = (sc, status, ident, lens)
+                kept = (ident, lens)
             else:
                 sc, cnt, status = bt.optimal_collect()
                 self.last = (sc, status)
+                kept = (cnt, status)                        # step_result = [scores, list lengths, status] of the last step
             parts = self.open_steps.setdefault(sid, [None] * self.split)
-            parts[h] = (np.array(sc, copy=True),) + tuple(np.array(x, copy=True) for x in self.last[2:])
+            parts[h] = (np.array(sc, copy=True),) + tuple(np.array(x, copy=True) for x in kept)
             if all(x is not None for x in parts):           # the step is complete on this rank: its ONE gather
                 mine = np.concatenate([x[0] for x in parts])
                 self.step_result = [np.concatenate([x[k] for x in parts]) for k in range(len(parts[0]))]
@@ -563,26 +577,34 @@ def rank_main(args):
         per[k] = per.get(k, 0) + 1
     hist = [units[k].dp_ms_history(min(n, 64)) for k, n in per.items()]
     kernel_ms = np.concatenate(hist) if hist else np.zeros(0, np.float32)
-    # parity inside the bench: every resident copy of a sub-batch gives identical scores, and the pairs the REAL reference
-    # was run on (tests/golden/full_cases.json) score exactly what it scored
-    ref_sc = {}
-    for (sidx, h), bt in units.items():
-        bt.reevaluate()
-        s_b, _, st_b = bt.optimal(want_pairs=False)
-        assert (st_b == 0).all()
-        if h not in ref_sc:
-            ref_sc[h] = np.array(s_b, copy=True)
-        else:
-            assert np.array_equal(ref_sc[h], s_b), "resident copies of a sub-batch disagree"
-    all_sc = np.concatenate([ref_sc[h] for h in range(split)])
-    assert np.array_equal(gathered[rank * args.pairs:(rank + 1) * args.pairs].view(np.uint32), all_sc.view(np.uint32)), "gathered scores differ"
+    if args.dump_outputs and rank == 0:                     # what the last timed step handed its caller
+        l_sc, l_cnt, l_st = plan.step_result
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "scores.npy"), np.array(gathered, dtype=np.float32))
+        np.save(os.path.join(args.dump_outputs, "list_lengths.npy"), l_cnt.astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "status.npy"), l_st.astype(np.float64))
     if cpu_rehearsal:
         assert np.array_equal(gathered, np.arange(n_total, dtype=np.float32)), "the gather misplaced a rank's block"
     if comm is not None:
         assert gathers[0] == steps_run[0], "not one gather per step"
-    pins = {} if cpu_rehearsal else pinned_scores(rank, args.pairs, args.length)
-    for p, want in pins.items():
-        assert np.float32(all_sc[p]).view(np.uint32) == np.float32(want).view(np.uint32), "pair %d: score %r, reference %r" % (p, all_sc[p], want)
+    all_sc, pins = None, {}
+    if args.full:
+        # parity inside the bench: every resident copy of a sub-batch gives identical scores, and the pairs the REAL reference
+        # was run on (tests/golden/full_cases.json) score exactly what it scored
+        ref_sc = {}
+        for (sidx, h), bt in units.items():
+            bt.reevaluate()
+            s_b, _, st_b = bt.optimal(want_pairs=False)
+            assert (st_b == 0).all()
+            if h not in ref_sc:
+                ref_sc[h] = np.array(s_b, copy=True)
+            else:
+                assert np.array_equal(ref_sc[h], s_b), "resident copies of a sub-batch disagree"
+        all_sc = np.concatenate([ref_sc[h] for h in range(split)])
+        assert np.array_equal(gathered[rank * args.pairs:(rank + 1) * args.pairs].view(np.uint32), all_sc.view(np.uint32)), "gathered scores differ"
+        pins = {} if cpu_rehearsal else pinned_scores(rank, args.pairs, args.length)
+        for p, want in pins.items():
+            assert np.float32(all_sc[p]).view(np.uint32) == np.float32(want).view(np.uint32), "pair %d: score %r, reference %r" % (p, all_sc[p], want)
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearse else dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -603,21 +625,22 @@ def rank_main(args):
         return
 
     # this box's plain streaming-store rate (torch fill of 8 GiB, HIP events on the same stream): what "HBM-write bound"
-    # can mean on this device today; boxes of the pool differ by ~20 % on it
+    # can mean on this device today; boxes of the pool differ by ~20 % on it (--full only: a run of its own)
     fill_gbs = None
-    try:
-        buf = torch.empty(2 << 30, dtype=torch.float32, device=dev)
-        buf.fill_(1.0)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(3):
-            buf.fill_(2.0)
-        e1.record()
-        torch.cuda.synchronize(dev)
-        fill_gbs = 3 * buf.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-        del buf
-    except Exception:
-        pass
+    if args.full:
+        try:
+            buf = torch.empty(2 << 30, dtype=torch.float32, device=dev)
+            buf.fill_(1.0)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(3):
+                buf.fill_(2.0)
+            e1.record()
+            torch.cuda.synchronize(dev)
+            fill_gbs = 3 * buf.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+            del buf
+        except Exception:
+            pass
 
     first_of = {}
     for (sidx, h), bt in units.items():
@@ -637,7 +660,7 @@ def rank_main(args):
     # ---- end to end, pipelined (rank 0, one GPU): three resident batches of all the pairs take turns, one launch sequence each;
     # every launch also encodes + uploads its residues and brings the gapped lines + identities of its pairs back to the host -------
     e2e_pipe = None
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         ep = Plan(3, 1)
         ep.e2e = True
         e2e_cal = {}
@@ -667,7 +690,7 @@ def rank_main(args):
     # kernel_only = the DP kernel's own duration (HIP events on its stream), the number `rocprofv3 --kernel-trace --stats` reports for
     # the same launch (profiles/r03_lone_kernel_stats.csv); lone_step = the whole step (DP + corner + find_max + traceback + results)
     lone = None
-    if args.lone_steps > 0:
+    if args.full and args.lone_steps > 0:
         c0 = ctxs[0]
         c0.set_hint("tag_occupancy", 0)                     # the library's own rule for a lone launch of this size
         c0.set_hint("tag_alt_prio", 1)
@@ -758,10 +781,10 @@ def rank_main(args):
                                       "whole_step_ms adds corner + find_max + traceback + results to the host" % args.pairs}
     if args.trace_steps:
         out["step_stamps_ms"] = stamps
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         out["end_to_end"] = end_to_end(aln_amd, ctxs, qs, ts, alphabet, table, mode, gi, ge, all_sc, args.pairs, e2e_pipe, 3, 1)
         out["secondary"] = secondary_configs(aln_amd, ctxs[0], alphabet, table, qs, ts, args.length)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(qs, ts, mode, gi, ge)
     if rank == 0:
         print(json.dumps(out), flush=True)

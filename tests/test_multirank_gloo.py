@@ -93,7 +93,9 @@ def test_sorted_deal_is_a_balanced_permutation():
 
 
 def test_two_rank_gather_equals_single_process():
-    import torch.multiprocessing as mp
+    # the standard library's spawn context: torch is imported by the ranks only.  torch brings its own copies of the HIP and HSA
+    # runtimes; loaded beside the ones libalnhip.so uses (in a run of the whole suite), both are torn down at exit and it aborts
+    import multiprocessing as mp
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     sys.path.insert(0, os.path.join(ROOT, "alignment-algos_amd"))
     import orc

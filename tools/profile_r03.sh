@@ -10,7 +10,7 @@
 set -e
 cd "$GRAFT_REPO_ROOT"
 TAGS="${@:-lone b42 b21 c3 c4 c5 sec}"
-B="--steps 10 --warmup 3 --no-secondary --no-cpu-baseline --lone-steps 0"
+B="--full --steps 10 --warmup 3 --no-secondary --no-cpu-baseline --lone-steps 0"
 for t in $TAGS; do
   case $t in
     lone) tools/profile.sh r03_lone -- python3 bench.py $B --streams 1 --split 1 --occupancy 2 --alt-prio 1 ;;
