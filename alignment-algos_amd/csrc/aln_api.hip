@@ -276,7 +276,10 @@ int upload_submatrix(aln_batch* b, const aln_submatrix* sub) {
   for (int i = 0; i < 32 * 32; ++i) { tf[i] = 0.f; ti[i] = 0; }
   for (int i = 0; i < sub->n; ++i)
     for (int j = 0; j < sub->n; ++j) {
-      tf[i * 32 + j] = sub->table[i * sub->n + j];
+      // a -0.0 entry goes to the device as +0.0: every score of the recurrence starts from +0.0 and x + (-0.0) == x + (+0.0) for every
+      // x but -0.0, so the reference never produces a -0.0 score.  The exact-order kernels did (first column, non-local builds): their
+      // "s = 0.f; s -= gap; s += sim" is lowered to one v_add_f32 of -gap and sim (aln_device.h dev_sim).  Not a no-op: keep the + 0.0f.
+      tf[i * 32 + j] = sub->table[i * sub->n + j] + 0.0f;
       ti[i * 32 + j] = (int32_t)sub->table[i * sub->n + j];
     }
   b->h_table.assign(sub->table, sub->table + sub->n * sub->n);

@@ -89,7 +89,11 @@ __device__ __forceinline__ float dev_sim(const EvalDev& e, int i, int j) {
     if (i <= 0 || j <= 0 || i >= e.Q - 1 || j >= e.T - 1) return 0.f;
     return e.tablef[(int)e.qc[i] * 32 + (int)e.tc[j]];
   }
-  return e.S[(size_t)i * e.ld + j];
+  // + 0.0f: a -0.0 element counts as +0.0 (as the table's entries do, upload_submatrix).  The reference never produces a -0.0 score:
+  // every score starts from +0.0 and x + (-0.0) == x + (+0.0) for every x but -0.0.  The kernels write "s = 0.f; s -= gap; s += sim"
+  // like the reference, but the compiler lowers that to one v_add_f32 of -gap and sim (it folds 0 - x + y), which gives -0.0 for a free
+  // gap and a -0.0 similarity (first row / column of non-local builds).  Do not remove the addition as a no-op.
+  return e.S[(size_t)i * e.ld + j] + 0.0f;
 }
 
 // A build rectangle and direction: frame coordinates (a,b) run from the origin (0,0) = (q0,t0) forward /
