@@ -62,6 +62,12 @@ class AlnAlignment(C.Structure):
     _fields_ = [("score", C.c_float), ("identity", C.c_float), ("uid", C.c_int32), ("n_pairs", C.c_int32), ("pair_off", C.c_int64)]
 
 
+class AlnHit(C.Structure):
+    _fields_ = [("t", C.c_int32), ("score", C.c_float), ("q_end", C.c_int32), ("t_end", C.c_int32)]
+
+
+HIT_DTYPE = np.dtype([("t", np.int32), ("score", np.float32), ("q_end", np.int32), ("t_end", np.int32)])
+
 EXPORTS = [
     "aln_ctx_create", "aln_ctx_destroy", "aln_error_string", "aln_last_error", "aln_ctx_synchronize", "aln_has_gfx950",
     "aln_batch_create", "aln_batch_destroy", "aln_batch_n_pairs", "aln_batch_device_bytes", "aln_batch_dp",
@@ -70,7 +76,7 @@ EXPORTS = [
     "aln_gapped_length", "aln_gapped_strings", "aln_hmap2_gap_arrays", "aln_score_all_vs_all", "aln_batch_last_dp_ms", "aln_batch_dp_ms_history", "aln_batch_dp_algorithmic_bytes", "aln_batch_cells",
     "aln_batch_optimal_strings", "aln_batch_optimal_strings_enqueue", "aln_batch_optimal_strings_collect", "aln_batch_last_exact_stats", "aln_batch_set_gap", "aln_ctx_set_hint", "aln_ctx_get_hint", "aln_batch_dp_contract_bytes", "aln_batch_plane_bytes_per_cell",
     "aln_deal_units", "aln_comm_unique_id", "aln_comm_create", "aln_ctx_create_multi", "aln_comm_destroy", "aln_comm_n_ranks",
-    "aln_comm_last_error", "aln_gather_scores",
+    "aln_comm_last_error", "aln_gather_scores", "aln_search_topk",
 ]
 COMM_ID_BYTES = 128
 
@@ -134,6 +140,8 @@ def lib():
         L.aln_batch_dp_ms_history.argtypes = [C.c_void_p, _fp, C.c_int32]
         L.aln_score_all_vs_all.argtypes = [C.c_void_p, C.POINTER(AlnSeqs), C.POINTER(AlnSeqs), C.POINTER(AlnSubmatrix), C.POINTER(AlnGap),
                                            C.c_int32, C.c_int32, _fp]
+        L.aln_search_topk.argtypes = [C.c_void_p, C.POINTER(AlnSeqs), C.POINTER(AlnSeqs), C.POINTER(AlnSubmatrix), C.POINTER(AlnGap),
+                                      C.c_int32, C.c_int32, C.c_int32, C.c_float, C.POINTER(AlnHit), _ip]
         L.aln_hmap2_gap_arrays.argtypes = [_fp, C.c_int64, C.c_float, C.c_float, C.c_float, _fp, _fp]
         L.aln_batch_plane_bytes_per_cell.argtypes = [C.c_void_p]
         L.aln_batch_optimal_strings.argtypes = [C.c_void_p, _fp, _fp, _ip, C.c_char_p, C.c_char_p, C.c_int32, _ip]
@@ -244,6 +252,48 @@ def score_all_vs_all(ctx, queries, templates, alphabet, table, gi, ge, q_begin=0
     out = np.empty((q_end - q_begin, len(tpool.seqs)), dtype=np.float32)
     _check(lib().aln_score_all_vs_all(ctx.h, C.byref(qpool.c), C.byref(tpool.c), C.byref(sub), C.byref(g), q_begin, q_end, _f(out)), ctx.h)
     return out
+
+
+def search_topk(ctx, queries, templates, alphabet, table, gi, ge, K, min_score=-np.inf, q_begin=0, q_end=None, align_type=LOCAL):
+    """aln_search_topk: for queries[q_begin:q_end] the K best templates with score >= min_score (score descending, ties by
+    template index), selected on the device.  -> hits[rows, K] (fields t, score, q_end, t_end; unused slots -1, 0, -1, -1),
+    n_hits[rows]."""
+    qpool = queries if isinstance(queries, SeqPool) else SeqPool(queries)
+    tpool = templates if isinstance(templates, SeqPool) else SeqPool(templates)
+    if q_end is None:
+        q_end = len(qpool.seqs)
+    tab = np.ascontiguousarray(table, dtype=np.float32)
+    ab = alphabet.encode()
+    sub = AlnSubmatrix(len(alphabet), ab, _f(tab))
+    g = AlnGap()
+    g.model = GAP_AFFINE_CONST
+    g.align_type = int(align_type)
+    g.gap_init = float(np.float32(gi))
+    g.gap_extn = float(np.float32(ge))
+    rows = max(q_end - q_begin, 0)
+    hits = np.zeros((rows, max(int(K), 0)), dtype=HIT_DTYPE)
+    n_hits = np.zeros(rows, dtype=np.int32)
+    _check(lib().aln_search_topk(ctx.h, C.byref(qpool.c), C.byref(tpool.c), C.byref(sub), C.byref(g), q_begin, q_end, int(K),
+                                 float(min_score), hits.ctypes.data_as(C.POINTER(AlnHit)), _i(n_hits)), ctx.h)
+    return hits, n_hits
+
+
+def align_hits(ctx, queries, templates, hits, n_hits, alphabet, table, gi, ge, q_begin=0, align_type=LOCAL):
+    """The "align what matters" half of a search: one resident Batch over the valid hits of search_topk (row-major hit order),
+    full builds + Optimal.  Host glue only.  -> scores[n], list of n pair arrays."""
+    rows, slots = np.nonzero(np.arange(hits.shape[1])[None, :] < np.asarray(n_hits)[:, None])
+    if len(rows) == 0:
+        return np.empty(0, dtype=np.float32), []
+    b = Batch(ctx, queries, templates, rows + q_begin, hits["t"][rows, slots])
+    try:
+        b.dp_submatrix(alphabet, table, align_type, gi, ge)
+        scores, lists, status = b.optimal()
+    finally:
+        b.close()
+    bad = np.nonzero(status)[0]
+    if len(bad):
+        _check(int(status[bad[0]]), ctx.h)
+    return scores, lists
 
 
 class Batch:

@@ -38,6 +38,8 @@ const HintDef kDefs[] = {
     {"exact_wavefront", "ALN_EXACT_WAVEFRONT", false, &aln_hints::exact_wavefront},
     {"exact_debug", "ALN_EXACT_DEBUG", false, &aln_hints::exact_debug},
     {"score_packed", "ALN_SCORE_NO_PACKED", true, &aln_hints::score_packed},
+    {"search_slab_rows", "ALN_SEARCH_SLAB_ROWS", false, &aln_hints::search_slab_rows},
+    {"search_debug", "ALN_SEARCH_DEBUG", false, &aln_hints::search_debug},
     {"enum_heavy_first", "ALN_ENUM_HEAVY_FIRST", false, &aln_hints::enum_heavy_first},
     {"enum_pool_retries", "ALN_ENUM_POOL_RETRIES", false, &aln_hints::enum_pool_retries},
     {"enum_waves", "ALN_ENUM_WAVES", false, &aln_hints::enum_waves},

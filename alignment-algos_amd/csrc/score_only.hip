@@ -16,37 +16,9 @@
 #include <cstdlib>
 #include <vector>
 
-#include "aln_internal.h"
+#include "score_common.h"
 
 namespace aln {
-
-constexpr int kNegS = -(1 << 28);
-
-template <int CTRL, int ROW_MASK = 0xF, int BANK_MASK = 0xF>
-__device__ __forceinline__ int sdpp(int old, int src) {
-  return __builtin_amdgcn_update_dpp(old, src, CTRL, ROW_MASK, BANK_MASK, false);
-}
-__device__ __forceinline__ int wave_incl_max_s(int v) {
-  const int ident = (int)0x80000000;
-  v = max(v, sdpp<0x111>(ident, v));
-  v = max(v, sdpp<0x112>(ident, v));
-  v = max(v, sdpp<0x114>(ident, v));
-  v = max(v, sdpp<0x118>(ident, v));
-  v = max(v, sdpp<0x142, 0xA>(ident, v));
-  v = max(v, sdpp<0x143, 0xC>(ident, v));
-  return v;
-}
-
-struct ScoreArgs {
-  const uint8_t* qcodes; const int64_t* qoff;   // query pool, offsets (n_q + 1)
-  const uint8_t* tcodes; const int64_t* toff;   // template pool
-  const int32_t* table32;                       // 32 x 32
-  const int32_t* tsel;                          // blockIdx.x -> template index (templates are launched by length class)
-  const int32_t* qsel;                          // packed kernel: query rows of the slab sorted by length (neighbours share a wave)
-  float* scores;                                // rows x n_t
-  int q_begin, n_t;
-  int gi, ge;
-};
 
 template <int R>
 __global__ __launch_bounds__(64) void score_local_kernel(ScoreArgs a) {
@@ -489,17 +461,14 @@ __global__ __launch_bounds__(64) void score_local_pk_kernel(ScoreArgs a, int n_r
   }
 }
 
-}  // namespace aln
-
-using namespace aln;
-
-// The general route: scores[(q - q_begin) * n_t + t] for the templates listed in `tlist`, through resident batches of full
+// The general route: scores[(q - q_begin) * ld + col[t]] for the templates listed in `tlist`, through resident batches of full
 // DP builds (aln_batch_dp picks the kernel: tagged keys, int32 rows, exact-order scans) + Optimal's score — what the reference does
 // for every pair, kept for what the register-resident kernels above do not take: templates beyond 2048 columns, fractional tables
 // or gaps.  Pairs are grouped so that one group's planes stay below ~12 GB.
-static int score_through_batches(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
-                                 const aln_gap* gap, int32_t q_begin, int32_t q_end, const std::vector<int32_t>& tlist, float* scores) {
-  const int n_t = templates->n_seqs;
+int score_through_batches(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
+                          const aln_gap* gap, int32_t q_begin, int32_t q_end, const std::vector<int32_t>& tlist, float* scores,
+                          const int32_t* col, size_t ld) {
+  if (ld == 0) ld = (size_t)templates->n_seqs;
   const size_t budget = (size_t)12 << 30;
   aln_sim sim = aln_sim();
   sim.kind = ALN_SIM_SUBMATRIX;
@@ -518,7 +487,7 @@ static int score_through_batches(aln_ctx* ctx, const aln_seqs* queries, const al
     if (rc != ALN_OK) return rc;
     for (size_t k = 0; k < qi.size(); ++k) {
       if (st[k] != 0) return st[k];
-      scores[(size_t)(qi[k] - q_begin) * n_t + tix[k]] = sc[k];
+      scores[(size_t)(qi[k] - q_begin) * ld + (col ? col[tix[k]] : tix[k])] = sc[k];
     }
     qi.clear(); tix.clear();
     return ALN_OK;
@@ -536,36 +505,34 @@ static int score_through_batches(aln_ctx* ctx, const aln_seqs* queries, const al
   return flush();
 }
 
-// The score Optimal reports for queries[q_begin .. q_end) against every template: scores[(q - q_begin) * n_t + t].
-// Replaces (q_end - q_begin) x n_t constructions of DPMatrix(q, t, AASubstitutionEval, fwd, align_type) + Optimal(align_type):
-// find_max for local alignments, the final cell's score for the four other align types.
-extern "C" int aln_score_all_vs_all(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
-                                    const aln_gap* gap, int32_t q_begin, int32_t q_end, float* scores) {
-  if (!ctx || !queries || !templates || !sub || !gap || !scores) return ALN_E_ARG;
+int ScoreRun::prepare(aln_ctx* ctx_, const aln_seqs* queries_, const aln_seqs* templates_, const aln_submatrix* sub_,
+                      const aln_gap* gap_, int32_t q_begin_, int32_t q_end_) {
+  ctx = ctx_; queries = queries_; templates = templates_; sub = sub_; gap = gap_; q_begin = q_begin_; q_end = q_end_;
+  route = kNothing;
+  if (!ctx || !queries || !templates || !sub || !gap) return ALN_E_ARG;
   if (q_begin < 0 || q_end > queries->n_seqs || q_begin > q_end) return ALN_E_ARG;
   if (gap->model != ALN_GAP_AFFINE_CONST || gap->align_type < 0 || gap->align_type > 4) return ALN_E_ARG;
-  const bool local = gap->align_type == ALN_LOCAL;
-  const int free_del = (gap->align_type == ALN_LOCAL || gap->align_type == ALN_SEMI_LOCAL || gap->align_type == ALN_LOCAL_GLOBAL);
-  const int free_ins = (gap->align_type == ALN_LOCAL || gap->align_type == ALN_SEMI_LOCAL || gap->align_type == ALN_GLOBAL_LOCAL);
+  local = gap->align_type == ALN_LOCAL;
+  free_del = (gap->align_type == ALN_LOCAL || gap->align_type == ALN_SEMI_LOCAL || gap->align_type == ALN_LOCAL_GLOBAL);
+  free_ins = (gap->align_type == ALN_LOCAL || gap->align_type == ALN_SEMI_LOCAL || gap->align_type == ALN_GLOBAL_LOCAL);
   if (!sub->alphabet || !sub->table || sub->n < 1 || sub->n > 30) return ALN_E_ARG;
   ALN_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const float gi = gap->gap_init, ge = gap->gap_extn;
-  std::vector<int32_t> every_t((size_t)templates->n_seqs);
-  for (int t = 0; t < templates->n_seqs; ++t) every_t[t] = t;
-  if (q_begin == q_end || templates->n_seqs == 0) return ALN_OK;
+  rows = q_end - q_begin; n_t = templates->n_seqs;
+  every_t.resize((size_t)n_t);
+  for (int t = 0; t < n_t; ++t) every_t[t] = t;
+  if (q_begin == q_end || n_t == 0) return ALN_OK;
   // fractional gaps or table values: full builds in the exact-order kernels (the reference's arithmetic), batch by batch
-  if (!(gi == (float)(int)gi) || !(ge == (float)(int)ge) || gi < 0 || ge < 0)
-    return score_through_batches(ctx, queries, templates, sub, gap, q_begin, q_end, every_t, scores);
+  if (!(gi == (float)(int)gi) || !(ge == (float)(int)ge) || gi < 0 || ge < 0) { route = kAllFull; return ALN_OK; }
   int idx[256];
   for (int i = 0; i < 256; ++i) idx[i] = -1;
   for (int i = 0; i < sub->n; ++i) idx[(unsigned char)sub->alphabet[i]] = i;
-  int32_t ti[32 * 32];
-  double maxs = 0;
+  maxs = 0;
   for (int i = 0; i < 32 * 32; ++i) ti[i] = 0;
   for (int i = 0; i < sub->n; ++i)
     for (int j = 0; j < sub->n; ++j) {
       float v = sub->table[i * sub->n + j];
-      if (!(v == (float)(int)v)) return score_through_batches(ctx, queries, templates, sub, gap, q_begin, q_end, every_t, scores);
+      if (!(v == (float)(int)v)) { route = kAllFull; return ALN_OK; }
       ti[i * 32 + j] = (int32_t)v;
       maxs = std::max(maxs, fabs((double)v));
     }
@@ -586,80 +553,93 @@ extern "C" int aln_score_all_vs_all(aln_ctx* ctx, const aln_seqs* queries, const
     }
     return ALN_OK;
   };
-  std::vector<uint8_t> qc, tc;
-  int maxQ = 0, maxT = 0, rc;
+  int rc;
   if ((rc = encode(queries, qc, maxQ)) != ALN_OK) return rc;
   if ((rc = encode(templates, tc, maxT)) != ALN_OK) return rc;
   if (maxT > kMaxLen || maxQ > kMaxLen) return ALN_E_TOO_LONG;
-  if ((maxs + ge) * ((double)maxQ + std::min(maxT, 2048)) + gi + maxs >= 8388608.0)
-    return score_through_batches(ctx, queries, templates, sub, gap, q_begin, q_end, every_t, scores);
-  const int rows = q_end - q_begin, n_t = templates->n_seqs;
-  if (rows == 0 || n_t == 0) return ALN_OK;
-
-  ScoreArgs a = {};
-  uint8_t *dq = nullptr, *dt = nullptr; int64_t *dqo = nullptr, *dto = nullptr; int32_t* dtab = nullptr; float* dsc = nullptr; int32_t* dsel = nullptr; int32_t* dqsel = nullptr;
-  auto cleanup = [&]() { hipFree(dq); hipFree(dt); hipFree(dqo); hipFree(dto); hipFree(dtab); hipFree(dsc); hipFree(dsel); hipFree(dqsel); };
-#define STRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(e_); cleanup(); return ALN_E_HIP; } } while (0)
-  STRY(hipMalloc((void**)&dq, qc.size())); STRY(hipMalloc((void**)&dt, tc.size()));
-  STRY(hipMalloc((void**)&dqo, (size_t)(queries->n_seqs + 1) * 8)); STRY(hipMalloc((void**)&dto, (size_t)(n_t + 1) * 8));
-  STRY(hipMalloc((void**)&dtab, sizeof ti)); STRY(hipMalloc((void**)&dsc, (size_t)rows * n_t * 4));
-  STRY(hipMemcpyAsync(dq, qc.data(), qc.size(), hipMemcpyHostToDevice, ctx->stream));
-  STRY(hipMemcpyAsync(dt, tc.data(), tc.size(), hipMemcpyHostToDevice, ctx->stream));
-  STRY(hipMemcpyAsync(dqo, queries->offsets, (size_t)(queries->n_seqs + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  STRY(hipMemcpyAsync(dto, templates->offsets, (size_t)(n_t + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  STRY(hipMemcpyAsync(dtab, ti, sizeof ti, hipMemcpyHostToDevice, ctx->stream));
-  a.qcodes = dq; a.qoff = dqo; a.tcodes = dt; a.toff = dto; a.table32 = dtab; a.scores = dsc;
-  a.q_begin = q_begin; a.n_t = n_t; a.gi = (int)gi; a.ge = (int)ge;
+  if ((maxs + ge) * ((double)maxQ + std::min(maxT, 2048)) + gi + maxs >= 8388608.0) { route = kAllFull; return ALN_OK; }
+  route = kFast;
   // Templates are launched by length class: a wave sweeps 256 R columns, so a template of T columns needs
   // R = ceil(T / 256) groups; one launch per class keeps short templates from paying for the longest one.
-  std::vector<int32_t> order, long_t; std::vector<int> cls_begin(10, 0);
+  cls_begin.assign(10, 0);
   {
     std::vector<std::vector<int32_t>> by(9);
     for (int t = 0; t < n_t; ++t) {
       const int T = (int)(templates->offsets[t + 1] - templates->offsets[t]);
-      if (T > 2048) long_t.push_back(t);            // beyond the register-resident kernels: full builds below
+      if (T > 2048) long_t.push_back(t);            // beyond the register-resident kernels: full builds
       else by[(T + 255) / 256].push_back(t);
     }
     for (int r = 1; r <= 8; ++r) { cls_begin[r] = (int)order.size(); order.insert(order.end(), by[r].begin(), by[r].end()); }
     cls_begin[9] = (int)order.size();
   }
-  STRY(hipMalloc((void**)&dsel, (size_t)n_t * 4));
-  if (!order.empty()) STRY(hipMemcpyAsync(dsel, order.data(), order.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   // packed 16-bit lanes (two queries per wave) when every intermediate provably fits: best local score <= maxs * min(Q,T),
   // A keys add ge * column, the "minus infinity" -12000 must stay below every real candidate and clear of wrap-around
   const int fastT = std::min(maxT, 2048);                // (longer templates do not run in these kernels)
   const double L = (double)std::max(maxQ, fastT), best = maxs * (double)std::min(maxQ, fastT);
-  const bool packed = local && best + ge * L + maxs < 30000.0 && ge * L + gi + maxs < 8000.0 && maxs < 2048.0 && ctx->hints.score_packed;
+  packed = local && best + ge * L + maxs < 30000.0 && ge * L + gi + maxs < 8000.0 && maxs < 2048.0 && ctx->hints.score_packed;
+  return ALN_OK;
+}
+
+void ScoreRun::release() {
+  hipFree(dq); hipFree(dt); hipFree(dqo); hipFree(dto); hipFree(dtab); hipFree(dsel); hipFree(dqsel);
+  dq = dt = nullptr; dqo = dto = nullptr; dtab = dsel = dqsel = nullptr;
+}
+
+#define STRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(e_); hipStreamSynchronize(ctx->stream); release(); return ALN_E_HIP; } } while (0)
+
+int ScoreRun::upload_offsets() {
+  STRY(hipMalloc((void**)&dqo, (size_t)(queries->n_seqs + 1) * 8)); STRY(hipMalloc((void**)&dto, (size_t)(n_t + 1) * 8));
+  STRY(hipMemcpyAsync(dqo, queries->offsets, (size_t)(queries->n_seqs + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+  STRY(hipMemcpyAsync(dto, templates->offsets, (size_t)(n_t + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+  return ALN_OK;
+}
+
+int ScoreRun::upload() {
+  STRY(hipMalloc((void**)&dq, qc.size())); STRY(hipMalloc((void**)&dt, tc.size()));
+  STRY(hipMalloc((void**)&dtab, sizeof ti));
+  STRY(hipMemcpyAsync(dq, qc.data(), qc.size(), hipMemcpyHostToDevice, ctx->stream));
+  STRY(hipMemcpyAsync(dt, tc.data(), tc.size(), hipMemcpyHostToDevice, ctx->stream));
+  int rc = upload_offsets();
+  if (rc != ALN_OK) return rc;
+  STRY(hipMemcpyAsync(dtab, ti, sizeof ti, hipMemcpyHostToDevice, ctx->stream));
+  a.qcodes = dq; a.qoff = dqo; a.tcodes = dt; a.toff = dto; a.table32 = dtab;
+  a.q_begin = q_begin; a.n_t = n_t; a.gi = (int)gap->gap_init; a.ge = (int)gap->gap_extn;
+  STRY(hipMalloc((void**)&dsel, (size_t)n_t * 4));
+  if (!order.empty()) STRY(hipMemcpyAsync(dsel, order.data(), order.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (packed) STRY(hipMalloc((void**)&dqsel, (size_t)rows * 4));
+  return ALN_OK;
+}
+
+int ScoreRun::launch(int row0, int nrows, float* dscores) {
   const dim3 block(64);
   // blockIdx.y is limited to 65535: walk the query rows in slabs.  The packed kernel pairs queries of similar length (a wave
-  // runs to the longer one's last row): every slab's length order goes to the device ONCE, before the first launch, into its own
+  // runs to the longer one's last row): every slab's length order goes to the device before the slab's first launch, into its own
   // region of dqsel (slab starting at row r0 -> dqsel + r0), so no launch can see another slab's order (the kernels run
-  // asynchronously on ctx->stream) and the host vector lives until the final synchronisation.
-  std::vector<int32_t> qo_all;
+  // asynchronously on ctx->stream) and the host vector lives until the caller's synchronisation.
   if (packed) {
-    qo_all.resize((size_t)rows);
-    for (int r0 = 0; r0 < rows; r0 += 32768) {
-      const int nr = std::min(32768, rows - r0);
+    qorders.emplace_back((size_t)nrows);
+    std::vector<int32_t>& qo_all = qorders.back();
+    for (int r0 = 0; r0 < nrows; r0 += 32768) {
+      const int nr = std::min(32768, nrows - r0);
       int32_t* qo = qo_all.data() + r0;
       for (int k = 0; k < nr; ++k) qo[k] = k;
       std::stable_sort(qo, qo + nr, [&](int32_t x, int32_t y) {
-        return queries->offsets[q_begin + r0 + x + 1] - queries->offsets[q_begin + r0 + x] <
-               queries->offsets[q_begin + r0 + y + 1] - queries->offsets[q_begin + r0 + y];
+        return queries->offsets[q_begin + row0 + r0 + x + 1] - queries->offsets[q_begin + row0 + r0 + x] <
+               queries->offsets[q_begin + row0 + r0 + y + 1] - queries->offsets[q_begin + row0 + r0 + y];
       });
     }
-    STRY(hipMalloc((void**)&dqsel, (size_t)rows * 4));
-    STRY(hipMemcpyAsync(dqsel, qo_all.data(), (size_t)rows * 4, hipMemcpyHostToDevice, ctx->stream));
+    STRY(hipMemcpyAsync(dqsel + row0, qo_all.data(), (size_t)nrows * 4, hipMemcpyHostToDevice, ctx->stream));
   }
-  for (int r0 = 0; r0 < rows; r0 += 32768) {
-    const int nr = std::min(32768, rows - r0);
+  for (int r0 = 0; r0 < nrows; r0 += 32768) {
+    const int nr = std::min(32768, nrows - r0);
     for (int r = 1; r <= 8; ++r) {
       const int nc = cls_begin[r + 1] - cls_begin[r];
       if (nc == 0) continue;
       ScoreArgs s = a;
-      s.q_begin = q_begin + r0;
-      s.scores = dsc + (size_t)r0 * n_t;
+      s.q_begin = q_begin + row0 + r0;
+      s.scores = dscores + (size_t)r0 * n_t;
       s.tsel = dsel + cls_begin[r];
-      s.qsel = dqsel ? dqsel + r0 : nullptr;
+      s.qsel = dqsel ? dqsel + row0 + r0 : nullptr;
       if (packed) {
         const dim3 grid(nc, (nr + 1) / 2);             // two query rows per wave
         switch (r) {
@@ -685,25 +665,49 @@ extern "C" int aln_score_all_vs_all(aln_ctx* ctx, const aln_seqs* queries, const
           default: hipLaunchKernelGGL(score_global_kernel<8>, grid, block, 0, ctx->stream, s, free_del, free_ins); break;
         }
       } else {
-      const dim3 grid(nc, nr);
-      switch (r) {
-        case 1: hipLaunchKernelGGL(score_local_kernel<1>, grid, block, 0, ctx->stream, s); break;
-        case 2: hipLaunchKernelGGL(score_local_kernel<2>, grid, block, 0, ctx->stream, s); break;
-        case 3: hipLaunchKernelGGL(score_local_kernel<3>, grid, block, 0, ctx->stream, s); break;
-        case 4: hipLaunchKernelGGL(score_local_kernel<4>, grid, block, 0, ctx->stream, s); break;
-        case 5: hipLaunchKernelGGL(score_local_kernel<5>, grid, block, 0, ctx->stream, s); break;
-        case 6: hipLaunchKernelGGL(score_local_kernel<6>, grid, block, 0, ctx->stream, s); break;
-        case 7: hipLaunchKernelGGL(score_local_kernel<7>, grid, block, 0, ctx->stream, s); break;
-        default: hipLaunchKernelGGL(score_local_kernel<8>, grid, block, 0, ctx->stream, s); break;
-      }
+        const dim3 grid(nc, nr);
+        switch (r) {
+          case 1: hipLaunchKernelGGL(score_local_kernel<1>, grid, block, 0, ctx->stream, s); break;
+          case 2: hipLaunchKernelGGL(score_local_kernel<2>, grid, block, 0, ctx->stream, s); break;
+          case 3: hipLaunchKernelGGL(score_local_kernel<3>, grid, block, 0, ctx->stream, s); break;
+          case 4: hipLaunchKernelGGL(score_local_kernel<4>, grid, block, 0, ctx->stream, s); break;
+          case 5: hipLaunchKernelGGL(score_local_kernel<5>, grid, block, 0, ctx->stream, s); break;
+          case 6: hipLaunchKernelGGL(score_local_kernel<6>, grid, block, 0, ctx->stream, s); break;
+          case 7: hipLaunchKernelGGL(score_local_kernel<7>, grid, block, 0, ctx->stream, s); break;
+          default: hipLaunchKernelGGL(score_local_kernel<8>, grid, block, 0, ctx->stream, s); break;
+        }
       }
       STRY(hipGetLastError());
     }
   }
+  return ALN_OK;
+}
+#undef STRY
+
+}  // namespace aln
+
+using namespace aln;
+
+// The score Optimal reports for queries[q_begin .. q_end) against every template: scores[(q - q_begin) * n_t + t].
+// Replaces (q_end - q_begin) x n_t constructions of DPMatrix(q, t, AASubstitutionEval, fwd, align_type) + Optimal(align_type):
+// find_max for local alignments, the final cell's score for the four other align types.
+extern "C" int aln_score_all_vs_all(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
+                                    const aln_gap* gap, int32_t q_begin, int32_t q_end, float* scores) {
+  if (!scores) return ALN_E_ARG;
+  ScoreRun run;
+  int rc = run.prepare(ctx, queries, templates, sub, gap, q_begin, q_end);
+  if (rc != ALN_OK || run.route == ScoreRun::kNothing) return rc;
+  if (run.route == ScoreRun::kAllFull) return score_through_batches(ctx, queries, templates, sub, gap, q_begin, q_end, run.every_t, scores);
+  const int rows = run.rows, n_t = run.n_t;
+  float* dsc = nullptr;
+#define STRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(e_); hipFree(dsc); return ALN_E_HIP; } } while (0)
+  STRY(hipMalloc((void**)&dsc, (size_t)rows * n_t * 4));
+  if ((rc = run.upload()) != ALN_OK || (rc = run.launch(0, rows, dsc)) != ALN_OK) { hipFree(dsc); return rc; }
   STRY(hipMemcpyAsync(scores, dsc, (size_t)rows * n_t * 4, hipMemcpyDeviceToHost, ctx->stream));
   STRY(hipStreamSynchronize(ctx->stream));
 #undef STRY
-  cleanup();
-  if (!long_t.empty()) return score_through_batches(ctx, queries, templates, sub, gap, q_begin, q_end, long_t, scores);
+  hipFree(dsc);
+  run.release();
+  if (!run.long_t.empty()) return score_through_batches(ctx, queries, templates, sub, gap, q_begin, q_end, run.long_t, scores);
   return ALN_OK;
 }

@@ -176,7 +176,7 @@ int aln_ctx_synchronize(aln_ctx* ctx);
 int aln_has_gfx950(void);
 /* Tuning / kernel-selection hints of ONE context.  A context reads its defaults from the environment once, when it is created
  * (ALN_NO_TAG_KERNEL, ALN_NO_H16, ALN_NO_KEY16, ALN_TAG_ALT_PRIO, ALN_TAG_SEGMENTS, ALN_DP_VARIANT="NW,R[,X]", ALN_EXACT_NO_TILES,
- * ALN_EXACT_LITERAL, ALN_EXACT_ALT_PRIO, ALN_SCORE_NO_PACKED, ALN_ENUM_NODE_CAP, ALN_TAG_LAG, ALN_TAG_SOLO, ALN_TAG_BITS, ALN_TAG_OCCUPANCY, ALN_PLANE_ROW_ALIGN, ALN_ENUM_POOL_RETRIES, ALN_ENUM_WAVES, ALN_ENUM_DEBUG, ALN_ENUM_KEEP_POOLS); launches never read the environment.  Keys:
+ * ALN_EXACT_LITERAL, ALN_EXACT_ALT_PRIO, ALN_SCORE_NO_PACKED, ALN_ENUM_NODE_CAP, ALN_TAG_LAG, ALN_TAG_SOLO, ALN_TAG_BITS, ALN_TAG_OCCUPANCY, ALN_PLANE_ROW_ALIGN, ALN_ENUM_POOL_RETRIES, ALN_ENUM_WAVES, ALN_ENUM_DEBUG, ALN_ENUM_KEEP_POOLS, ALN_SEARCH_SLAB_ROWS, ALN_SEARCH_DEBUG); launches never read the environment.  Keys:
  *   "tag_kernel" "h16" "key16"     1/0: tagged-key kernel / uint16 score plane / 16-bit key layout allowed (results identical)
  *   "tag_alt_prio"                  1/0: row-alternating wave priority in the tagged kernel (a scheduling hint; pays when launches
  *                                   follow each other on one stream, loses when launches of several contexts overlap);
@@ -206,6 +206,9 @@ int aln_has_gfx950(void);
  *                                   (allocating tens of GB costs seconds); 0: frees them when it returns
  *   "enum_pool_retries"             aln_batch_enumerate_all: how often a pair whose pools overflowed is searched again with four
  *                                   times the capacity (default 2)
+ *   "search_slab_rows"              aln_search_topk: query rows whose scores are resident on the device at a time; 0 (default) = as many as
+ *                                   keep the slab's scores (4 B x n_templates per row) and hits (16 B x K per row) below 1 GiB each
+ *   "search_debug"                  1: aln_search_topk reports its slabs and the device time of scoring / selection / end cells on stderr
  * Unknown key -> ALN_E_ARG.  No hint changes any result. */
 int aln_ctx_set_hint(aln_ctx* ctx, const char* key, int64_t value);
 int aln_ctx_get_hint(const aln_ctx* ctx, const char* key, int64_t* value);
@@ -327,6 +330,28 @@ int aln_batch_last_enum_ms(aln_batch* b, float* search_ms, float* unroll_ms);
  * same call, ~12 GB of planes at a time; sequences beyond 65534 residues: ALN_E_TOO_LONG. */
 int aln_score_all_vs_all(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
                          const aln_gap* gap, int32_t q_begin, int32_t q_end, float* scores);
+
+/* ---- all-vs-all search: the K best templates of every query, with end cells, selected on the device ---------------- */
+/* One hit: template index, the score aln_score_all_vs_all reports for the pair (bit-identical), and the cell the optimal
+ * alignment ends in, sentinels counted.  Unused slots hold { -1, 0.0f, -1, -1 }. */
+typedef struct {
+  int32_t t;        /* template index, -1 = unused slot */
+  float   score;    /* bit-identical to aln_score_all_vs_all's value for (q, t) */
+  int32_t q_end, t_end;
+} aln_hit;
+/* For every query of queries[q_begin..q_end): the K best templates among those with score >= min_score (-INFINITY: no
+ * threshold), score descending, ties by template index ascending; n_hits[row] = min(K, candidates), hits[row * K + k].
+ * Stands for (q_end - q_begin) x n_templates DPMatrix + Optimal constructions followed by a sort on the host (the reference has
+ * no such driver); the dense score matrix never reaches the host, only hits and n_hits do.  Accepts what aln_score_all_vs_all
+ * accepts, with its argument checks and status codes; K in 1..1024, else ALN_E_ARG.  q_begin == q_end: ALN_OK, nothing written.
+ * (q_end, t_end): ALN_LOCAL — the cell Optimal::find_max returns (optimal.h:108-124: seeded at (Q-2, T-2), replaced only by a
+ * strictly greater score, rows then columns ascending; a pair whose best score is 0 reports the seed), i.e. the entry before
+ * the closing (Q-1, T-1) of aln_batch_optimal's pair list; the four other align types — (Q-1, T-1), where Optimal starts.
+ * Query rows are scored a slab at a time (hint "search_slab_rows"); a rank of a multi-GPU job passes its own block of
+ * rows and its hits are final (templates are replicated). */
+int aln_search_topk(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
+                    const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K, float min_score,
+                    aln_hit* hits /* (q_end-q_begin) x K */, int32_t* n_hits /* q_end-q_begin */);
 
 /* ---- multi-GPU: a length-sorted deal of independent units + ONE collective (RCCL all-gather of scores) ----------- */
 /* The reference is one thread, one DPMatrix at a time; pairs are independent (dpmatrix.h:104-111), so ranks own disjoint pair
