@@ -76,7 +76,7 @@ EXPORTS = [
     "aln_gapped_length", "aln_gapped_strings", "aln_hmap2_gap_arrays", "aln_score_all_vs_all", "aln_batch_last_dp_ms", "aln_batch_dp_ms_history", "aln_batch_dp_algorithmic_bytes", "aln_batch_cells",
     "aln_batch_optimal_strings", "aln_batch_optimal_strings_enqueue", "aln_batch_optimal_strings_collect", "aln_batch_last_exact_stats", "aln_batch_set_gap", "aln_ctx_set_hint", "aln_ctx_get_hint", "aln_batch_dp_contract_bytes", "aln_batch_plane_bytes_per_cell",
     "aln_deal_units", "aln_comm_unique_id", "aln_comm_create", "aln_ctx_create_multi", "aln_comm_destroy", "aln_comm_n_ranks",
-    "aln_comm_last_error", "aln_gather_scores", "aln_search_topk",
+    "aln_comm_last_error", "aln_gather_scores", "aln_gather_resident_enqueue", "aln_gather_resident_collect", "aln_search_topk",
 ]
 COMM_ID_BYTES = 128
 
@@ -159,6 +159,8 @@ def lib():
         L.aln_comm_last_error.argtypes = [C.c_void_p]
         L.aln_comm_last_error.restype = C.c_char_p
         L.aln_gather_scores.argtypes = [C.c_void_p, C.POINTER(_fp), C.POINTER(_ip), _ip, C.c_int32, _fp, C.c_int64]
+        L.aln_gather_resident_enqueue.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(_ip), _ip, C.c_int32, C.c_int64]
+        L.aln_gather_resident_collect.argtypes = [C.c_void_p, _fp, C.c_int64]
         _LIB = L
     return _LIB
 

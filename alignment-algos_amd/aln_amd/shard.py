@@ -1,5 +1,6 @@
 """Multi-GPU plumbing for the pair-sharded path — a thin binding of the C ABI's aln_deal_units /
-aln_comm_* / aln_gather_scores (csrc/aln_comm.hip: length-sorted deal, ONE RCCL all-gather of (index, score) records).
+aln_comm_* / aln_gather_scores / aln_gather_resident_* (csrc/aln_comm.hip: length-sorted deal, ONE RCCL all-gather of
+(index, score) records, from host arrays or straight from a resident batch).
 
 Pairs are independent, so rank r owns the units the deal gives it and the only collective is the gather of the fp32
 scores.  The 128-byte RCCL id reaches the other processes through the job's own transport; here that is torch.distributed
@@ -78,6 +79,29 @@ class Comm:
         rc = aln_amd.lib().aln_gather_scores(self.h, scp, gip, nl, int(n_max), out.ctypes.data_as(fp), int(n_total))
         if rc != 0:
             raise aln_amd.AlnError(rc, "aln_gather_scores: " + aln_amd.lib().aln_comm_last_error(self.h).decode())
+        return out
+
+    def gather_enqueue(self, batch, global_index, n_max, n_total):
+        """aln_gather_resident_enqueue: the Optimal scores of the first len(global_index) pairs of `batch` (resident; None when the
+        list is empty) go into the collective without touching the host; returns at once (two slots)."""
+        import aln_amd
+        gi = np.ascontiguousarray(global_index, dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        bp = (C.c_void_p * 1)(batch.h if batch is not None else None)
+        gip = (ip * 1)(gi.ctypes.data_as(ip))
+        nl = (C.c_int32 * 1)(len(gi))
+        rc = aln_amd.lib().aln_gather_resident_enqueue(self.h, bp, gip, nl, int(n_max), int(n_total))
+        if rc != 0:
+            raise aln_amd.AlnError(rc, "aln_gather_resident_enqueue: " + aln_amd.lib().aln_comm_last_error(self.h).decode())
+
+    def gather_collect(self, n_total, out=None):
+        """aln_gather_resident_collect: wait for the oldest enqueued gather -> float32[n_total] in global order."""
+        import aln_amd
+        if out is None:
+            out = np.zeros(n_total, dtype=np.float32)
+        rc = aln_amd.lib().aln_gather_resident_collect(self.h, out.ctypes.data_as(C.POINTER(C.c_float)), int(n_total))
+        if rc != 0:
+            raise aln_amd.AlnError(rc, "aln_gather_resident_collect: " + aln_amd.lib().aln_comm_last_error(self.h).decode())
         return out
 
     def close(self):

@@ -152,6 +152,8 @@ struct aln_batch {
   static const int kEvRing = 64;               // ... and of the builds before it (aln_batch_dp_ms_history)
   hipEvent_t ring0[kEvRing] = {}, ring1[kEvRing] = {};
   long n_builds = 0;
+  long optimal_build = 0;                      // n_builds when Optimal's traceback was last launched on a full build (0 = never):
+                                               // equal to n_builds <=> the CURRENT build has had it (aln_gather_resident_enqueue)
   float enum_search_ms = 0.f, enum_unroll_ms = 0.f;   // last aln_batch_enumerate_all
   // device pools of aln_batch_enumerate_all, kept between calls (hint enum_keep_pools): a hipMalloc of tens of GB costs seconds
   uint8_t* h_stage_pin = nullptr; size_t h_stage_bytes = 0;   // pinned staging of residue codes + table (upload_submatrix)

@@ -109,6 +109,7 @@ int launch_traceback(aln_batch* b, bool subali) {
   hipLaunchKernelGGL(traceback_kernel, dim3(b->n_pairs), dim3(64), 0, b->ctx->stream, b->d_pairs, b->d_H, b->d_P,
                      b->d_res, b->d_path, prm);
   ALN_HIP_CHECK(b->ctx, hipGetLastError());
+  if (!subali) b->optimal_build = b->n_builds;
   return ALN_OK;
 }
 

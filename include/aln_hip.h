@@ -377,6 +377,18 @@ const char* aln_comm_last_error(const aln_comm* comm);
  * every contributed score on every rank.  One ncclAllGather of (index, score) records over xGMI. */
 int aln_gather_scores(aln_comm* comm, const float* const* local_scores, const int32_t* const* global_index,
                       const int32_t* n_local, int32_t n_max, float* global_out, int64_t n_total);
+/* The same collective for scores that are still on the device, split like aln_batch_optimal_enqueue / _collect.  Local rank k
+ * contributes the Optimal scores of the first n_local[k] pairs of batches[k] (a batch of context k of `comm`; NULL when
+ * n_local[k] == 0), whose current build must have had Optimal launched (aln_batch_optimal*, ..._enqueue; else ALN_E_STATE).
+ * _enqueue launches, on each context's stream, a pack kernel over the resident results, the ncclAllGather, a scatter kernel and
+ * the copy of the dense result into one of two pinned slots (ALN_E_STATE when both are waiting), and returns at once: it never
+ * waits for the device.  global_index is read during the call (an index outside [0, n_total) is ALN_E_ARG, nothing enqueued).
+ * _collect waits for the OLDEST slot only and writes global_out[i] for every contributed i (the others keep their value);
+ * ALN_E_ARG if another process's rank sent an index >= n_total, ALN_E_STATE if n_total is not that slot's or nothing is pending.
+ * `reevaluate; optimal_enqueue; gather_resident_enqueue; collect(previous)` keeps the cross-rank wait off the launching thread. */
+int aln_gather_resident_enqueue(aln_comm* comm, aln_batch* const* batches, const int32_t* const* global_index,
+                                const int32_t* n_local, int32_t n_max, int64_t n_total);
+int aln_gather_resident_collect(aln_comm* comm, float* global_out, int64_t n_total);
 
 /* ---- host-side helpers with no device work (alignment.h / gstrings.h) -------------------- */
 /* AlignedPairList::calcIdentity (alignment.h:856-865). qstr/tstr include sentinels. */
