@@ -68,6 +68,13 @@ class AlnHit(C.Structure):
 
 HIT_DTYPE = np.dtype([("t", np.int32), ("score", np.float32), ("q_end", np.int32), ("t_end", np.int32)])
 
+
+class AlnHitStats(C.Structure):
+    _fields_ = [("sum", C.c_int64), ("sumsq", C.c_int64), ("n", C.c_int32), ("z", C.c_float)]
+
+
+HIT_STATS_DTYPE = np.dtype([("sum", np.int64), ("sumsq", np.int64), ("n", np.int32), ("z", np.float32)])
+
 EXPORTS = [
     "aln_ctx_create", "aln_ctx_destroy", "aln_error_string", "aln_last_error", "aln_ctx_synchronize", "aln_has_gfx950",
     "aln_batch_create", "aln_batch_destroy", "aln_batch_n_pairs", "aln_batch_device_bytes", "aln_batch_dp",
@@ -77,6 +84,7 @@ EXPORTS = [
     "aln_batch_optimal_strings", "aln_batch_optimal_strings_enqueue", "aln_batch_optimal_strings_collect", "aln_batch_last_exact_stats", "aln_batch_set_gap", "aln_ctx_set_hint", "aln_ctx_get_hint", "aln_batch_dp_contract_bytes", "aln_batch_plane_bytes_per_cell",
     "aln_deal_units", "aln_comm_unique_id", "aln_comm_create", "aln_ctx_create_multi", "aln_comm_destroy", "aln_comm_n_ranks",
     "aln_comm_last_error", "aln_gather_scores", "aln_gather_resident_enqueue", "aln_gather_resident_collect", "aln_search_topk",
+    "aln_hits_zscores",
 ]
 COMM_ID_BYTES = 128
 
@@ -142,6 +150,9 @@ def lib():
                                            C.c_int32, C.c_int32, _fp]
         L.aln_search_topk.argtypes = [C.c_void_p, C.POINTER(AlnSeqs), C.POINTER(AlnSeqs), C.POINTER(AlnSubmatrix), C.POINTER(AlnGap),
                                       C.c_int32, C.c_int32, C.c_int32, C.c_float, C.POINTER(AlnHit), _ip]
+        L.aln_hits_zscores.argtypes = [C.c_void_p, C.POINTER(AlnSeqs), C.POINTER(AlnSeqs), C.POINTER(AlnSubmatrix), C.POINTER(AlnGap),
+                                       C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.c_int32, C.c_uint32,
+                                       C.POINTER(AlnHitStats)]
         L.aln_hmap2_gap_arrays.argtypes = [_fp, C.c_int64, C.c_float, C.c_float, C.c_float, _fp, _fp]
         L.aln_batch_plane_bytes_per_cell.argtypes = [C.c_void_p]
         L.aln_batch_optimal_strings.argtypes = [C.c_void_p, _fp, _fp, _ip, C.c_char_p, C.c_char_p, C.c_int32, _ip]
@@ -278,6 +289,51 @@ def search_topk(ctx, queries, templates, alphabet, table, gi, ge, K, min_score=-
     _check(lib().aln_search_topk(ctx.h, C.byref(qpool.c), C.byref(tpool.c), C.byref(sub), C.byref(g), q_begin, q_end, int(K),
                                  float(min_score), hits.ctypes.data_as(C.POINTER(AlnHit)), _i(n_hits)), ctx.h)
     return hits, n_hits
+
+
+def _fmix32(x):
+    x ^= x >> 16
+    x = (x * 0x85EBCA6B) & 0xFFFFFFFF
+    x ^= x >> 13
+    x = (x * 0xC2B2AE35) & 0xFFFFFFFF
+    return x ^ (x >> 16)
+
+
+def shuffle_query(seed, q_index, s, residues):
+    """Shuffle s of query q_index (its index in the pool) under `seed`, as aln_hits_zscores permutes it (include/aln_hip.h):
+    pure Python over the interior residues — `residues` comes WITHOUT sentinels.  Reproduces a background sample."""
+    key = _fmix32((_fmix32((_fmix32((seed ^ 0x9E3779B9) & 0xFFFFFFFF) + q_index) & 0xFFFFFFFF) + s) & 0xFFFFFFFF)
+    a = list(residues)
+    for i in range(len(a) - 1, 0, -1):
+        j = (_fmix32((key + i * 0x9E3779B9) & 0xFFFFFFFF) * (i + 1)) >> 32
+        a[i], a[j] = a[j], a[i]
+    return "".join(a)
+
+
+def hits_zscores(ctx, queries, templates, hits, n_hits, alphabet, table, gi, ge, n_shuffles, seed=0, q_begin=0, align_type=LOCAL):
+    """aln_hits_zscores: for the used slots of hits[rows, K] (search_topk's layout; row r is query q_begin + r) the sum and the
+    sum of squares of the scores of n_shuffles permutations of the query against the hit's template, scored and reduced on
+    the device, and the z-score of the hit's own score against that sample.  Integer scoring only.
+    -> stats[rows, K] (fields sum, sumsq, n, z; unused slots 0)."""
+    qpool = queries if isinstance(queries, SeqPool) else SeqPool(queries)
+    tpool = templates if isinstance(templates, SeqPool) else SeqPool(templates)
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    n_hits = np.ascontiguousarray(n_hits, dtype=np.int32)
+    rows, K = hits.shape
+    assert n_hits.shape == (rows,)
+    tab = np.ascontiguousarray(table, dtype=np.float32)
+    ab = alphabet.encode()
+    sub = AlnSubmatrix(len(alphabet), ab, _f(tab))
+    g = AlnGap()
+    g.model = GAP_AFFINE_CONST
+    g.align_type = int(align_type)
+    g.gap_init = float(np.float32(gi))
+    g.gap_extn = float(np.float32(ge))
+    stats = np.zeros((rows, K), dtype=HIT_STATS_DTYPE)
+    _check(lib().aln_hits_zscores(ctx.h, C.byref(qpool.c), C.byref(tpool.c), C.byref(sub), C.byref(g), q_begin, q_begin + rows, int(K),
+                                  hits.ctypes.data_as(C.POINTER(AlnHit)), _i(n_hits), int(n_shuffles), int(seed) & 0xFFFFFFFF,
+                                  stats.ctypes.data_as(C.POINTER(AlnHitStats))), ctx.h)
+    return stats
 
 
 def align_hits(ctx, queries, templates, hits, n_hits, alphabet, table, gi, ge, q_begin=0, align_type=LOCAL):

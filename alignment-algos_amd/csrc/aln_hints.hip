@@ -40,6 +40,7 @@ const HintDef kDefs[] = {
     {"score_packed", "ALN_SCORE_NO_PACKED", true, &aln_hints::score_packed},
     {"search_slab_rows", "ALN_SEARCH_SLAB_ROWS", false, &aln_hints::search_slab_rows},
     {"search_debug", "ALN_SEARCH_DEBUG", false, &aln_hints::search_debug},
+    {"zscore_chunk_rows", "ALN_ZSCORE_CHUNK_ROWS", false, &aln_hints::zscore_chunk_rows},
     {"enum_heavy_first", "ALN_ENUM_HEAVY_FIRST", false, &aln_hints::enum_heavy_first},
     {"enum_pool_retries", "ALN_ENUM_POOL_RETRIES", false, &aln_hints::enum_pool_retries},
     {"enum_waves", "ALN_ENUM_WAVES", false, &aln_hints::enum_waves},

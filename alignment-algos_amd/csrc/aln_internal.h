@@ -82,6 +82,7 @@ struct aln_hints {
   int score_packed = 1;      // 0: one query per wave in aln_score_all_vs_all
   int search_slab_rows = 0;  // aln_search_topk: query rows whose scores are resident at a time; 0 = by the 1 GiB slab budget
   int search_debug = 0;      // 1: aln_search_topk reports its slabs and the device time of scoring / selection / end cells on stderr
+  int zscore_chunk_rows = 0; // aln_hits_zscores: query rows whose shuffled strings are resident at a time; 0 = by the 1 GiB budget
   int plane_row_align = 8;   // cells a plane row is padded to when a batch is created (8, 16, 32 or 64)
   int64_t enum_node_cap = 0; // trie nodes of aln_batch_enumerate (0 = default)
   int enum_keep_pools = 1;   // 1: aln_batch_enumerate_all keeps its device pools with the batch (freed with it); 0: frees them when it returns

@@ -209,6 +209,9 @@ int aln_has_gfx950(void);
  *   "search_slab_rows"              aln_search_topk: query rows whose scores are resident on the device at a time; 0 (default) = as many as
  *                                   keep the slab's scores (4 B x n_templates per row) and hits (16 B x K per row) below 1 GiB each
  *   "search_debug"                  1: aln_search_topk reports its slabs and the device time of scoring / selection / end cells on stderr
+ *   "zscore_chunk_rows"             aln_hits_zscores: query rows whose shuffled strings and accumulators are resident on the device at a
+ *                                   time; 0 (default) = as many as keep the shuffled pool (n_shuffles x |q| bytes per row with a hit) and the
+ *                                   accumulators (16 B x K per row) below 1 GiB each; a larger value is cut to that
  * Unknown key -> ALN_E_ARG.  No hint changes any result. */
 int aln_ctx_set_hint(aln_ctx* ctx, const char* key, int64_t value);
 int aln_ctx_get_hint(const aln_ctx* ctx, const char* key, int64_t* value);
@@ -352,6 +355,41 @@ typedef struct {
 int aln_search_topk(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
                     const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K, float min_score,
                     aln_hit* hits /* (q_end-q_begin) x K */, int32_t* n_hits /* q_end-q_begin */);
+
+/* ---- shuffle z-scores of search hits: the background of every hit scored and reduced on the device ------------------- */
+/* The reference has the hook (AlignedPairList::calcSignificance takes a Significance<Model> functor, significance.h) and ships
+ * no model; this is the classic one.  The query of a hit is permuted n_shuffles times, every permutation is aligned to the
+ * hit's template with the call's align type, table and gaps, and the hit's own score is placed against that sample. */
+typedef struct {
+  int64_t sum;     /* sum of the n shuffled-query scores (integer scoring, exact) */
+  int64_t sumsq;   /* sum of their squares */
+  int32_t n;       /* n_shuffles for a used slot, 0 for an unused one */
+  float   z;       /* (score - mean) / sample standard deviation, see below; 0 when n < 2 or the sample has no spread */
+} aln_hit_stats;   /* 24 bytes */
+/* The layout is aln_search_topk's: row r is query q_begin + r, slots k < n_hits[r] of hits[r * K ..] are used, and only their
+ * .t and .score are read — any list of (row, template) pairs will do, duplicates included.  stats[r * K + k] receives the
+ * record of slot k; an unused slot gets { 0, 0, 0, 0.0f }.
+ * Shuffle s (0 .. n_shuffles-1) of query q (its index in the POOL, not the row) with `seed`, all arithmetic uint32:
+ *   fmix(x): x ^= x>>16; x *= 0x85EBCA6B; x ^= x>>13; x *= 0xC2B2AE35; x ^= x>>16
+ *   key = fmix(fmix(fmix(seed ^ 0x9E3779B9) + q) + s)
+ *   a = the interior residues (the sentinels stay), L = |q| - 2
+ *   for i = L-1 down to 1:  r = fmix(key + i*0x9E3779B9);  j = (uint64(r) * (i+1)) >> 32;  swap(a[i], a[j])
+ * so a shuffle depends on neither n_shuffles, the row block, K nor the chunking (hint "zscore_chunk_rows").
+ * sum / sumsq run over the scores aln_score_all_vs_all reports for (shuffle s of the query, template t), all five align types.
+ * With n = n_shuffles, N = n * (int64)score - sum and D = n * sumsq - sum * sum (exact, 128 bits):
+ *   z = (float)((double)N * sqrt((double)(n-1) / ((double)n * (double)D))),   0.0f when n < 2 or D == 0.
+ * INTEGER SCORING ONLY: the sums are exact integers, so a scoring system aln_score_all_vs_all would send through full builds
+ * as a whole (fractional table or gaps, values beyond its 2^23 bound) is refused with ALN_E_NOT_INTEGRAL.  Templates beyond
+ * 2048 columns are scored through full builds inside the call, like there.
+ * Arguments: the checks and status codes of aln_score_all_vs_all; K in 1..1024, n_shuffles in 1..4096, every n_hits[r] in
+ * 0..K and every used slot's t in [0, n_templates), else ALN_E_ARG — nothing is written when a check fails.
+ * Order of the checks: NULL hits / n_hits / stats, K and n_shuffles first; then aln_score_all_vs_all's, in its order; then
+ * n_hits and the used slots' t; ALN_E_NOT_INTEGRAL last.
+ * q_begin == q_end: ALN_OK, nothing written.  Returns when stats is complete. */
+int aln_hits_zscores(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
+                     const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K,
+                     const aln_hit* hits /* (q_end-q_begin) x K */, const int32_t* n_hits /* q_end-q_begin */,
+                     int32_t n_shuffles, uint32_t seed, aln_hit_stats* stats /* (q_end-q_begin) x K */);
 
 /* ---- multi-GPU: a length-sorted deal of independent units + ONE collective (RCCL all-gather of scores) ----------- */
 /* The reference is one thread, one DPMatrix at a time; pairs are independent (dpmatrix.h:104-111), so ranks own disjoint pair
