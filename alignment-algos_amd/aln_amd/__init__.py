@@ -75,6 +75,12 @@ class AlnHitStats(C.Structure):
 
 HIT_STATS_DTYPE = np.dtype([("sum", np.int64), ("sumsq", np.int64), ("n", np.int32), ("z", np.float32)])
 
+class AlnHitAlignment(C.Structure):
+    _fields_ = [("n_pairs", C.c_int32), ("status", C.c_int32), ("score", C.c_float), ("identity", C.c_float)]
+
+
+HIT_ALIGNMENT_DTYPE = np.dtype([("n_pairs", np.int32), ("status", np.int32), ("score", np.float32), ("identity", np.float32)])
+
 EXPORTS = [
     "aln_ctx_create", "aln_ctx_destroy", "aln_error_string", "aln_last_error", "aln_ctx_synchronize", "aln_has_gfx950",
     "aln_batch_create", "aln_batch_destroy", "aln_batch_n_pairs", "aln_batch_device_bytes", "aln_batch_dp",
@@ -84,7 +90,7 @@ EXPORTS = [
     "aln_batch_optimal_strings", "aln_batch_optimal_strings_enqueue", "aln_batch_optimal_strings_collect", "aln_batch_last_exact_stats", "aln_batch_set_gap", "aln_ctx_set_hint", "aln_ctx_get_hint", "aln_batch_dp_contract_bytes", "aln_batch_plane_bytes_per_cell",
     "aln_deal_units", "aln_comm_unique_id", "aln_comm_create", "aln_ctx_create_multi", "aln_comm_destroy", "aln_comm_n_ranks",
     "aln_comm_last_error", "aln_gather_scores", "aln_gather_resident_enqueue", "aln_gather_resident_collect", "aln_search_topk",
-    "aln_hits_zscores",
+    "aln_hits_zscores", "aln_hits_align",
 ]
 COMM_ID_BYTES = 128
 
@@ -153,6 +159,9 @@ def lib():
         L.aln_hits_zscores.argtypes = [C.c_void_p, C.POINTER(AlnSeqs), C.POINTER(AlnSeqs), C.POINTER(AlnSubmatrix), C.POINTER(AlnGap),
                                        C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.c_int32, C.c_uint32,
                                        C.POINTER(AlnHitStats)]
+        L.aln_hits_align.argtypes = [C.c_void_p, C.POINTER(AlnSeqs), C.POINTER(AlnSeqs), C.POINTER(AlnSubmatrix), C.POINTER(AlnGap),
+                                     C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.POINTER(AlnHitAlignment), _ip, C.c_int32,
+                                     C.c_char_p, C.c_char_p, C.c_int32, _ip]
         L.aln_hmap2_gap_arrays.argtypes = [_fp, C.c_int64, C.c_float, C.c_float, C.c_float, _fp, _fp]
         L.aln_batch_plane_bytes_per_cell.argtypes = [C.c_void_p]
         L.aln_batch_optimal_strings.argtypes = [C.c_void_p, _fp, _fp, _ip, C.c_char_p, C.c_char_p, C.c_int32, _ip]
@@ -334,6 +343,55 @@ def hits_zscores(ctx, queries, templates, hits, n_hits, alphabet, table, gi, ge,
                                   hits.ctypes.data_as(C.POINTER(AlnHit)), _i(n_hits), int(n_shuffles), int(seed) & 0xFFFFFFFF,
                                   stats.ctypes.data_as(C.POINTER(AlnHitStats))), ctx.h)
     return stats
+
+
+def hits_align(ctx, queries, templates, hits, n_hits, alphabet, table, gi, ge, q_begin=0, align_type=LOCAL, want_pairs=True,
+               want_lines=True, pair_stride=None, line_stride=None):
+    """aln_hits_align: Optimal's alignment of every used slot of hits[rows, K] (search_topk's layout; row r is query q_begin + r),
+    traced on the device from the end cell the search reported.  -> rec[rows, K] (fields n_pairs, status, score, identity;
+    unused slots 0), lists (rows x K pair arrays in list order, or None), tlines, qlines (rows x K str, or None), lengths[rows, K]
+    (or None), rc (the call's status: 0, or the lowest per-slot status).  Raises only when the call wrote nothing."""
+    qpool = queries if isinstance(queries, SeqPool) else SeqPool(queries)
+    tpool = templates if isinstance(templates, SeqPool) else SeqPool(templates)
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    n_hits = np.ascontiguousarray(n_hits, dtype=np.int32)
+    rows, K = hits.shape
+    assert n_hits.shape == (rows,)
+    tab = np.ascontiguousarray(table, dtype=np.float32)
+    ab = alphabet.encode()
+    sub = AlnSubmatrix(len(alphabet), ab, _f(tab))
+    g = AlnGap()
+    g.model = GAP_AFFINE_CONST
+    g.align_type = int(align_type)
+    g.gap_init = float(np.float32(gi))
+    g.gap_extn = float(np.float32(ge))
+    maxq = max([len(s) for s in qpool.seqs[q_begin:q_begin + rows]] + [2])
+    maxt = max([len(s) for s in tpool.seqs] + [2])
+    if pair_stride is None:
+        pair_stride = min(maxq, maxt) + 3
+    if line_stride is None:
+        line_stride = maxq + maxt + 2
+    rec = np.zeros((rows, K), dtype=HIT_ALIGNMENT_DTYPE)
+    pairs = np.zeros((rows, K, pair_stride, 2), dtype=np.int32) if want_pairs else None
+    tl = C.create_string_buffer(max(rows * K * line_stride, 1)) if want_lines else None
+    ql = C.create_string_buffer(max(rows * K * line_stride, 1)) if want_lines else None
+    lengths = np.zeros((rows, K), dtype=np.int32) if want_lines else None
+    rc = lib().aln_hits_align(ctx.h, C.byref(qpool.c), C.byref(tpool.c), C.byref(sub), C.byref(g), q_begin, q_begin + rows, int(K),
+                              hits.ctypes.data_as(C.POINTER(AlnHit)), _i(n_hits), rec.ctypes.data_as(C.POINTER(AlnHitAlignment)),
+                              _i(pairs) if want_pairs else None, int(pair_stride) if want_pairs else 0, tl, ql,
+                              int(line_stride) if want_lines else 0, _i(lengths) if want_lines else None)
+    if rc != 0 and not (rec["status"] == rc).any():
+        _check(rc, ctx.h)
+    lists = tlines = qlines = None
+    if want_pairs:
+        lists = [[pairs[r, k, :min(int(rec["n_pairs"][r, k]), pair_stride)].copy() for k in range(K)] for r in range(rows)]
+    if want_lines:
+        def cut(buf):
+            raw = buf.raw
+            return [[raw[(r * K + k) * line_stride:(r * K + k) * line_stride + int(lengths[r, k])].decode() for k in range(K)]
+                    for r in range(rows)]
+        tlines, qlines = cut(tl), cut(ql)
+    return rec, lists, tlines, qlines, lengths, rc
 
 
 def align_hits(ctx, queries, templates, hits, n_hits, alphabet, table, gi, ge, q_begin=0, align_type=LOCAL):

@@ -43,6 +43,23 @@ struct PairResult {
   uint32_t part_pos;     // scratch: packed (row<<16|col) of its first row-major occurrence
 };
 
+// gapped_strings.hip: what the string kernel leaves per pair, and its parameters
+struct StrOut {            // per pair, 32 bytes
+  float score;
+  int32_t status;          // the traceback's status (0 or ALN_E_STARTPAIR / ALN_E_HIP ...)
+  int32_t length;          // line length, 0 = no lines
+  int32_t same;            // identical aligned residues - 2 (calcIdentity's numerator)
+  int32_t err;             // ALN_OK, ALN_E_OVERFLOW (line does not fit the stride) or ALN_E_ARG (a list that does not rise strictly)
+  int32_t pad[3];
+};
+
+struct StrParams {
+  int path_stride;
+  int flip;                // forward builds: the traceback wrote the list end -> start
+  int corner_score;        // non-local: the corner's score is the alignment's
+  int stride;              // chars per line slot
+};
+
 struct GapDev {
   int32_t model, align_type;
   float gi, ge;
@@ -83,6 +100,7 @@ struct aln_hints {
   int search_slab_rows = 0;  // aln_search_topk: query rows whose scores are resident at a time; 0 = by the 1 GiB slab budget
   int search_debug = 0;      // 1: aln_search_topk reports its slabs and the device time of scoring / selection / end cells on stderr
   int zscore_chunk_rows = 0; // aln_hits_zscores: query rows whose shuffled strings are resident at a time; 0 = by the 1 GiB budget
+  int align_chunk_hits = 0;  // aln_hits_align: hit slots whose strips are resident at a time; 0 = by the 1 GiB budget (never lifts it)
   int plane_row_align = 8;   // cells a plane row is padded to when a batch is created (8, 16, 32 or 64)
   int64_t enum_node_cap = 0; // trie nodes of aln_batch_enumerate (0 = default)
   int enum_keep_pools = 1;   // 1: aln_batch_enumerate_all keeps its device pools with the batch (freed with it); 0: frees them when it returns
@@ -210,6 +228,8 @@ int launch_dp_corner(aln_batch* b);
 int launch_traceback(aln_batch* b, bool subali);
 // gapped_strings.hip
 void free_string_buffers(aln_batch* b);
+int launch_gapped_strings(aln_ctx* ctx, int n, const PairDesc* pairs, const PairResult* res, const int32_t* path, const char* qchars,
+                          const char* tchars, char* lines, StrOut* out, const StrParams& prm);
 // dp_exact.hip
 int launch_dp_exact(aln_batch* b);
 // dp_exact_blocked.hip

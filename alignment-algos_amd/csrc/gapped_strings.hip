@@ -29,22 +29,6 @@
 
 namespace aln {
 
-struct StrOut {            // per pair, 32 bytes
-  float score;
-  int32_t status;          // the traceback's status (0 or ALN_E_STARTPAIR / ALN_E_HIP ...)
-  int32_t length;          // line length, 0 = no lines
-  int32_t same;            // identical aligned residues - 2 (calcIdentity's numerator)
-  int32_t err;             // ALN_OK, ALN_E_OVERFLOW (line does not fit the stride) or ALN_E_ARG (a list that does not rise strictly)
-  int32_t pad[3];
-};
-
-struct StrParams {
-  int path_stride;
-  int flip;                // forward builds: the traceback wrote the list end -> start
-  int corner_score;        // non-local: the corner's score is the alignment's
-  int stride;              // chars per line slot
-};
-
 __device__ __forceinline__ char lower_ascii(char c) { return (c >= 'A' && c <= 'Z') ? (char)(c | 0x20) : c; }
 
 // A list that does not rise strictly in both indices (an empty template or query: the local list of "^PAWHE$" against "^$" is
@@ -198,6 +182,14 @@ __global__ __launch_bounds__(64) void gapped_strings_kernel(const PairDesc* __re
     o.length = len;
     out[p] = o;
   }
+}
+
+// The kernel over lists that do not belong to a batch (aln_hits_align): descriptors, results and lists of the caller.
+int launch_gapped_strings(aln_ctx* ctx, int n, const PairDesc* pairs, const PairResult* res, const int32_t* path, const char* qchars,
+                          const char* tchars, char* lines, StrOut* out, const StrParams& prm) {
+  hipLaunchKernelGGL(gapped_strings_kernel, dim3(n), dim3(64), 0, ctx->stream, pairs, res, path, qchars, tchars, lines, out, prm);
+  ALN_HIP_CHECK(ctx, hipGetLastError());
+  return ALN_OK;
 }
 
 }  // namespace aln

@@ -1,0 +1,541 @@
+// search_align.hip — the alignments of search hits, on the device: aln_hits_align (gfx950).
+//
+// aln_search_topk reports, per hit, the cell the optimal local alignment ends in.  Traceback through the collapsed recurrence of
+// score_only.hip needs neither scores nor (prev_q, prev_t) pointers: five bits per cell, all of them comparisons between values
+// the row sweep already holds, say which candidate won and where a gap jump lands.  So one wave per hit
+//   align_local_hit_kernel<R>   sweeps rows 1 .. q_end (score_local_end_kernel<R>'s sweep), writes ONE byte per cell into a
+//                               transient strip of its own, walks back from the given end cell through that strip, writes
+//                               Optimal's pair list and counts the identities;
+//   ahit_list_kernel            lists a chunk's hits by template length class R = ceil(T / 256) (zhit_list_kernel over descriptors);
+//   gapped_strings_kernel       (gapped_strings.hip, unchanged) lays the two lines of every list out.
+// No aln_batch, no planes, no find_max.  The strip byte of row i (2 .. q_end), column slot c:
+//   bits 0-1  the move INTO cell (i, c+1): 0 match, 1 deletion, 2 insertion — the reference tries match, deletions (k ascending),
+//             insertions (k ascending) and a later candidate wins only when strictly greater (dpmatrix.h:607-649): with m, e, f
+//             the three maxima, match if m >= max(e, f), else deletion if e >= f, else insertion.  (Candidates are clipped at 0
+//             before they are compared; the walk only ever reads the move of a cell whose score is > 0, where the clip is idle.)
+//   bit 2     cell (i-1, c) as a deletion source: an earlier column of row i-1 already holds at least its key D + ge k
+//             (the sweep's pv >= A).  The smallest k wins ties, so a deletion into (i, j) walks row i-1 leftwards from
+//             column j-2 while the bit is set and lands on the first clear one.
+//   bit 3     cell (i-1, c) as an insertion source: an earlier row of column c already holds at least its key (gmx_old >= m + ge row);
+//             the walk goes upwards in column j-1 from row i-2.
+//   bit 4     D[i-1][c] > 0: Optimal's local walk stops BEFORE a cell whose score is <= 0 (optimal.h:100).
+// Bits 2-4 of row i describe row i-1, whose values the sweep holds while it computes row i: the last row the walk needs them
+// for is q_end - 1.  Rows 1 and columns 1 need no move: their cells point at the origin (dpmatrix.h:579-599).
+// Everything the kernel does not take — the four non-local align types, templates beyond 2048 columns, scoring systems ScoreRun
+// sends through full builds, pairs without an interior — goes through resident batches inside the call.
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "score_common.h"
+
+namespace aln {
+
+constexpr size_t kAlignBudget = (size_t)1 << 30;   // bytes of strips (and of lists, and of lines) resident at a time
+
+struct HitDesc {            // one used slot the fused kernel takes, 32 bytes
+  int32_t q, t;             // sequence indices in the pools
+  int32_t q_end, t_end;     // the trusted end cell
+  float score;              // the slot's score: D[q_end][t_end] must equal it
+  int32_t cls;              // template length class 1 .. 8
+  int64_t strip_off;        // first byte of the hit's strip: (q_end - 1) rows of 256 cls bytes
+};
+
+struct AClassOff { int off[9]; };
+
+// list[off[c] ..) = the chunk's hits of length class c, in no particular order (zhit_list_kernel over descriptors)
+__global__ __launch_bounds__(256) void ahit_list_kernel(const HitDesc* desc, int n, AClassOff co, int32_t* fill, int32_t* list) {
+  __shared__ int lc[9], lb[9];
+  const int tid = threadIdx.x;
+  const int h = blockIdx.x * 256 + tid;
+  if (tid < 9) lc[tid] = 0;
+  __syncthreads();
+  int cls = -1, my = 0;
+  if (h < n) { cls = desc[h].cls; my = atomicAdd(&lc[cls], 1); }
+  __syncthreads();
+  if (tid < 9 && lc[tid]) lb[tid] = co.off[tid] + atomicAdd(&fill[tid], lc[tid]);
+  __syncthreads();
+  if (cls >= 0) list[lb[cls] + my] = h;
+}
+
+struct AlignArgs {
+  const int32_t* list;      // blockIdx.x -> hit of the chunk
+  const HitDesc* desc;
+  uint8_t* strip;
+  int32_t* trav;            // hit h's list in TRAVERSAL order (end -> start) at trav + h * trav_stride * 2
+  int trav_stride;
+  PairResult* res;          // best = score, n_path, status (what gapped_strings_kernel reads)
+  int32_t* same;            // identical aligned residues of the list (calcIdentity's count before its "- 2")
+};
+
+template <int R>
+__global__ __launch_bounds__(64) void align_local_hit_kernel(ScoreArgs a, AlignArgs g) {
+  __shared__ int tab[32 * 32];
+  const int lane = threadIdx.x;
+  for (int k = lane; k < 32 * 32; k += 64) tab[k] = a.table32[k];
+  __syncthreads();
+  const int hit = g.list[blockIdx.x];
+  const HitDesc hd = g.desc[hit];
+  const int ti = hd.t, qi = hd.q, q_end = hd.q_end, t_end = hd.t_end;
+  const uint8_t* __restrict__ qc = a.qcodes + a.qoff[qi];
+  const uint8_t* __restrict__ tc = a.tcodes + a.toff[ti];
+  const int Q = (int)(a.qoff[qi + 1] - a.qoff[qi]), T = (int)(a.toff[ti + 1] - a.toff[ti]);
+  const int gi = a.gi, ge = a.ge;
+  const int cb = 4 * lane;
+  const int gime = gi - ge;
+  constexpr int kPitch = 256 * R;
+  uint8_t* strip = g.strip + hd.strip_off;      // row i (2 .. q_end) at strip + (i - 2) * kPitch
+
+  int code4[R][4], gec[R][4], ekc[R][4], inm[R][4];
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+      const int c = cb + 256 * r + x;
+      int code = kCodeTail;
+      if (c < T) code = tc[c];
+      code4[r][x] = code * 4;
+      gec[r][x] = ge * c;
+      ekc[r][x] = ge * c + gime;
+      inm[r][x] = ((unsigned)(c - 1) < (unsigned)(T - 2)) ? -1 : 0;
+    }
+  int d[R][4], gmx[R][4], cv[R], ak[R][4];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    cv[r] = kNegS;
+#pragma unroll
+    for (int x = 0; x < 4; ++x) { d[r][x] = 0; gmx[r][x] = kNegS; }
+  }
+  auto tab_at = [&](int qrow, int c4) -> int {
+    return *reinterpret_cast<const int*>(reinterpret_cast<const char*>(tab) + qrow + c4);
+  };
+  auto finish_row = [&]() {
+    int sk = kNegS;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      int tk = kNegS;
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        int A = d[r][x] + gec[r][x];
+        if (r == 0 && x == 0) A = (lane == 0) ? kNegS : A;   // column 0 is never a source
+        ak[r][x] = A;
+        tk = max(tk, A);
+      }
+      const int ik = wave_incl_max_s(tk);
+      const int ek = sdpp<0x138>(kNegS, ik);
+      cv[r] = max(sk, ek);
+      sk = max(sk, __builtin_amdgcn_readlane(ik, 63));
+    }
+  };
+  {
+    const int qrow = (int)qc[1] * 128;           // row 1 (Q >= 3: the host sends other pairs elsewhere)
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        const int h = max(tab_at(qrow, code4[r][x]), 0);
+        d[r][x] = h & inm[r][x];
+      }
+    finish_row();
+  }
+  int qcode_next = (q_end >= 2) ? (int)qc[2] : 0;
+  for (int i = 2; i <= q_end; ++i) {                          // dpmatrix.h:607-649, rows below q_end are not needed
+    const int qrow = qcode_next * 128;
+    if (i + 1 <= q_end) qcode_next = (int)qc[i + 1];
+    const int roff = gi + ge * (i - 2);
+    const int rowB = ge * (i - 1);
+    uint32_t* srow = reinterpret_cast<uint32_t*>(strip + (size_t)(i - 2) * kPitch) + lane;
+    int bk[R][4];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      int pv = cv[r];
+      uint32_t w = 0;
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        const int m = d[r][x];
+        const int A = ak[r][x];
+        const int e = pv - ekc[r][x];
+        const int f = gmx[r][x] - roff;
+        const int key = m + rowB;
+        bk[r][x] = max(max(m, e), f);
+        uint32_t b = (m >= max(e, f)) ? 0u : (e >= f ? 1u : 2u);
+        b |= (pv >= A) ? 4u : 0u;
+        b |= (gmx[r][x] >= key) ? 8u : 0u;
+        b |= (m > 0) ? 16u : 0u;
+        w |= b << (8 * x);
+        pv = max(pv, A);
+        gmx[r][x] = max(gmx[r][x], key);
+      }
+      srow[64 * r] = w;                                       // the lane's four columns: 256 contiguous bytes per wave
+    }
+    int prev_k = 0;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      int uk = sdpp<0x138>(0, bk[r][3]);
+      if (r > 0) uk = (lane == 0) ? prev_k : uk;
+      prev_k = __builtin_amdgcn_readlane(bk[r][3], 63);
+      const bool masked = (r == 0) || (256 * (r + 1) > T - 1);
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        const int c = cb + 256 * r + x;
+        const int s = tab_at(qrow, code4[r][x]);
+        int h = max(((x == 0) ? uk : bk[r][x - 1]) + s, 0);
+        if (r == 0 && x == 1) h = (c == 1) ? max(s, 0) : h;  // column 1 (lane 0 only): free insertion from the origin
+        if (masked) h &= inm[r][x];                          // columns 0 and >= T-1 stay 0
+        d[r][x] = h;
+      }
+    }
+    finish_row();
+  }
+  // D[q_end][t_end]: row q_end is in d[], column t_end in slot (rs, xs) of lane ls
+  int dend;
+  {
+    const int rs = t_end / 256, xs = t_end & 3, ls = (t_end & 255) >> 2;
+    int v = 0;
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int x = 0; x < 4; ++x) v = (r == rs && x == xs) ? d[r][x] : v;
+    dend = __shfl(v, ls);
+  }
+  PairResult res = {};
+  res.best = (float)dend; res.corner = 0.f; res.best_q = q_end; res.best_t = t_end;
+  if (!((float)dend == hd.score)) {                          // not the cell the slot's score stands in: refuse the slot
+    if (lane == 0) { res.best = 0.f; res.status = ALN_E_ARG; res.n_path = 0; g.res[hit] = res; g.same[hit] = 0; }
+    return;
+  }
+  __threadfence();                                           // the walk's lanes read bytes other lanes stored
+  __syncthreads();
+
+  // ---- the walk back (optimal.h:79-105), emitted in traversal order ---------------------------------------------------------
+  int32_t* o = g.trav + (size_t)hit * g.trav_stride * 2;
+  const int cap = g.trav_stride;
+  int n = 0, same = 0;
+  auto emit1 = [&](int q, int t) {
+    if (lane == 0 && n < cap) { o[2 * n] = q; o[2 * n + 1] = t; same += (qc[q] == tc[t]) ? 1 : 0; }
+    ++n;
+  };
+  auto at = [&](int i, int c) -> uint32_t { return strip[(size_t)(i - 2) * kPitch + c]; };
+  emit1(Q - 1, T - 1);
+  emit1(q_end, t_end);
+  int i = q_end, j = t_end;
+  bool origin = false;                                       // the walk stopped at a cell with both indices > 0: (0,0) is prepended
+  while (i >= 2 && j >= 2) {                                 // a cell of row 1 or column 1 points at (0,0), whose score is 0
+    // lane l looks at cell (i - l, j - l): its byte holds the move into it and the score bit of its diagonal predecessor
+    const int ci = i - lane, cj = j - lane;
+    const bool valid = ci >= 2 && cj >= 2;
+    const uint32_t b = valid ? at(ci, cj - 1) : 0u;
+    const bool go = valid && (b & 3u) == 0u && (b & 16u) != 0u;
+    const unsigned long long m = __ballot(go);
+    const int L = (~m == 0ull) ? 64 : __builtin_ctzll(~m);   // lanes 0 .. L-1 step diagonally onto a cell that is kept
+    if (lane < L) {
+      const int k = n + lane;
+      if (k < cap) { o[2 * k] = ci - 1; o[2 * k + 1] = cj - 1; same += (qc[ci - 1] == tc[cj - 1]) ? 1 : 0; }
+    }
+    n += L; i -= L; j -= L;
+    if (L == 64) continue;
+    if (i < 2 || j < 2) break;
+    const uint32_t bL = (uint32_t)__shfl((int)b, L);
+    const uint32_t mv = bL & 3u;
+    if (mv == 0u) { origin = true; break; }                  // a match whose predecessor's score is <= 0
+    int pi, pj; uint32_t bp = 0;
+    if (mv == 1u) {                                          // deletion: the smallest column of row i-1 holding the maximal key
+      pi = i - 1; pj = 0;
+      for (int k0 = j - 2; k0 >= 1; k0 -= 64) {
+        const int kk = k0 - lane;
+        const uint32_t bb = kk >= 1 ? at(i, kk) : 0u;
+        const unsigned long long clr = __ballot((bb & 4u) == 0u);
+        if (clr) { const int l0 = __builtin_ctzll(clr); pj = k0 - l0; bp = (uint32_t)__shfl((int)bb, l0); break; }
+      }
+    } else {                                                 // insertion: the smallest row of column j-1 holding the maximal key
+      pj = j - 1; pi = 0;
+      for (int k0 = i - 2; k0 >= 1; k0 -= 64) {
+        const int kk = k0 - lane;
+        const uint32_t bb = kk >= 1 ? at(kk + 1, pj) : 0u;
+        const unsigned long long clr = __ballot((bb & 8u) == 0u);
+        if (clr) { const int l0 = __builtin_ctzll(clr); pi = k0 - l0; bp = (uint32_t)__shfl((int)bb, l0); break; }
+      }
+    }
+    if (pi < 1 || pj < 1) break;                             // (cannot happen: row 1 and column 1 always clear their bits)
+    if ((bp & 16u) == 0u) { origin = true; break; }          // the source's score is <= 0
+    emit1(pi, pj);
+    i = pi; j = pj;
+  }
+  if (origin) emit1(0, 0);
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) same += __shfl_xor(same, off);
+  if (lane == 0) {
+    res.n_path = n;
+    res.status = n <= cap ? 0 : ALN_E_OVERFLOW;
+    g.res[hit] = res;
+    g.same[hit] = same;
+  }
+}
+
+// The instantiations kept: every one compiles without scratch memory and without VGPR spills (DESIGN 4.8d has the table).
+// R = 8 (templates of 1793 .. 2048 columns) does not — 24 VGPRs spilled into AGPRs — so that class goes the batch route.
+constexpr unsigned kFusedClasses = 0x0FEu;                   // bit R set: class R runs in align_local_hit_kernel<R>
+
+static void launch_align_kernel(int r, int n, hipStream_t stream, const ScoreArgs& s, const AlignArgs& g) {
+  const dim3 grid(n), block(64);
+  switch (r) {
+    case 1: hipLaunchKernelGGL(align_local_hit_kernel<1>, grid, block, 0, stream, s, g); break;
+    case 2: hipLaunchKernelGGL(align_local_hit_kernel<2>, grid, block, 0, stream, s, g); break;
+    case 3: hipLaunchKernelGGL(align_local_hit_kernel<3>, grid, block, 0, stream, s, g); break;
+    case 4: hipLaunchKernelGGL(align_local_hit_kernel<4>, grid, block, 0, stream, s, g); break;
+    case 5: hipLaunchKernelGGL(align_local_hit_kernel<5>, grid, block, 0, stream, s, g); break;
+    case 6: hipLaunchKernelGGL(align_local_hit_kernel<6>, grid, block, 0, stream, s, g); break;
+    default: hipLaunchKernelGGL(align_local_hit_kernel<7>, grid, block, 0, stream, s, g); break;
+  }
+}
+
+// Where the results of one slot go, and how they are written (the same for both routes)
+struct AlignOut {
+  aln_hit_alignment* out; int32_t* pairs; int32_t pair_stride; char* tlines; char* qlines; int32_t line_stride; int32_t* lengths;
+  int worst = ALN_OK;
+  void note(int st) { if (st < worst) worst = st; }
+  // list: n entries, reversed when flip; line: the slot's two lines of `len` chars (nullptr: none)
+  void put(size_t slot, int status, float score, float identity, int n, const int32_t* list, bool flip, int len, const char* tl,
+           const char* ql) {
+    aln_hit_alignment o = {n, status, score, identity};
+    if (pairs && status == ALN_OK) {
+      const int m = std::min(n, pair_stride);
+      int32_t* dst = pairs + slot * (size_t)pair_stride * 2;
+      for (int k = 0; k < m; ++k) {
+        const int sk = flip ? n - 1 - k : k;
+        dst[2 * k] = list[2 * sk]; dst[2 * k + 1] = list[2 * sk + 1];
+      }
+      if (n > pair_stride) o.status = ALN_E_OVERFLOW;
+    }
+    if (tlines) {
+      char* t = tlines + slot * (size_t)line_stride; char* q = qlines + slot * (size_t)line_stride;
+      int wrote = 0;
+      if (status == ALN_OK && len >= line_stride) o.status = ALN_E_OVERFLOW;
+      else if (status == ALN_OK && len > 0 && tl) { memcpy(t, tl, (size_t)len); memcpy(q, ql, (size_t)len); wrote = len; }
+      t[wrote] = 0; q[wrote] = 0;
+      if (lengths) lengths[slot] = wrote;
+    }
+    out[slot] = o;
+    note(o.status);
+  }
+};
+
+// The batch route over the listed slots: aln_batch_create + aln_batch_dp + aln_batch_optimal / _strings, grouped under the
+// plane budget exactly as end_cells_through_batches (search_topk.hip) groups them.
+static int align_through_batches(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
+                                 const aln_gap* gap, const std::vector<int32_t>& qi_all, const std::vector<int32_t>& ti_all,
+                                 const std::vector<size_t>& slot_all, AlignOut& ao) {
+  const size_t budget = (size_t)12 << 30, max_pairs = 65536;
+  aln_sim sim = aln_sim();
+  sim.kind = ALN_SIM_SUBMATRIX;
+  sim.sub = *sub;
+  std::vector<int32_t> n, st, pairs, len;
+  std::vector<float> sc, ident;
+  std::vector<char> tl, ql;
+  size_t g0 = 0;
+  while (g0 < qi_all.size()) {
+    size_t g1 = g0, bytes = 0;
+    int64_t mq = 0, mt = 0, msum = 0;
+    while (g1 < qi_all.size() && g1 - g0 < max_pairs) {
+      const int64_t Q = queries->offsets[qi_all[g1] + 1] - queries->offsets[qi_all[g1]];
+      const int64_t T = templates->offsets[ti_all[g1] + 1] - templates->offsets[ti_all[g1]];
+      const size_t need = (size_t)Q * (size_t)(T + 16) * 8;
+      if (g1 > g0 && bytes + need > budget) break;
+      bytes += need; mq = std::max(mq, Q); mt = std::max(mt, T); msum = std::max(msum, Q + T); ++g1;
+    }
+    const int32_t np = (int32_t)(g1 - g0), stride = (int32_t)std::max<int64_t>(std::min(mq, mt) + 3, 4), ls = (int32_t)(msum + 2);
+    n.assign((size_t)np, 0); st.assign((size_t)np, 0); pairs.assign((size_t)np * stride * 2, 0);
+    sc.assign((size_t)np, 0.f); ident.assign((size_t)np, 0.f); len.assign((size_t)np, 0);
+    aln_batch* bb = nullptr;
+    int rc = aln_batch_create(ctx, queries, templates, np, qi_all.data() + g0, ti_all.data() + g0, 0, &bb);
+    if (rc == ALN_OK) rc = aln_batch_dp(bb, &sim, gap, ALN_FWD, ALN_DP_AUTO, 0);
+    if (rc == ALN_OK) rc = aln_batch_optimal(bb, sc.data(), n.data(), pairs.data(), stride, st.data());
+    if (rc == ALN_OK) {
+      tl.assign((size_t)np * ls, 0); ql.assign((size_t)np * ls, 0);
+      rc = aln_batch_optimal_strings(bb, nullptr, ident.data(), nullptr, tl.data(), ql.data(), ls, len.data());
+      if (rc == ALN_E_STARTPAIR) rc = ALN_OK;                 // reported per slot
+    }
+    if (bb) aln_batch_destroy(bb);
+    if (rc != ALN_OK) return rc;
+    for (int32_t p = 0; p < np; ++p)
+      ao.put(slot_all[g0 + p], st[p], sc[p], ident[p], st[p] == 0 ? n[p] : 0, pairs.data() + (size_t)p * stride * 2, false, len[p],
+             tl.data() + (size_t)p * ls, ql.data() + (size_t)p * ls);
+    g0 = g1;
+  }
+  return ALN_OK;
+}
+
+}  // namespace aln
+
+using namespace aln;
+
+extern "C" int aln_hits_align(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
+                              const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K, const aln_hit* hits,
+                              const int32_t* n_hits, aln_hit_alignment* out, int32_t* pairs, int32_t pair_stride, char* tlines,
+                              char* qlines, int32_t line_stride, int32_t* lengths) {
+  if (!hits || !n_hits || !out || K < 1 || K > 1024) return ALN_E_ARG;
+  if (pairs ? pair_stride < 2 : false) return ALN_E_ARG;
+  const bool want_lines = tlines || qlines;
+  if (want_lines ? (!tlines || !qlines || line_stride < 1) : lengths != nullptr) return ALN_E_ARG;
+  ScoreRun run;
+  int rc = run.prepare(ctx, queries, templates, sub, gap, q_begin, q_end);
+  if (rc != ALN_OK) return rc;
+  const int rows = run.rows, n_t = run.n_t;
+  if (rows == 0) return ALN_OK;
+  const bool fused_ok = run.route == ScoreRun::kFast && run.local;
+
+  // one walk: validate every used slot, describe it for its route, count the classes (nothing is written before it ends)
+  std::vector<HitDesc> fast;            // the fused kernel's hits, row-major
+  std::vector<size_t> fast_slot;
+  std::vector<int32_t> bq, bt;          // the batch route's
+  std::vector<size_t> bslot;
+  for (int r = 0; r < rows; ++r) {
+    if (n_hits[r] < 0 || n_hits[r] > K) return ALN_E_ARG;
+    const int q = q_begin + r;
+    const int64_t Q = queries->offsets[q + 1] - queries->offsets[q];
+    for (int k = 0; k < n_hits[r]; ++k) {
+      const size_t slot = (size_t)r * K + k;
+      const aln_hit& h = hits[slot];
+      if (h.t < 0 || h.t >= n_t) return ALN_E_ARG;
+      const int64_t T = templates->offsets[h.t + 1] - templates->offsets[h.t];
+      const bool interior = Q >= 3 && T >= 3;
+      if (run.local && interior && (h.q_end < 1 || h.q_end > Q - 2 || h.t_end < 1 || h.t_end > T - 2)) return ALN_E_ARG;
+      const int cls = (int)((T + 255) / 256);
+      if (fused_ok && interior && T <= 2048 && ((kFusedClasses >> cls) & 1u)) {
+        HitDesc d = {q, h.t, h.q_end, h.t_end, h.score, cls, 0};
+        fast.push_back(d); fast_slot.push_back(slot);
+      } else { bq.push_back(q); bt.push_back(h.t); bslot.push_back(slot); }
+    }
+  }
+  AlignOut ao = {out, pairs, pair_stride, tlines, qlines, line_stride, lengths};
+  for (int r = 0; r < rows; ++r)
+    for (int k = std::max(n_hits[r], 0); k < K; ++k) {
+      const size_t slot = (size_t)r * K + k;
+      const aln_hit_alignment zero = {0, 0, 0.0f, 0.0f};
+      out[slot] = zero;
+      if (tlines) { tlines[slot * (size_t)line_stride] = 0; qlines[slot * (size_t)line_stride] = 0; }
+      if (lengths) lengths[slot] = 0;
+    }
+
+  // chunks of fused hits: strips, lists and lines each stay below the budget; the hint only asks for fewer
+  struct Chunk { size_t h0, n; size_t strip; int trav_stride; int cls_cnt[9]; };
+  std::vector<Chunk> chunks;
+  {
+    const size_t forced = ctx->hints.align_chunk_hits > 0 ? (size_t)ctx->hints.align_chunk_hits : (size_t)-1;
+    Chunk c = {0, 0, 0, 4, {0, 0, 0, 0, 0, 0, 0, 0, 0}};
+    for (size_t h = 0; h < fast.size(); ++h) {
+      HitDesc& d = fast[h];
+      const size_t need = (size_t)std::max(d.q_end - 1, 1) * 256 * (size_t)d.cls;
+      const int ts = std::max(c.trav_stride, std::min(d.q_end, d.t_end) + 3);
+      const bool full = c.n >= forced || c.strip + need > kAlignBudget || (c.n + 1) * (size_t)ts * 8 > kAlignBudget ||
+                        (want_lines && (c.n + 1) * 2 * (size_t)line_stride > kAlignBudget);
+      if (c.n > 0 && full) {
+        chunks.push_back(c);
+        c = {h, 0, 0, 4, {0, 0, 0, 0, 0, 0, 0, 0, 0}};
+      }
+      d.strip_off = (int64_t)c.strip;
+      c.strip += need; c.n++; c.cls_cnt[d.cls]++;
+      c.trav_stride = std::max(c.trav_stride, std::min(d.q_end, d.t_end) + 3);
+    }
+    if (c.n > 0) chunks.push_back(c);
+  }
+
+  if (!chunks.empty()) {
+    size_t max_n = 1, max_strip = 1, max_trav = 1;
+    for (const Chunk& c : chunks) {
+      max_n = std::max(max_n, c.n); max_strip = std::max(max_strip, c.strip);
+      max_trav = std::max(max_trav, c.n * (size_t)c.trav_stride * 2);
+    }
+    uint8_t* dstrip = nullptr; HitDesc* ddesc = nullptr; int32_t *dlist = nullptr, *dfill = nullptr, *dtrav = nullptr, *dsame = nullptr;
+    PairResult* dres = nullptr; PairDesc* dpd = nullptr; StrOut* dso = nullptr; char *dlines = nullptr, *dqch = nullptr, *dtch = nullptr;
+    auto cleanup = [&]() {
+      hipFree(dstrip); hipFree(ddesc); hipFree(dlist); hipFree(dfill); hipFree(dtrav); hipFree(dsame); hipFree(dres); hipFree(dpd);
+      hipFree(dso); hipFree(dlines); hipFree(dqch); hipFree(dtch);
+      run.release();
+    };
+#define STRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(e_); hipStreamSynchronize(ctx->stream); cleanup(); return ALN_E_HIP; } } while (0)
+#define RTRY(expr) do { int r_ = (expr); if (r_ != ALN_OK) { hipStreamSynchronize(ctx->stream); cleanup(); return r_; } } while (0)
+    RTRY(run.upload());
+    STRY(hipMalloc((void**)&dstrip, max_strip));
+    STRY(hipMalloc((void**)&ddesc, max_n * sizeof(HitDesc)));
+    STRY(hipMalloc((void**)&dlist, max_n * 4));
+    STRY(hipMalloc((void**)&dfill, 9 * 4));
+    STRY(hipMalloc((void**)&dtrav, max_trav * 4));
+    STRY(hipMalloc((void**)&dsame, max_n * 4));
+    STRY(hipMalloc((void**)&dres, max_n * sizeof(PairResult)));
+    std::vector<PairResult> hres(max_n);
+    std::vector<int32_t> hsame(max_n), htrav(max_trav);
+    std::vector<PairDesc> hpd;
+    std::vector<StrOut> hso;
+    std::vector<char> hlines;
+    if (want_lines) {
+      const size_t nq = (size_t)queries->offsets[queries->n_seqs], nt = (size_t)templates->offsets[n_t];
+      STRY(hipMalloc((void**)&dpd, max_n * sizeof(PairDesc)));
+      STRY(hipMalloc((void**)&dso, max_n * sizeof(StrOut)));
+      STRY(hipMalloc((void**)&dlines, max_n * 2 * (size_t)line_stride));
+      STRY(hipMalloc((void**)&dqch, std::max<size_t>(nq, 1)));
+      STRY(hipMalloc((void**)&dtch, std::max<size_t>(nt, 1)));
+      STRY(hipMemcpyAsync(dqch, queries->residues, nq, hipMemcpyHostToDevice, ctx->stream));
+      STRY(hipMemcpyAsync(dtch, templates->residues, nt, hipMemcpyHostToDevice, ctx->stream));
+      hpd.resize(max_n); hso.resize(max_n); hlines.resize(max_n * 2 * (size_t)line_stride);
+    }
+    for (const Chunk& c : chunks) {
+      const int n = (int)c.n;
+      AClassOff co = {};
+      for (int k = 1; k < 9; ++k) co.off[k] = co.off[k - 1] + c.cls_cnt[k - 1];
+      STRY(hipMemcpyAsync(ddesc, fast.data() + c.h0, (size_t)n * sizeof(HitDesc), hipMemcpyHostToDevice, ctx->stream));
+      STRY(hipMemsetAsync(dfill, 0, 9 * 4, ctx->stream));
+      hipLaunchKernelGGL(ahit_list_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ddesc, n, co, dfill, dlist);
+      STRY(hipGetLastError());
+      AlignArgs g = {};
+      g.desc = ddesc; g.strip = dstrip; g.trav = dtrav; g.trav_stride = c.trav_stride; g.res = dres; g.same = dsame;
+      for (int k = 1; k <= 8; ++k) {
+        if (c.cls_cnt[k] == 0) continue;
+        g.list = dlist + co.off[k];
+        launch_align_kernel(k, c.cls_cnt[k], ctx->stream, run.a, g);
+        STRY(hipGetLastError());
+      }
+      if (want_lines) {
+        for (int h = 0; h < n; ++h) {
+          const HitDesc& d = fast[c.h0 + h];
+          PairDesc pd = {};
+          pd.Q = (int32_t)(queries->offsets[d.q + 1] - queries->offsets[d.q]);
+          pd.T = (int32_t)(templates->offsets[d.t + 1] - templates->offsets[d.t]);
+          pd.q_seq = d.q; pd.t_seq = d.t; pd.q_off = queries->offsets[d.q]; pd.t_off = templates->offsets[d.t];
+          hpd[h] = pd;
+        }
+        STRY(hipMemcpyAsync(dpd, hpd.data(), (size_t)n * sizeof(PairDesc), hipMemcpyHostToDevice, ctx->stream));
+        StrParams prm = {c.trav_stride, 1, 0, line_stride};
+        RTRY(launch_gapped_strings(ctx, n, dpd, dres, dtrav, dqch, dtch, dlines, dso, prm));
+        STRY(hipMemcpyAsync(hso.data(), dso, (size_t)n * sizeof(StrOut), hipMemcpyDeviceToHost, ctx->stream));
+        STRY(hipMemcpyAsync(hlines.data(), dlines, (size_t)n * 2 * (size_t)line_stride, hipMemcpyDeviceToHost, ctx->stream));
+      }
+      STRY(hipMemcpyAsync(hres.data(), dres, (size_t)n * sizeof(PairResult), hipMemcpyDeviceToHost, ctx->stream));
+      STRY(hipMemcpyAsync(hsame.data(), dsame, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+      if (pairs) STRY(hipMemcpyAsync(htrav.data(), dtrav, (size_t)n * c.trav_stride * 8, hipMemcpyDeviceToHost, ctx->stream));
+      STRY(hipStreamSynchronize(ctx->stream));                 // the host vectors above are read by the copies until here
+      for (int h = 0; h < n; ++h) {
+        const HitDesc& d = fast[c.h0 + h];
+        const PairResult& r = hres[h];
+        const int64_t Q = queries->offsets[d.q + 1] - queries->offsets[d.q], T = templates->offsets[d.t + 1] - templates->offsets[d.t];
+        const float ident = r.status == 0 ? float(hsame[h] - 2) / float(std::min(Q, T) - 2) * 100.f : 0.f;   // alignment.h:864
+        int len = 0; const char* tl = nullptr; const char* ql = nullptr; int st = r.status;
+        if (want_lines && st == 0) {
+          if (hso[h].err == ALN_E_OVERFLOW) len = line_stride;             // put() turns it into the slot's status
+          else if (hso[h].err != ALN_OK) st = hso[h].err;
+          else { len = hso[h].length; tl = hlines.data() + (size_t)h * 2 * line_stride; ql = tl + line_stride; }
+        }
+        ao.put(fast_slot[c.h0 + h], st, r.best, ident, r.n_path, htrav.data() + (size_t)h * c.trav_stride * 2, true, len, tl, ql);
+      }
+    }
+#undef STRY
+#undef RTRY
+    cleanup();
+  }
+  if (!bq.empty()) {
+    rc = align_through_batches(ctx, queries, templates, sub, gap, bq, bt, bslot, ao);
+    if (rc != ALN_OK) return rc;
+  }
+  return ao.worst;
+}

@@ -176,7 +176,7 @@ int aln_ctx_synchronize(aln_ctx* ctx);
 int aln_has_gfx950(void);
 /* Tuning / kernel-selection hints of ONE context.  A context reads its defaults from the environment once, when it is created
  * (ALN_NO_TAG_KERNEL, ALN_NO_H16, ALN_NO_KEY16, ALN_TAG_ALT_PRIO, ALN_TAG_SEGMENTS, ALN_DP_VARIANT="NW,R[,X]", ALN_EXACT_NO_TILES,
- * ALN_EXACT_LITERAL, ALN_EXACT_ALT_PRIO, ALN_SCORE_NO_PACKED, ALN_ENUM_NODE_CAP, ALN_TAG_LAG, ALN_TAG_SOLO, ALN_TAG_BITS, ALN_TAG_OCCUPANCY, ALN_PLANE_ROW_ALIGN, ALN_ENUM_POOL_RETRIES, ALN_ENUM_WAVES, ALN_ENUM_DEBUG, ALN_ENUM_KEEP_POOLS, ALN_SEARCH_SLAB_ROWS, ALN_SEARCH_DEBUG); launches never read the environment.  Keys:
+ * ALN_EXACT_LITERAL, ALN_EXACT_ALT_PRIO, ALN_SCORE_NO_PACKED, ALN_ENUM_NODE_CAP, ALN_TAG_LAG, ALN_TAG_SOLO, ALN_TAG_BITS, ALN_TAG_OCCUPANCY, ALN_PLANE_ROW_ALIGN, ALN_ENUM_POOL_RETRIES, ALN_ENUM_WAVES, ALN_ENUM_DEBUG, ALN_ENUM_KEEP_POOLS, ALN_SEARCH_SLAB_ROWS, ALN_SEARCH_DEBUG, ALN_ZSCORE_CHUNK_ROWS, ALN_ALIGN_CHUNK_HITS); launches never read the environment.  Keys:
  *   "tag_kernel" "h16" "key16"     1/0: tagged-key kernel / uint16 score plane / 16-bit key layout allowed (results identical)
  *   "tag_alt_prio"                  1/0: row-alternating wave priority in the tagged kernel (a scheduling hint; pays when launches
  *                                   follow each other on one stream, loses when launches of several contexts overlap);
@@ -212,6 +212,8 @@ int aln_has_gfx950(void);
  *   "zscore_chunk_rows"             aln_hits_zscores: query rows whose shuffled strings and accumulators are resident on the device at a
  *                                   time; 0 (default) = as many as keep the shuffled pool (n_shuffles x |q| bytes per row with a hit) and the
  *                                   accumulators (16 B x K per row) below 1 GiB each; a larger value is cut to that
+ *   "align_chunk_hits"              aln_hits_align: hit slots whose 1 B/cell strips are resident on the device at a time; 0 (default) = as
+ *                                   many as keep the strips, the lists and the lines below 1 GiB each; a value never lifts that budget
  * Unknown key -> ALN_E_ARG.  No hint changes any result. */
 int aln_ctx_set_hint(aln_ctx* ctx, const char* key, int64_t value);
 int aln_ctx_get_hint(const aln_ctx* ctx, const char* key, int64_t* value);
@@ -390,6 +392,41 @@ int aln_hits_zscores(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* temp
                      const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K,
                      const aln_hit* hits /* (q_end-q_begin) x K */, const int32_t* n_hits /* q_end-q_begin */,
                      int32_t n_shuffles, uint32_t seed, aln_hit_stats* stats /* (q_end-q_begin) x K */);
+
+/* ---- the alignments of search hits, traced on the device from the end cells the search reported -------------------- */
+/* One record per hit slot.  Unused slots hold { 0, 0, 0.0f, 0.0f }. */
+typedef struct {
+  int32_t n_pairs;          /* length of the pair list, 0 for an unused slot */
+  int32_t status;           /* 0, ALN_E_STARTPAIR, ALN_E_OVERFLOW (list longer than pair_stride, line longer than line_stride), ALN_E_ARG (below) */
+  float   score;            /* the score Optimal reports, bit-identical to aln_score_all_vs_all */
+  float   identity;         /* calcIdentity, alignment.h:856-865, as aln_batch_optimal_strings reports it */
+} aln_hit_alignment;        /* 16 bytes */
+/* Optimal's alignment (optimal.h:48-105) of every used slot of a hit list in aln_search_topk's layout (row r is query
+ * q_begin + r, slots k < n_hits[r] are used; duplicates allowed): out[r * K + k], the pair list in list order at
+ * pairs + (r * K + k) * pair_stride * 2 (pairs == NULL: not wanted), the gapped template / query lines at
+ * tlines / qlines + (r * K + k) * line_stride, NUL-terminated, and their length in lengths (the three line arguments all NULL:
+ * not wanted; lengths alone may be NULL).  Every value is what aln_batch_create over the pair + aln_batch_dp(ALN_SIM_SUBMATRIX,
+ * gap, ALN_FWD, ALN_DP_AUTO) + aln_batch_optimal / aln_batch_optimal_strings give, bit for bit.
+ * ALN_LOCAL: the slot's (q_end, t_end) is TRUSTED as the cell the traceback starts from — it must be the cell aln_search_topk
+ * reported (1 <= q_end <= Q-2, 1 <= t_end <= T-2 for pairs with Q >= 3 and T >= 3, else ALN_E_ARG before anything is written).
+ * With an integer table and gaps and a template of up to 2048 columns one wave per hit sweeps rows 1 .. q_end with the state
+ * in registers, writes 1 byte per cell into a transient strip and walks back through it (csrc/search_align.hip): no batch, no
+ * planes, no find_max.  When the sweep's D[q_end][t_end] differs from the slot's .score the slot reports status ALN_E_ARG and
+ * n_pairs 0 and the call goes on.  The four other align types ignore q_end / t_end.  They, longer templates, fractional
+ * scoring systems and pairs without an interior go through resident batches inside the call (~12 GB of planes at a time), so
+ * the call accepts what aln_search_topk accepts.
+ * Checks, in this order, nothing written when one fails: NULL hits / n_hits / out, K outside 1..1024, pairs with
+ * pair_stride < 2, the line group given in part or line_stride < 1 (ALN_E_ARG); aln_score_all_vs_all's, in its order; every
+ * n_hits[r] in 0..K, every used slot's t in [0, n_templates) and, local, its end cell in range (ALN_E_ARG).
+ * q_begin == q_end: ALN_OK, nothing written.  A list longer than pair_stride (its first pair_stride entries are written) or a
+ * line that does not fit line_stride (empty lines) gives the slot ALN_E_OVERFLOW.  Returns when every output is complete: the
+ * lowest (most negative) per-slot status, ALN_OK when all are 0.  Hits are handled a chunk at a time (hint "align_chunk_hits"). */
+int aln_hits_align(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
+                   const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K,
+                   const aln_hit* hits, const int32_t* n_hits,
+                   aln_hit_alignment* out /* (q_end-q_begin) x K */,
+                   int32_t* pairs, int32_t pair_stride /* NULL, or rows x K x pair_stride x 2 int32 */,
+                   char* tlines, char* qlines, int32_t line_stride, int32_t* lengths /* all NULL, or as aln_batch_optimal_strings */);
 
 /* ---- multi-GPU: a length-sorted deal of independent units + ONE collective (RCCL all-gather of scores) ----------- */
 /* The reference is one thread, one DPMatrix at a time; pairs are independent (dpmatrix.h:104-111), so ranks own disjoint pair
