@@ -1,30 +1,15 @@
-// score_common.h — what the all-vs-all score kernels (score_only.hip) and the top-K search built on them (search_topk.hip) share:
-// the DPP helpers of the collapsed recurrence, the kernels' argument block, and ScoreRun, the host side of one all-vs-all
-// scoring call cut into steps so that a caller can leave the scores of a slab of query rows in a device buffer of its own.
+// score_common.h — what the all-vs-all score kernels (score_only.hip) and the entries built on them (search_topk.hip,
+// search_zscore.hip, search_align.hip) share beside the row sweep itself (score_sweep.h): the kernels' argument block, how
+// work is listed and launched by template length class, and ScoreRun, the host side of one all-vs-all scoring call cut into
+// steps so that a caller can leave the scores of a slab of query rows in a device buffer of its own.
 #pragma once
 #include <deque>
+#include <type_traits>
 #include <vector>
 
-#include "aln_internal.h"
+#include "score_sweep.h"
 
 namespace aln {
-
-constexpr int kNegS = -(1 << 28);
-
-template <int CTRL, int ROW_MASK = 0xF, int BANK_MASK = 0xF>
-__device__ __forceinline__ int sdpp(int old, int src) {
-  return __builtin_amdgcn_update_dpp(old, src, CTRL, ROW_MASK, BANK_MASK, false);
-}
-__device__ __forceinline__ int wave_incl_max_s(int v) {
-  const int ident = (int)0x80000000;
-  v = max(v, sdpp<0x111>(ident, v));
-  v = max(v, sdpp<0x112>(ident, v));
-  v = max(v, sdpp<0x114>(ident, v));
-  v = max(v, sdpp<0x118>(ident, v));
-  v = max(v, sdpp<0x142, 0xA>(ident, v));
-  v = max(v, sdpp<0x143, 0xC>(ident, v));
-  return v;
-}
 
 struct ScoreArgs {
   const uint8_t* qcodes; const int64_t* qoff;   // query pool, offsets (n_q + 1)
@@ -36,6 +21,37 @@ struct ScoreArgs {
   int q_begin, n_t;
   int gi, ge;
 };
+
+// A template of T <= 2048 columns is of length class R = ceil(T / 256): the groups of 256 columns a wave sweeps.
+// dispatch_r calls f(std::integral_constant<int, R>) for the runtime class r (1 .. RMAX; a larger r takes RMAX).
+template <int RMAX, class F>
+inline void dispatch_r(int r, F&& f) {
+  if constexpr (RMAX > 1) {
+    if (r < RMAX) return dispatch_r<RMAX - 1>(r, f);
+  }
+  f(std::integral_constant<int, RMAX>());
+}
+
+struct ClassOff { int off[9]; };
+
+// list[off[c] ..) = the slots h < n_slots with cls(h) == c (cls(h) < 0: unused slot), in no particular order; fill[9] starts at 0
+template <class ClassOf>
+__global__ __launch_bounds__(256) void class_list_kernel(ClassOf cls_of, int n_slots, ClassOff co, int32_t* fill, int32_t* list) {
+  __shared__ int lc[9], lb[9];
+  const int tid = threadIdx.x;
+  const int h = blockIdx.x * 256 + tid;
+  if (tid < 9) lc[tid] = 0;
+  __syncthreads();
+  int cls = -1, my = 0;
+  if (h < n_slots) {
+    cls = cls_of(h);
+    if (cls >= 0) my = atomicAdd(&lc[cls], 1);
+  }
+  __syncthreads();
+  if (tid < 9 && lc[tid]) lb[tid] = co.off[tid] + atomicAdd(&fill[tid], lc[tid]);
+  __syncthreads();
+  if (cls >= 0) list[lb[cls] + my] = h;
+}
 
 // One all-vs-all scoring call (the arguments of aln_score_all_vs_all): prepare() checks them and decides the route, upload()
 // puts what the register-resident kernels read on the device, launch() enqueues those kernels for a block of query rows

@@ -6,6 +6,7 @@
 // with the whole state in VGPRs — the same collapsed recurrence as dp_affine_tag.hip, without tags:
 //   E(j) by a DPP max-plus prefix scan of A(k) = D[i-1][k] + ge k, F by a per-column running max of D[k][c] + ge k,
 //   best = max3(match, E, F) + S, clipped at 0, running maximum per lane.
+// The sweep itself is score_sweep.h's (sweep_local, sweep_global); only the packed 16-bit kernel below carries its own.
 // Algorithmic bytes per pair: |q| + |t| residue bytes in, 4 bytes out (~0 B/cell) — the kernel is
 // bound by VALU issue (about 6 half-rate + 8 full-rate instructions per cell), not by HBM.
 // Grid: x = template index, y = query index inside the caller's row block; templates are replicated on every GPU,
@@ -30,110 +31,10 @@ __global__ __launch_bounds__(64) void score_local_kernel(ScoreArgs a) {
   const uint8_t* __restrict__ qc = a.qcodes + a.qoff[qi];
   const uint8_t* __restrict__ tc = a.tcodes + a.toff[ti];
   const int Q = (int)(a.qoff[qi + 1] - a.qoff[qi]), T = (int)(a.toff[ti + 1] - a.toff[ti]);
-  const int gi = a.gi, ge = a.ge;
-  const int cb = 4 * lane;
-  const int gime = gi - ge;
-
-  int code4[R][4], gec[R][4], ekc[R][4], inm[R][4];
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int x = 0; x < 4; ++x) {
-      const int c = cb + 256 * r + x;
-      int code = kCodeTail;
-      if (c < T) code = tc[c];
-      code4[r][x] = code * 4;
-      gec[r][x] = ge * c;
-      ekc[r][x] = ge * c + gime;                                      // E(c+1) = prefix max - ekc
-      inm[r][x] = ((unsigned)(c - 1) < (unsigned)(T - 2)) ? -1 : 0;   // interior column: scores are >= 0, so "& mask" zeroes the rest
-    }
-  int d[R][4], gmx[R][4], cv[R], ak[R][4];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    cv[r] = kNegS;
-#pragma unroll
-    for (int x = 0; x < 4; ++x) { d[r][x] = 0; gmx[r][x] = kNegS; }
-  }
-  int lmax = 0;
-  auto tab_at = [&](int qrow, int c4) -> int {
-    return *reinterpret_cast<const int*>(reinterpret_cast<const char*>(tab) + qrow + c4);
-  };
-  // prefix-scan preparation on the row held in d[] + running maximum
-  auto finish_row = [&]() {
-    int sk = kNegS;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      int tk = kNegS;
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        int A = d[r][x] + gec[r][x];
-        if (r == 0 && x == 0) A = (lane == 0) ? kNegS : A;   // column 0 is never a source
-        ak[r][x] = A;
-        tk = max(tk, A);
-      }
-      lmax = max(max(lmax, d[r][0]), d[r][1]);               // two v_max3 per group
-      lmax = max(max(lmax, d[r][2]), d[r][3]);
-      const int ik = wave_incl_max_s(tk);
-      const int ek = sdpp<0x138>(kNegS, ik);
-      cv[r] = max(sk, ek);
-      sk = max(sk, __builtin_amdgcn_readlane(ik, 63));
-    }
-  };
-  if (Q >= 3) {
-    // row 1 (dpmatrix.h:579-590): local mode -> end gaps are free: clip(S[1][c])
-    const int qrow = (int)qc[1] * 128;
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        const int c = cb + 256 * r + x;
-        const int h = max(tab_at(qrow, code4[r][x]), 0);
-        d[r][x] = h & inm[r][x];
-        (void)c;
-      }
-    finish_row();
-  }
-  int qcode_next = (Q >= 4) ? (int)qc[2] : 0;
-  for (int i = 2; i <= Q - 2; ++i) {                        // dpmatrix.h:607-649
-    const int qrow = qcode_next * 128;
-    if (i + 1 <= Q - 2) qcode_next = (int)qc[i + 1];
-    const int roff = gi + ge * (i - 2);
-    const int rowB = ge * (i - 1);
-    int bk[R][4];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      int pv = cv[r];
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        const int m = d[r][x];
-        const int A = ak[r][x];
-        const int e = pv - ekc[r][x];
-        const int f = gmx[r][x] - roff;
-        bk[r][x] = max(max(m, e), f);
-        pv = max(pv, A);
-        gmx[r][x] = max(gmx[r][x], m + rowB);
-      }
-    }
-    int prev_k = 0;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      int uk = sdpp<0x138>(0, bk[r][3]);
-      if (r > 0) uk = (lane == 0) ? prev_k : uk;
-      prev_k = __builtin_amdgcn_readlane(bk[r][3], 63);
-      const bool masked = (r == 0) || (256 * (r + 1) > T - 1);
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        const int c = cb + 256 * r + x;
-        const int s = tab_at(qrow, code4[r][x]);
-        int h = max(((x == 0) ? uk : bk[r][x - 1]) + s, 0);
-        if (r == 0 && x == 1) h = (c == 1) ? max(s, 0) : h;  // column 1 (lane 0 only): free insertion from the origin (:593-599)
-        if (masked) h &= inm[r][x];                          // columns 0 and >= T-1 stay 0
-        d[r][x] = h;
-      }
-    }
-    finish_row();
-  }
-  int m = lmax;
+  LocalCols<R> cols;
+  cols.load(tc, T, a.gi, a.ge);
+  int d[R][4];
+  int m = sweep_local<R>(tab, cols, qc, Q - 2, d, NoObserver());
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) m = max(m, __shfl_xor(m, o));
   if (lane == 0) a.scores[(size_t)blockIdx.y * a.n_t + ti] = (float)m;
@@ -141,10 +42,6 @@ __global__ __launch_bounds__(64) void score_local_kernel(ScoreArgs a) {
 
 
 // ---- the four non-local align types: the score Optimal reports is the FINAL cell's (optimal.h:56-74) ---------------------------
-// Same row sweep without the clip: values may be negative, so columns outside the interior are kept at "minus infinity"
-// instead of being masked to 0; row 1 and column 1 pay (or not: free end gaps, aasubalib.h:34-49,60-75) the gap from the origin
-// (dpmatrix.h:409-426); the final cell (dpmatrix.h:505-534) is the best of the last interior cell, a deletion from the last
-// interior row and an insertion from the last interior column, each free or priced by the align type.
 template <int R>
 __global__ __launch_bounds__(64) void score_global_kernel(ScoreArgs a, int free_del, int free_ins) {
   __shared__ int tab[32 * 32];
@@ -165,136 +62,9 @@ __global__ __launch_bounds__(64) void score_global_kernel(ScoreArgs a, int free_
     if (lane == 0) *out = (float)(-cost);
     return;
   }
-  const int cb = 4 * lane;
-  const int gime = gi - ge;
-  const int cl = T - 2;                                            // last interior column; its (wave-uniform) slot and lane
-  const int rs = cl / 256, xs = cl & 3, ls = (cl & 255) >> 2;
-
-  int code4[R][4], gec[R][4], ekc[R][4]; bool in[R][4];
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int x = 0; x < 4; ++x) {
-      const int c = cb + 256 * r + x;
-      int code = kCodeTail;
-      if (c < T) code = tc[c];
-      code4[r][x] = code * 4;
-      gec[r][x] = ge * c;
-      ekc[r][x] = ge * c + gime;
-      in[r][x] = (unsigned)(c - 1) < (unsigned)(T - 2);
-    }
-  int d[R][4], gmx[R][4], cv[R], ak[R][4];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    cv[r] = kNegS;
-#pragma unroll
-    for (int x = 0; x < 4; ++x) { d[r][x] = kNegS; gmx[r][x] = kNegS; }
-  }
-  int clast = kNegS;                                               // max over rows of D[k][T-2] (free insertions into the final cell)
-  auto tab_at = [&](int qrow, int c4) -> int {
-    return *reinterpret_cast<const int*>(reinterpret_cast<const char*>(tab) + qrow + c4);
-  };
-  auto pick = [&](const int (&v)[R][4]) -> int {                   // this lane's value in slot (rs, xs)
-    int o = kNegS;
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-      for (int x = 0; x < 4; ++x) o = (r == rs && x == xs) ? v[r][x] : o;
-    return o;
-  };
-  auto finish_row = [&]() {
-    int sk = kNegS;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      int tk = kNegS;
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        const int A = d[r][x] + gec[r][x];                       // non-interior cells hold "minus infinity": never a source
-        ak[r][x] = A;
-        tk = max(tk, A);
-      }
-      const int ik = wave_incl_max_s(tk);
-      const int ek = sdpp<0x138>(kNegS, ik);
-      cv[r] = max(sk, ek);
-      sk = max(sk, __builtin_amdgcn_readlane(ik, 63));
-    }
-    const int v = pick(d);
-    clast = max(clast, lane == ls ? v : kNegS);
-  };
-  {
-    // row 1 (dpmatrix.h:409-418): one deletion from the origin, free if the template's head gap is
-    const int qrow = (int)qc[1] * 128;
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        const int c = cb + 256 * r + x;
-        const int cost = (c >= 2 && !free_del) ? gi + ge * (c - 2) : 0;
-        d[r][x] = in[r][x] ? tab_at(qrow, code4[r][x]) - cost : kNegS;
-      }
-    finish_row();
-  }
-  int qcode_next = (Q >= 4) ? (int)qc[2] : 0;
-  for (int i = 2; i <= Q - 2; ++i) {                               // dpmatrix.h:447-486
-    const int qrow = qcode_next * 128;
-    if (i + 1 <= Q - 2) qcode_next = (int)qc[i + 1];
-    const int roff = gi + ge * (i - 2);
-    const int rowB = ge * (i - 1);
-    const int col1 = free_ins ? 0 : roff;                          // column 1: one insertion from the origin (:421-426)
-    int bk[R][4];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      int pv = cv[r];
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        const int m = d[r][x];
-        const int A = ak[r][x];
-        const int e = pv - ekc[r][x];
-        const int f = gmx[r][x] - roff;
-        bk[r][x] = max(max(m, e), f);
-        pv = max(pv, A);
-        gmx[r][x] = max(gmx[r][x], m + rowB);
-      }
-    }
-    int prev_k = 0;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      int uk = sdpp<0x138>(0, bk[r][3]);
-      if (r > 0) uk = (lane == 0) ? prev_k : uk;
-      prev_k = __builtin_amdgcn_readlane(bk[r][3], 63);
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        const int c = cb + 256 * r + x;
-        const int s = tab_at(qrow, code4[r][x]);
-        int h = ((x == 0) ? uk : bk[r][x - 1]) + s;
-        if (r == 0 && x == 1) h = (c == 1) ? s - col1 : h;
-        d[r][x] = in[r][x] ? h : kNegS;
-      }
-    }
-    finish_row();
-  }
-  // ---- the final cell (dpmatrix.h:505-534): row Q-2 is in d[], gmx holds rows <= Q-3, clast every row of column T-2 -----
-  int best = (lane == ls) ? pick(d) : kNegS;                       // match: D[Q-2][T-2] (the final cell's similarity is 0)
-  {
-    int dl = kNegS;                                                // deletion from (Q-2, k), k = 1 .. T-2 (k = T-2 costs nothing)
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        const int c = cb + 256 * r + x;
-        const int len = T - 2 - c;
-        const int cost = (len < 1 || free_del) ? 0 : gi + ge * (len - 1);
-        dl = max(dl, in[r][x] ? d[r][x] - cost : kNegS);
-      }
-    best = max(best, dl);
-    int il;                                                        // insertion from (k, T-2), k = 1 .. Q-2
-    if (free_ins) il = clast;
-    else {
-      const int g = pick(gmx);                                     // max over k <= Q-3 of D[k][T-2] + ge k
-      il = (lane == ls && Q >= 4) ? g - (gi + ge * (Q - 3)) : kNegS;
-    }
-    best = max(best, il);
-  }
+  GlobalCols<R> cols;
+  cols.load(tc, T, gi, ge);
+  int best = sweep_global<R>(tab, cols, qc, Q, free_del, free_ins);
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) best = max(best, __shfl_xor(best, o));
   if (lane == 0) *out = (float)best;
@@ -640,43 +410,13 @@ int ScoreRun::launch(int row0, int nrows, float* dscores) {
       s.scores = dscores + (size_t)r0 * n_t;
       s.tsel = dsel + cls_begin[r];
       s.qsel = dqsel ? dqsel + row0 + r0 : nullptr;
-      if (packed) {
-        const dim3 grid(nc, (nr + 1) / 2);             // two query rows per wave
-        switch (r) {
-          case 1: hipLaunchKernelGGL(score_local_pk_kernel<1>, grid, block, 0, ctx->stream, s, nr); break;
-          case 2: hipLaunchKernelGGL(score_local_pk_kernel<2>, grid, block, 0, ctx->stream, s, nr); break;
-          case 3: hipLaunchKernelGGL(score_local_pk_kernel<3>, grid, block, 0, ctx->stream, s, nr); break;
-          case 4: hipLaunchKernelGGL(score_local_pk_kernel<4>, grid, block, 0, ctx->stream, s, nr); break;
-          case 5: hipLaunchKernelGGL(score_local_pk_kernel<5>, grid, block, 0, ctx->stream, s, nr); break;
-          case 6: hipLaunchKernelGGL(score_local_pk_kernel<6>, grid, block, 0, ctx->stream, s, nr); break;
-          case 7: hipLaunchKernelGGL(score_local_pk_kernel<7>, grid, block, 0, ctx->stream, s, nr); break;
-          default: hipLaunchKernelGGL(score_local_pk_kernel<8>, grid, block, 0, ctx->stream, s, nr); break;
-        }
-      } else if (!local) {
-        const dim3 grid(nc, nr);
-        switch (r) {
-          case 1: hipLaunchKernelGGL(score_global_kernel<1>, grid, block, 0, ctx->stream, s, free_del, free_ins); break;
-          case 2: hipLaunchKernelGGL(score_global_kernel<2>, grid, block, 0, ctx->stream, s, free_del, free_ins); break;
-          case 3: hipLaunchKernelGGL(score_global_kernel<3>, grid, block, 0, ctx->stream, s, free_del, free_ins); break;
-          case 4: hipLaunchKernelGGL(score_global_kernel<4>, grid, block, 0, ctx->stream, s, free_del, free_ins); break;
-          case 5: hipLaunchKernelGGL(score_global_kernel<5>, grid, block, 0, ctx->stream, s, free_del, free_ins); break;
-          case 6: hipLaunchKernelGGL(score_global_kernel<6>, grid, block, 0, ctx->stream, s, free_del, free_ins); break;
-          case 7: hipLaunchKernelGGL(score_global_kernel<7>, grid, block, 0, ctx->stream, s, free_del, free_ins); break;
-          default: hipLaunchKernelGGL(score_global_kernel<8>, grid, block, 0, ctx->stream, s, free_del, free_ins); break;
-        }
-      } else {
-        const dim3 grid(nc, nr);
-        switch (r) {
-          case 1: hipLaunchKernelGGL(score_local_kernel<1>, grid, block, 0, ctx->stream, s); break;
-          case 2: hipLaunchKernelGGL(score_local_kernel<2>, grid, block, 0, ctx->stream, s); break;
-          case 3: hipLaunchKernelGGL(score_local_kernel<3>, grid, block, 0, ctx->stream, s); break;
-          case 4: hipLaunchKernelGGL(score_local_kernel<4>, grid, block, 0, ctx->stream, s); break;
-          case 5: hipLaunchKernelGGL(score_local_kernel<5>, grid, block, 0, ctx->stream, s); break;
-          case 6: hipLaunchKernelGGL(score_local_kernel<6>, grid, block, 0, ctx->stream, s); break;
-          case 7: hipLaunchKernelGGL(score_local_kernel<7>, grid, block, 0, ctx->stream, s); break;
-          default: hipLaunchKernelGGL(score_local_kernel<8>, grid, block, 0, ctx->stream, s); break;
-        }
-      }
+      const dim3 grid(nc, packed ? (nr + 1) / 2 : nr);   // packed: two query rows per wave
+      dispatch_r<8>(r, [&](auto rc) {
+        constexpr int R = decltype(rc)::value;
+        if (packed) hipLaunchKernelGGL(score_local_pk_kernel<R>, grid, block, 0, ctx->stream, s, nr);
+        else if (!local) hipLaunchKernelGGL(score_global_kernel<R>, grid, block, 0, ctx->stream, s, free_del, free_ins);
+        else hipLaunchKernelGGL(score_local_kernel<R>, grid, block, 0, ctx->stream, s);
+      });
       STRY(hipGetLastError());
     }
   }

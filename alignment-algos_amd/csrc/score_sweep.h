@@ -1,0 +1,327 @@
+// score_sweep.h — the register-resident row sweep of the collapsed recurrence, 32-bit, device only.
+//
+// One wave holds a whole DP row in VGPRs: lane l owns columns 256 r + 4 l + x (r < R groups, x < 4).  Per row
+//   E(j) comes from a DPP max-plus prefix scan of A(k) = D[i-1][k] + ge k, F from a per-column running max of D[k][c] + ge k,
+//   best = max3(match, E, F) + S.
+// Two recurrences live here, each as a pair "column state" (built once per template) + "sweep" (run once per query string):
+//   LocalCols<R>  + sweep_local   clipped at 0, end gaps free, columns outside the interior masked to 0        (dpmatrix.h:538-689)
+//   GlobalCols<R> + sweep_global  the four non-local align types: no clip, "minus infinity" outside the interior,
+//                                 end gaps priced per align type, the final cell included                      (dpmatrix.h:375-534)
+// Users: score_only.hip (scores), search_topk.hip (end cells), search_zscore.hip (one sweep per shuffle), search_align.hip
+// (five bits per cell into a strip).  What a user sees of the local sweep beyond its result goes through an observer; the
+// packed 16-bit kernel of score_only.hip has its own types and its own sweep.
+#pragma once
+#include "aln_internal.h"
+
+namespace aln {
+
+constexpr int kNegS = -(1 << 28);
+
+template <int CTRL, int ROW_MASK = 0xF, int BANK_MASK = 0xF>
+__device__ __forceinline__ int sdpp(int old, int src) {
+  return __builtin_amdgcn_update_dpp(old, src, CTRL, ROW_MASK, BANK_MASK, false);
+}
+__device__ __forceinline__ int wave_incl_max_s(int v) {
+  const int ident = (int)0x80000000;
+  v = max(v, sdpp<0x111>(ident, v));
+  v = max(v, sdpp<0x112>(ident, v));
+  v = max(v, sdpp<0x114>(ident, v));
+  v = max(v, sdpp<0x118>(ident, v));
+  v = max(v, sdpp<0x142, 0xA>(ident, v));
+  v = max(v, sdpp<0x143, 0xC>(ident, v));
+  return v;
+}
+
+// S[q][c] from the 32 x 32 LDS table: qrow = 128 * query code, c4 = 4 * template code (byte offsets)
+__device__ __forceinline__ int sweep_tab_at(const int* tab, int qrow, int c4) {
+  return *reinterpret_cast<const int*>(reinterpret_cast<const char*>(tab) + qrow + c4);
+}
+
+// What a user of sweep_local may watch.  The default watches nothing and compiles to nothing.
+struct NoObserver {
+  // cell(r, x, m, e, f, pv, A, gmx, key): a cell (group r, slot x) of row i-1 while row i is computed.  m, e, f are the three
+  // maxima row i's cell to its right chooses from; pv >= A says an earlier column of row i-1 holds at least this cell's deletion
+  // key, gmx >= key that an earlier row of the column holds at least its insertion key.  Then group(i, r): the lane's four cells
+  // of the group are through.
+  __device__ __forceinline__ void cell(int, int, int, int, int, int, int, int, int) {}
+  __device__ __forceinline__ void group(int, int) {}
+  // row(i, d, lane_max): row i is in d[]; lane_max is the lane's maximum over rows 1 .. i
+  template <int R>
+  __device__ __forceinline__ void row(int, const int (&)[R][4], int) {}
+};
+
+// ---- local -------------------------------------------------------------------------------------------------------------------
+template <int R>
+struct LocalCols {
+  int code4[R][4], gec[R][4], ekc[R][4], inm[R][4];
+  int T, gi, ge;
+  __device__ __forceinline__ void load(const uint8_t* tc, int T_, int gi_, int ge_) {
+    T = T_; gi = gi_; ge = ge_;
+    const int cb = 4 * (int)threadIdx.x;
+    const int gime = gi - ge;
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        const int c = cb + 256 * r + x;
+        int code = kCodeTail;
+        if (c < T) code = tc[c];
+        code4[r][x] = code * 4;
+        gec[r][x] = ge * c;
+        ekc[r][x] = ge * c + gime;                                      // E(c+1) = prefix max - ekc
+        inm[r][x] = ((unsigned)(c - 1) < (unsigned)(T - 2)) ? -1 : 0;   // interior column: scores are >= 0, so "& mask" zeroes the rest
+      }
+  }
+};
+
+// Rows 1 .. last of the query codes qc (last <= Q - 2; last < 1: no row).  Leaves row `last` in d[] (all 0 without a row) and
+// returns the lane's maximum over every cell it computed.  The sweep owns that maximum and both inner loops stay in this
+// function: an observer that keeps the maximum by reference, or a helper that takes the row arrays by reference, costs
+// registers and with them waves per SIMD.
+template <int R, class Obs>
+__device__ __forceinline__ int sweep_local(const int* tab, const LocalCols<R>& k, const uint8_t* qc, int last,
+                                           int (&d)[R][4], Obs&& obs) {
+  const int lane = threadIdx.x;
+  const int cb = 4 * lane;
+  const int gi = k.gi, ge = k.ge, T = k.T;
+  int gmx[R][4], cv[R], ak[R][4];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    cv[r] = kNegS;
+#pragma unroll
+    for (int x = 0; x < 4; ++x) { d[r][x] = 0; gmx[r][x] = kNegS; }
+  }
+  int lmax = 0;
+  // prefix-scan preparation on the row held in d[] (ak = D + ge c, cv[r] = the maximum of the keys left of the lane's group r)
+  // + running maximum
+  auto finish_row = [&]() {
+    int sk = kNegS;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      int tk = kNegS;
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        int A = d[r][x] + k.gec[r][x];
+        if (r == 0 && x == 0) A = (lane == 0) ? kNegS : A;   // column 0 is never a source
+        ak[r][x] = A;
+        tk = max(tk, A);
+      }
+      lmax = max(max(lmax, d[r][0]), d[r][1]);               // two v_max3 per group
+      lmax = max(max(lmax, d[r][2]), d[r][3]);
+      const int ik = wave_incl_max_s(tk);
+      const int ek = sdpp<0x138>(kNegS, ik);
+      cv[r] = max(sk, ek);
+      sk = max(sk, __builtin_amdgcn_readlane(ik, 63));
+    }
+  };
+  if (last >= 1) {
+    // row 1 (dpmatrix.h:579-590): local mode -> end gaps are free: clip(S[1][c])
+    const int qrow = (int)qc[1] * 128;
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        const int h = max(sweep_tab_at(tab, qrow, k.code4[r][x]), 0);
+        d[r][x] = h & k.inm[r][x];
+      }
+    finish_row();
+    obs.row(1, d, lmax);
+  }
+  int qcode_next = (last >= 2) ? (int)qc[2] : 0;
+  for (int i = 2; i <= last; ++i) {                         // dpmatrix.h:607-649
+    const int qrow = qcode_next * 128;
+    if (i + 1 <= last) qcode_next = (int)qc[i + 1];
+    const int roff = gi + ge * (i - 2);
+    const int rowB = ge * (i - 1);
+    int bk[R][4];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      int pv = cv[r];
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        const int m = d[r][x];
+        const int A = ak[r][x];
+        const int e = pv - k.ekc[r][x];
+        const int f = gmx[r][x] - roff;
+        bk[r][x] = max(max(m, e), f);
+        obs.cell(r, x, m, e, f, pv, A, gmx[r][x], m + rowB);
+        pv = max(pv, A);
+        gmx[r][x] = max(gmx[r][x], m + rowB);
+      }
+      obs.group(i, r);
+    }
+    int prev_k = 0;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      int uk = sdpp<0x138>(0, bk[r][3]);
+      if (r > 0) uk = (lane == 0) ? prev_k : uk;
+      prev_k = __builtin_amdgcn_readlane(bk[r][3], 63);
+      const bool masked = (r == 0) || (256 * (r + 1) > T - 1);
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        const int c = cb + 256 * r + x;
+        const int s = sweep_tab_at(tab, qrow, k.code4[r][x]);
+        int h = max(((x == 0) ? uk : bk[r][x - 1]) + s, 0);
+        if (r == 0 && x == 1) h = (c == 1) ? max(s, 0) : h;  // column 1 (lane 0 only): free insertion from the origin (:593-599)
+        if (masked) h &= k.inm[r][x];                        // columns 0 and >= T-1 stay 0
+        d[r][x] = h;
+      }
+    }
+    finish_row();
+    obs.row(i, d, lmax);
+  }
+  return lmax;
+}
+
+// this lane's value in slot (rs, xs) of a row (rs, xs wave-uniform); `none` where the slot does not exist
+template <int R>
+__device__ __forceinline__ int sweep_pick(const int (&v)[R][4], int rs, int xs, int none) {
+  int o = none;
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int x = 0; x < 4; ++x) o = (r == rs && x == xs) ? v[r][x] : o;
+  return o;
+}
+
+// ---- non-local -----------------------------------------------------------------------------------------------------------------
+// Values may be negative, so columns outside the interior are kept at "minus infinity" instead of being masked to 0; row 1 and
+// column 1 pay (or not: free end gaps, aasubalib.h:34-49,60-75) the gap from the origin (dpmatrix.h:409-426); the final cell
+// (dpmatrix.h:505-534) is the best of the last interior cell, a deletion from the last interior row and an insertion from the
+// last interior column, each free or priced by the align type.
+template <int R>
+struct GlobalCols {
+  int code4[R][4], gec[R][4], ekc[R][4]; bool in[R][4];
+  int T, gi, ge;
+  int rs, xs, ls;                                                  // column T-2, the last interior one: its (wave-uniform) slot and lane
+  __device__ __forceinline__ void load(const uint8_t* tc, int T_, int gi_, int ge_) {
+    T = T_; gi = gi_; ge = ge_;
+    const int cb = 4 * (int)threadIdx.x;
+    const int gime = gi - ge;
+    const int cl = T - 2;
+    rs = cl / 256; xs = cl & 3; ls = (cl & 255) >> 2;
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        const int c = cb + 256 * r + x;
+        int code = kCodeTail;
+        if (c < T) code = tc[c];
+        code4[r][x] = code * 4;
+        gec[r][x] = ge * c;
+        ekc[r][x] = ge * c + gime;
+        in[r][x] = (unsigned)(c - 1) < (unsigned)(T - 2);
+      }
+  }
+};
+
+// Rows 1 .. Q-2 and the final cell (Q >= 3 and T >= 3: the callers deal with the degenerate shapes).  Returns the lane's
+// candidate for the final cell's score; the maximum over the wave is the score.
+template <int R>
+__device__ __forceinline__ int sweep_global(const int* tab, const GlobalCols<R>& k, const uint8_t* qc, int Q,
+                                            int free_del, int free_ins) {
+  const int lane = threadIdx.x;
+  const int cb = 4 * lane;
+  const int gi = k.gi, ge = k.ge, T = k.T, ls = k.ls;
+  int d[R][4], gmx[R][4], cv[R], ak[R][4];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    cv[r] = kNegS;
+#pragma unroll
+    for (int x = 0; x < 4; ++x) { d[r][x] = kNegS; gmx[r][x] = kNegS; }
+  }
+  int clast = kNegS;                                               // max over rows of D[k][T-2] (free insertions into the final cell)
+  auto finish_row = [&]() {
+    int sk = kNegS;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      int tk = kNegS;
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        const int A = d[r][x] + k.gec[r][x];                     // non-interior cells hold "minus infinity": never a source
+        ak[r][x] = A;
+        tk = max(tk, A);
+      }
+      const int ik = wave_incl_max_s(tk);
+      const int ek = sdpp<0x138>(kNegS, ik);
+      cv[r] = max(sk, ek);
+      sk = max(sk, __builtin_amdgcn_readlane(ik, 63));
+    }
+    const int v = sweep_pick<R>(d, k.rs, k.xs, kNegS);
+    clast = max(clast, lane == ls ? v : kNegS);
+  };
+  {
+    // row 1 (dpmatrix.h:409-418): one deletion from the origin, free if the template's head gap is
+    const int qrow = (int)qc[1] * 128;
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        const int c = cb + 256 * r + x;
+        const int cost = (c >= 2 && !free_del) ? gi + ge * (c - 2) : 0;
+        d[r][x] = k.in[r][x] ? sweep_tab_at(tab, qrow, k.code4[r][x]) - cost : kNegS;
+      }
+    finish_row();
+  }
+  int qcode_next = (Q >= 4) ? (int)qc[2] : 0;
+  for (int i = 2; i <= Q - 2; ++i) {                               // dpmatrix.h:447-486
+    const int qrow = qcode_next * 128;
+    if (i + 1 <= Q - 2) qcode_next = (int)qc[i + 1];
+    const int roff = gi + ge * (i - 2);
+    const int rowB = ge * (i - 1);
+    const int col1 = free_ins ? 0 : roff;                          // column 1: one insertion from the origin (:421-426)
+    int bk[R][4];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      int pv = cv[r];
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        const int m = d[r][x];
+        const int A = ak[r][x];
+        const int e = pv - k.ekc[r][x];
+        const int f = gmx[r][x] - roff;
+        bk[r][x] = max(max(m, e), f);
+        pv = max(pv, A);
+        gmx[r][x] = max(gmx[r][x], m + rowB);
+      }
+    }
+    int prev_k = 0;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      int uk = sdpp<0x138>(0, bk[r][3]);
+      if (r > 0) uk = (lane == 0) ? prev_k : uk;
+      prev_k = __builtin_amdgcn_readlane(bk[r][3], 63);
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        const int c = cb + 256 * r + x;
+        const int s = sweep_tab_at(tab, qrow, k.code4[r][x]);
+        int h = ((x == 0) ? uk : bk[r][x - 1]) + s;
+        if (r == 0 && x == 1) h = (c == 1) ? s - col1 : h;
+        d[r][x] = k.in[r][x] ? h : kNegS;
+      }
+    }
+    finish_row();
+  }
+  // ---- the final cell (dpmatrix.h:505-534): row Q-2 is in d[], gmx holds rows <= Q-3, clast every row of column T-2 -----
+  int best = (lane == ls) ? sweep_pick<R>(d, k.rs, k.xs, kNegS) : kNegS;   // match: D[Q-2][T-2] (the final cell's similarity is 0)
+  int dl = kNegS;                                                  // deletion from (Q-2, k), k = 1 .. T-2 (k = T-2 costs nothing)
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+      const int c = cb + 256 * r + x;
+      const int len = T - 2 - c;
+      const int cost = (len < 1 || free_del) ? 0 : gi + ge * (len - 1);
+      dl = max(dl, k.in[r][x] ? d[r][x] - cost : kNegS);
+    }
+  best = max(best, dl);
+  int il;                                                          // insertion from (k, T-2), k = 1 .. Q-2
+  if (free_ins) il = clast;
+  else {
+    const int g = sweep_pick<R>(gmx, k.rs, k.xs, kNegS);           // max over k <= Q-3 of D[k][T-2] + ge k
+    il = (lane == ls && Q >= 4) ? g - (gi + ge * (Q - 3)) : kNegS;
+  }
+  return max(best, il);
+}
+
+}  // namespace aln

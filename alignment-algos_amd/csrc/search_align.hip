@@ -3,10 +3,10 @@
 // aln_search_topk reports, per hit, the cell the optimal local alignment ends in.  Traceback through the collapsed recurrence of
 // score_only.hip needs neither scores nor (prev_q, prev_t) pointers: five bits per cell, all of them comparisons between values
 // the row sweep already holds, say which candidate won and where a gap jump lands.  So one wave per hit
-//   align_local_hit_kernel<R>   sweeps rows 1 .. q_end (score_local_end_kernel<R>'s sweep), writes ONE byte per cell into a
+//   align_local_hit_kernel<R>   sweeps rows 1 .. q_end (sweep_local, score_sweep.h), writes ONE byte per cell into a
 //                               transient strip of its own, walks back from the given end cell through that strip, writes
 //                               Optimal's pair list and counts the identities;
-//   ahit_list_kernel            lists a chunk's hits by template length class R = ceil(T / 256) (zhit_list_kernel over descriptors);
+//   class_list_kernel           (score_common.h) lists a chunk's hits by template length class R = ceil(T / 256);
 //   gapped_strings_kernel       (gapped_strings.hip, unchanged) lays the two lines of every list out.
 // No aln_batch, no planes, no find_max.  The strip byte of row i (2 .. q_end), column slot c:
 //   bits 0-1  the move INTO cell (i, c+1): 0 match, 1 deletion, 2 insertion — the reference tries match, deletions (k ascending),
@@ -42,22 +42,11 @@ struct HitDesc {            // one used slot the fused kernel takes, 32 bytes
   int64_t strip_off;        // first byte of the hit's strip: (q_end - 1) rows of 256 cls bytes
 };
 
-struct AClassOff { int off[9]; };
-
-// list[off[c] ..) = the chunk's hits of length class c, in no particular order (zhit_list_kernel over descriptors)
-__global__ __launch_bounds__(256) void ahit_list_kernel(const HitDesc* desc, int n, AClassOff co, int32_t* fill, int32_t* list) {
-  __shared__ int lc[9], lb[9];
-  const int tid = threadIdx.x;
-  const int h = blockIdx.x * 256 + tid;
-  if (tid < 9) lc[tid] = 0;
-  __syncthreads();
-  int cls = -1, my = 0;
-  if (h < n) { cls = desc[h].cls; my = atomicAdd(&lc[cls], 1); }
-  __syncthreads();
-  if (tid < 9 && lc[tid]) lb[tid] = co.off[tid] + atomicAdd(&fill[tid], lc[tid]);
-  __syncthreads();
-  if (cls >= 0) list[lb[cls] + my] = h;
-}
+// hit of the chunk -> its length class (class_list_kernel, score_common.h)
+struct DescClass {
+  const HitDesc* desc;
+  __device__ int operator()(int h) const { return desc[h].cls; }
+};
 
 struct AlignArgs {
   const int32_t* list;      // blockIdx.x -> hit of the chunk
@@ -67,6 +56,22 @@ struct AlignArgs {
   int trav_stride;
   PairResult* res;          // best = score, n_path, status (what gapped_strings_kernel reads)
   int32_t* same;            // identical aligned residues of the list (calcIdentity's count before its "- 2")
+};
+
+// sweep_local's observer: the strip byte of every cell (see the head of the file), one 32-bit store per lane and group
+struct StripObserver : NoObserver {
+  uint8_t* strip; int pitch;                    // row i (2 .. q_end) at strip + (i - 2) * pitch
+  uint32_t w = 0;
+  __device__ __forceinline__ void cell(int, int x, int m, int e, int f, int pv, int A, int gmx, int key) {
+    uint32_t b = (m >= max(e, f)) ? 0u : (e >= f ? 1u : 2u);
+    b |= (pv >= A) ? 4u : 0u;
+    b |= (gmx >= key) ? 8u : 0u;
+    b |= (m > 0) ? 16u : 0u;
+    w = (x == 0 ? 0u : w) | (b << (8 * x));
+  }
+  __device__ __forceinline__ void group(int i, int r) {       // the lane's four columns: 256 contiguous bytes per wave
+    (reinterpret_cast<uint32_t*>(strip + (size_t)(i - 2) * pitch) + threadIdx.x)[64 * r] = w;
+  }
 };
 
 template <int R>
@@ -81,124 +86,19 @@ __global__ __launch_bounds__(64) void align_local_hit_kernel(ScoreArgs a, AlignA
   const uint8_t* __restrict__ qc = a.qcodes + a.qoff[qi];
   const uint8_t* __restrict__ tc = a.tcodes + a.toff[ti];
   const int Q = (int)(a.qoff[qi + 1] - a.qoff[qi]), T = (int)(a.toff[ti + 1] - a.toff[ti]);
-  const int gi = a.gi, ge = a.ge;
-  const int cb = 4 * lane;
-  const int gime = gi - ge;
   constexpr int kPitch = 256 * R;
   uint8_t* strip = g.strip + hd.strip_off;      // row i (2 .. q_end) at strip + (i - 2) * kPitch
 
-  int code4[R][4], gec[R][4], ekc[R][4], inm[R][4];
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int x = 0; x < 4; ++x) {
-      const int c = cb + 256 * r + x;
-      int code = kCodeTail;
-      if (c < T) code = tc[c];
-      code4[r][x] = code * 4;
-      gec[r][x] = ge * c;
-      ekc[r][x] = ge * c + gime;
-      inm[r][x] = ((unsigned)(c - 1) < (unsigned)(T - 2)) ? -1 : 0;
-    }
-  int d[R][4], gmx[R][4], cv[R], ak[R][4];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    cv[r] = kNegS;
-#pragma unroll
-    for (int x = 0; x < 4; ++x) { d[r][x] = 0; gmx[r][x] = kNegS; }
-  }
-  auto tab_at = [&](int qrow, int c4) -> int {
-    return *reinterpret_cast<const int*>(reinterpret_cast<const char*>(tab) + qrow + c4);
-  };
-  auto finish_row = [&]() {
-    int sk = kNegS;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      int tk = kNegS;
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        int A = d[r][x] + gec[r][x];
-        if (r == 0 && x == 0) A = (lane == 0) ? kNegS : A;   // column 0 is never a source
-        ak[r][x] = A;
-        tk = max(tk, A);
-      }
-      const int ik = wave_incl_max_s(tk);
-      const int ek = sdpp<0x138>(kNegS, ik);
-      cv[r] = max(sk, ek);
-      sk = max(sk, __builtin_amdgcn_readlane(ik, 63));
-    }
-  };
-  {
-    const int qrow = (int)qc[1] * 128;           // row 1 (Q >= 3: the host sends other pairs elsewhere)
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        const int h = max(tab_at(qrow, code4[r][x]), 0);
-        d[r][x] = h & inm[r][x];
-      }
-    finish_row();
-  }
-  int qcode_next = (q_end >= 2) ? (int)qc[2] : 0;
-  for (int i = 2; i <= q_end; ++i) {                          // dpmatrix.h:607-649, rows below q_end are not needed
-    const int qrow = qcode_next * 128;
-    if (i + 1 <= q_end) qcode_next = (int)qc[i + 1];
-    const int roff = gi + ge * (i - 2);
-    const int rowB = ge * (i - 1);
-    uint32_t* srow = reinterpret_cast<uint32_t*>(strip + (size_t)(i - 2) * kPitch) + lane;
-    int bk[R][4];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      int pv = cv[r];
-      uint32_t w = 0;
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        const int m = d[r][x];
-        const int A = ak[r][x];
-        const int e = pv - ekc[r][x];
-        const int f = gmx[r][x] - roff;
-        const int key = m + rowB;
-        bk[r][x] = max(max(m, e), f);
-        uint32_t b = (m >= max(e, f)) ? 0u : (e >= f ? 1u : 2u);
-        b |= (pv >= A) ? 4u : 0u;
-        b |= (gmx[r][x] >= key) ? 8u : 0u;
-        b |= (m > 0) ? 16u : 0u;
-        w |= b << (8 * x);
-        pv = max(pv, A);
-        gmx[r][x] = max(gmx[r][x], key);
-      }
-      srow[64 * r] = w;                                       // the lane's four columns: 256 contiguous bytes per wave
-    }
-    int prev_k = 0;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      int uk = sdpp<0x138>(0, bk[r][3]);
-      if (r > 0) uk = (lane == 0) ? prev_k : uk;
-      prev_k = __builtin_amdgcn_readlane(bk[r][3], 63);
-      const bool masked = (r == 0) || (256 * (r + 1) > T - 1);
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        const int c = cb + 256 * r + x;
-        const int s = tab_at(qrow, code4[r][x]);
-        int h = max(((x == 0) ? uk : bk[r][x - 1]) + s, 0);
-        if (r == 0 && x == 1) h = (c == 1) ? max(s, 0) : h;  // column 1 (lane 0 only): free insertion from the origin
-        if (masked) h &= inm[r][x];                          // columns 0 and >= T-1 stay 0
-        d[r][x] = h;
-      }
-    }
-    finish_row();
-  }
+  // rows 1 .. q_end (1 <= q_end <= Q - 2: the host sends other pairs elsewhere); rows below q_end are not needed
+  LocalCols<R> cols;
+  cols.load(tc, T, a.gi, a.ge);
+  int d[R][4];
+  __builtin_assume(q_end >= 1);                 // row 1 always runs, as the host guarantees: no path around it to keep registers for
+  StripObserver bytes;
+  bytes.strip = strip; bytes.pitch = kPitch;
+  sweep_local<R>(tab, cols, qc, q_end, d, bytes);
   // D[q_end][t_end]: row q_end is in d[], column t_end in slot (rs, xs) of lane ls
-  int dend;
-  {
-    const int rs = t_end / 256, xs = t_end & 3, ls = (t_end & 255) >> 2;
-    int v = 0;
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-      for (int x = 0; x < 4; ++x) v = (r == rs && x == xs) ? d[r][x] : v;
-    dend = __shfl(v, ls);
-  }
+  const int dend = __shfl(sweep_pick<R>(d, t_end / 256, t_end & 3, 0), (t_end & 255) >> 2);
   PairResult res = {};
   res.best = (float)dend; res.corner = 0.f; res.best_q = q_end; res.best_t = t_end;
   if (!((float)dend == hd.score)) {                          // not the cell the slot's score stands in: refuse the slot
@@ -276,19 +176,6 @@ __global__ __launch_bounds__(64) void align_local_hit_kernel(ScoreArgs a, AlignA
 // The instantiations kept: every one compiles without scratch memory and without VGPR spills (DESIGN 4.8d has the table).
 // R = 8 (templates of 1793 .. 2048 columns) does not — 24 VGPRs spilled into AGPRs — so that class goes the batch route.
 constexpr unsigned kFusedClasses = 0x0FEu;                   // bit R set: class R runs in align_local_hit_kernel<R>
-
-static void launch_align_kernel(int r, int n, hipStream_t stream, const ScoreArgs& s, const AlignArgs& g) {
-  const dim3 grid(n), block(64);
-  switch (r) {
-    case 1: hipLaunchKernelGGL(align_local_hit_kernel<1>, grid, block, 0, stream, s, g); break;
-    case 2: hipLaunchKernelGGL(align_local_hit_kernel<2>, grid, block, 0, stream, s, g); break;
-    case 3: hipLaunchKernelGGL(align_local_hit_kernel<3>, grid, block, 0, stream, s, g); break;
-    case 4: hipLaunchKernelGGL(align_local_hit_kernel<4>, grid, block, 0, stream, s, g); break;
-    case 5: hipLaunchKernelGGL(align_local_hit_kernel<5>, grid, block, 0, stream, s, g); break;
-    case 6: hipLaunchKernelGGL(align_local_hit_kernel<6>, grid, block, 0, stream, s, g); break;
-    default: hipLaunchKernelGGL(align_local_hit_kernel<7>, grid, block, 0, stream, s, g); break;
-  }
-}
 
 // Where the results of one slot go, and how they are written (the same for both routes)
 struct AlignOut {
@@ -482,18 +369,21 @@ extern "C" int aln_hits_align(aln_ctx* ctx, const aln_seqs* queries, const aln_s
     }
     for (const Chunk& c : chunks) {
       const int n = (int)c.n;
-      AClassOff co = {};
+      ClassOff co = {};
       for (int k = 1; k < 9; ++k) co.off[k] = co.off[k - 1] + c.cls_cnt[k - 1];
       STRY(hipMemcpyAsync(ddesc, fast.data() + c.h0, (size_t)n * sizeof(HitDesc), hipMemcpyHostToDevice, ctx->stream));
       STRY(hipMemsetAsync(dfill, 0, 9 * 4, ctx->stream));
-      hipLaunchKernelGGL(ahit_list_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ddesc, n, co, dfill, dlist);
+      const DescClass dc = {ddesc};
+      hipLaunchKernelGGL(class_list_kernel<DescClass>, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, dc, n, co, dfill, dlist);
       STRY(hipGetLastError());
       AlignArgs g = {};
       g.desc = ddesc; g.strip = dstrip; g.trav = dtrav; g.trav_stride = c.trav_stride; g.res = dres; g.same = dsame;
       for (int k = 1; k <= 8; ++k) {
         if (c.cls_cnt[k] == 0) continue;
         g.list = dlist + co.off[k];
-        launch_align_kernel(k, c.cls_cnt[k], ctx->stream, run.a, g);
+        dispatch_r<7>(k, [&](auto rc) {                         // (class 8 never gets here: kFusedClasses)
+          hipLaunchKernelGGL(align_local_hit_kernel<decltype(rc)::value>, dim3(c.cls_cnt[k]), dim3(64), 0, ctx->stream, run.a, g);
+        });
         STRY(hipGetLastError());
       }
       if (want_lines) {

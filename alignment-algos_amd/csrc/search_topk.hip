@@ -4,8 +4,9 @@
 // and where their alignments end.  Here the score kernels of score_only.hip leave a slab of query rows' scores in a device
 // buffer (ScoreRun, score_common.h), and three kernels turn the slab into hits without the matrix ever reaching the host:
 //   topk_select_kernel         one workgroup per query row: the K largest 64-bit keys (score mapped to uint32, ~template index)
-//   hit_list_kernel            the hits of local searches, listed by template length class R = ceil(T / 256)
-//   score_local_end_kernel<R>  one wave per hit: score_local_kernel<R>'s row sweep + the cell Optimal::find_max returns
+//   class_list_kernel          (score_common.h) the hits of local searches, listed by template length class R = ceil(T / 256)
+//   score_local_end_kernel<R>  one wave per hit: the row sweep of score_local_kernel<R> (score_sweep.h), observed for the
+//                              cell Optimal::find_max returns
 // Only K x 16 B per query row travel to the host.  Pairs the register-resident kernels do not take (templates beyond 2048
 // columns, fractional values, the value-range test) are scored through full builds as in aln_score_all_vs_all, uploaded into
 // the slab before the selection, and the end cells of such hits come from one resident batch over just those hits.
@@ -119,26 +120,14 @@ __global__ __launch_bounds__(kSelThreads) void topk_select_kernel(SelectArgs a) 
   if (a.local && tid < 9 && ccnt[tid]) atomicAdd(&a.cls_cnt[tid], ccnt[tid]);
 }
 
-struct ClassOff { int off[9]; };
-
-// list[off[c] ..) = the slab's hit slots (row * K + k) whose template is of length class c, in no particular order
-__global__ __launch_bounds__(256) void hit_list_kernel(const aln_hit* hits, int n_slots, const int64_t* toff, int all_full,
-                                                       ClassOff co, int32_t* fill, int32_t* list) {
-  __shared__ int lc[9], lb[9];
-  const int tid = threadIdx.x;
-  const int h = blockIdx.x * 256 + tid;
-  if (tid < 9) lc[tid] = 0;
-  __syncthreads();
-  int cls = -1, my = 0;
-  if (h < n_slots) {
+// slot (row * K + k) -> the length class of its hit's template, -1 for a padding slot (class_list_kernel, score_common.h)
+struct HitClass {
+  const aln_hit* hits; const int64_t* toff; int all_full;
+  __device__ int operator()(int h) const {
     const int t = hits[h].t;
-    if (t >= 0) { cls = hit_class((int)(toff[t + 1] - toff[t]), all_full); my = atomicAdd(&lc[cls], 1); }
+    return t < 0 ? -1 : hit_class((int)(toff[t + 1] - toff[t]), all_full);
   }
-  __syncthreads();
-  if (tid < 9 && lc[tid]) lb[tid] = co.off[tid] + atomicAdd(&fill[tid], lc[tid]);
-  __syncthreads();
-  if (cls >= 0) list[lb[cls] + my] = h;
-}
+};
 
 // scores of the full-build route, computed on the host side as compact nr x n_cols, into their columns of the slab
 __global__ __launch_bounds__(256) void scatter_cols_kernel(float* slab, int n_t, const float* vals, const int32_t* cols, int n_cols,
@@ -148,12 +137,27 @@ __global__ __launch_bounds__(256) void scatter_cols_kernel(float* slab, int n_t,
 }
 
 // ---- the end cell of a local hit -------------------------------------------------------------------------------------
-// score_local_kernel<R>'s sweep for ONE hit slot per wave (blockIdx.x -> list -> (row, template)), which also keeps what
+// sweep_local (score_sweep.h) for ONE hit slot per wave (blockIdx.x -> list -> (row, template)), observed for what
 // Optimal::find_max (optimal.h:108-124) needs.  find_max seeds (Q-2, T-2) and replaces it only on a strictly greater score,
 // scanning rows, then columns, ascending: the seed wins every tie it takes part in, otherwise the first maximal cell in
-// row-major order does.  Per lane: the running maximum, the row at which it last strictly improved and — inside that rare
+// row-major order does.  Per lane: the row at which the running maximum last strictly improved and — inside that rare
 // branch — the smallest of the lane's columns holding it; the wave reduces by (value max, row min, column min); then the seed
 // exception: D[Q-2][T-2] is in the registers when the sweep ends.  A maximum of 0 (no positive cell, or no interior) is the seed's.
+struct FirstMaxObserver : NoObserver {
+  int seen = 0, lrow = 0, lcol = 0;
+  // the lane's maximum rose in row i exactly when row i's maximum exceeds the old one, and then equals it
+  template <int R>
+  __device__ __forceinline__ void row(int i, const int (&d)[R][4], int lane_max) {
+    if (lane_max > seen) {
+      seen = lane_max; lrow = i;
+#pragma unroll
+      for (int r = R - 1; r >= 0; --r)
+#pragma unroll
+        for (int x = 3; x >= 0; --x) lcol = (d[r][x] == lane_max) ? 4 * (int)threadIdx.x + 256 * r + x : lcol;
+    }
+  }
+};
+
 template <int R>
 __global__ __launch_bounds__(64) void score_local_end_kernel(ScoreArgs a, const int32_t* __restrict__ list, aln_hit* hits, int K) {
   __shared__ int tab[32 * 32];
@@ -165,153 +169,31 @@ __global__ __launch_bounds__(64) void score_local_end_kernel(ScoreArgs a, const 
   const uint8_t* __restrict__ qc = a.qcodes + a.qoff[qi];
   const uint8_t* __restrict__ tc = a.tcodes + a.toff[ti];
   const int Q = (int)(a.qoff[qi + 1] - a.qoff[qi]), T = (int)(a.toff[ti + 1] - a.toff[ti]);
-  const int gi = a.gi, ge = a.ge;
-  const int cb = 4 * lane;
-  const int gime = gi - ge;
-
-  int code4[R][4], gec[R][4], ekc[R][4], inm[R][4];
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int x = 0; x < 4; ++x) {
-      const int c = cb + 256 * r + x;
-      int code = kCodeTail;
-      if (c < T) code = tc[c];
-      code4[r][x] = code * 4;
-      gec[r][x] = ge * c;
-      ekc[r][x] = ge * c + gime;
-      inm[r][x] = ((unsigned)(c - 1) < (unsigned)(T - 2)) ? -1 : 0;
-    }
-  int d[R][4], gmx[R][4], cv[R], ak[R][4];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    cv[r] = kNegS;
-#pragma unroll
-    for (int x = 0; x < 4; ++x) { d[r][x] = 0; gmx[r][x] = kNegS; }
-  }
-  int lmax = 0, lrow = 0, lcol = 0;
-  auto tab_at = [&](int qrow, int c4) -> int {
-    return *reinterpret_cast<const int*>(reinterpret_cast<const char*>(tab) + qrow + c4);
-  };
-  // prefix-scan preparation on the row held in d[] (row i) + this lane's running maximum and where it first stood
-  auto finish_row = [&](int i) {
-    int sk = kNegS, rm = 0;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      int tk = kNegS;
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        int A = d[r][x] + gec[r][x];
-        if (r == 0 && x == 0) A = (lane == 0) ? kNegS : A;   // column 0 is never a source
-        ak[r][x] = A;
-        tk = max(tk, A);
-      }
-      rm = max(max(rm, d[r][0]), d[r][1]);
-      rm = max(max(rm, d[r][2]), d[r][3]);
-      const int ik = wave_incl_max_s(tk);
-      const int ek = sdpp<0x138>(kNegS, ik);
-      cv[r] = max(sk, ek);
-      sk = max(sk, __builtin_amdgcn_readlane(ik, 63));
-    }
-    if (rm > lmax) {
-      lmax = rm; lrow = i;
-#pragma unroll
-      for (int r = R - 1; r >= 0; --r)
-#pragma unroll
-        for (int x = 3; x >= 0; --x) lcol = (d[r][x] == rm) ? cb + 256 * r + x : lcol;
-    }
-  };
-  if (Q >= 3) {
-    const int qrow = (int)qc[1] * 128;
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        const int h = max(tab_at(qrow, code4[r][x]), 0);
-        d[r][x] = h & inm[r][x];
-      }
-    finish_row(1);
-  }
-  int qcode_next = (Q >= 4) ? (int)qc[2] : 0;
-  for (int i = 2; i <= Q - 2; ++i) {
-    const int qrow = qcode_next * 128;
-    if (i + 1 <= Q - 2) qcode_next = (int)qc[i + 1];
-    const int roff = gi + ge * (i - 2);
-    const int rowB = ge * (i - 1);
-    int bk[R][4];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      int pv = cv[r];
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        const int m = d[r][x];
-        const int A = ak[r][x];
-        const int e = pv - ekc[r][x];
-        const int f = gmx[r][x] - roff;
-        bk[r][x] = max(max(m, e), f);
-        pv = max(pv, A);
-        gmx[r][x] = max(gmx[r][x], m + rowB);
-      }
-    }
-    int prev_k = 0;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      int uk = sdpp<0x138>(0, bk[r][3]);
-      if (r > 0) uk = (lane == 0) ? prev_k : uk;
-      prev_k = __builtin_amdgcn_readlane(bk[r][3], 63);
-      const bool masked = (r == 0) || (256 * (r + 1) > T - 1);
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        const int c = cb + 256 * r + x;
-        const int s = tab_at(qrow, code4[r][x]);
-        int h = max(((x == 0) ? uk : bk[r][x - 1]) + s, 0);
-        if (r == 0 && x == 1) h = (c == 1) ? max(s, 0) : h;  // column 1 (lane 0 only): free insertion from the origin
-        if (masked) h &= inm[r][x];                          // columns 0 and >= T-1 stay 0
-        d[r][x] = h;
-      }
-    }
-    finish_row(i);
-  }
+  LocalCols<R> cols;
+  cols.load(tc, T, a.gi, a.ge);
+  int d[R][4];
+  FirstMaxObserver first;
+  const int lmax = sweep_local<R>(tab, cols, qc, Q - 2, d, first);
   // wave reduction: value max, then row min, then column min among the lanes that hold it
   int m = lmax;
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) m = max(m, __shfl_xor(m, o));
-  int br = (lmax == m) ? lrow : 0x7FFFFFFF;
+  int br = (lmax == m) ? first.lrow : 0x7FFFFFFF;
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) br = min(br, __shfl_xor(br, o));
-  int bc = (lmax == m && lrow == br) ? lcol : 0x7FFFFFFF;
+  int bc = (lmax == m && first.lrow == br) ? first.lcol : 0x7FFFFFFF;
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) bc = min(bc, __shfl_xor(bc, o));
   // the seed D[Q-2][T-2]: row Q-2 is in d[] (Q >= 3), column T-2 in slot (rs, xs) of lane ls (T >= 3)
   int seed = 0;
   if (m > 0) {
     const int cl = T - 2;
-    const int rs = cl / 256, xs = cl & 3, ls = (cl & 255) >> 2;
-    int v = 0;
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-      for (int x = 0; x < 4; ++x) v = (r == rs && x == xs) ? d[r][x] : v;
-    seed = __shfl(v, ls);
+    seed = __shfl(sweep_pick<R>(d, cl / 256, cl & 3, 0), (cl & 255) >> 2);
   }
   if (lane == 0) {
     const bool seed_wins = (m == 0) || (seed == m);
     hits[slot].q_end = seed_wins ? Q - 2 : br;
     hits[slot].t_end = seed_wins ? T - 2 : bc;
-  }
-}
-
-static void launch_end_kernel(int r, int n, hipStream_t stream, const ScoreArgs& s, const int32_t* list, aln_hit* hits, int K) {
-  const dim3 grid(n), block(64);
-  switch (r) {
-    case 1: hipLaunchKernelGGL(score_local_end_kernel<1>, grid, block, 0, stream, s, list, hits, K); break;
-    case 2: hipLaunchKernelGGL(score_local_end_kernel<2>, grid, block, 0, stream, s, list, hits, K); break;
-    case 3: hipLaunchKernelGGL(score_local_end_kernel<3>, grid, block, 0, stream, s, list, hits, K); break;
-    case 4: hipLaunchKernelGGL(score_local_end_kernel<4>, grid, block, 0, stream, s, list, hits, K); break;
-    case 5: hipLaunchKernelGGL(score_local_end_kernel<5>, grid, block, 0, stream, s, list, hits, K); break;
-    case 6: hipLaunchKernelGGL(score_local_end_kernel<6>, grid, block, 0, stream, s, list, hits, K); break;
-    case 7: hipLaunchKernelGGL(score_local_end_kernel<7>, grid, block, 0, stream, s, list, hits, K); break;
-    default: hipLaunchKernelGGL(score_local_end_kernel<8>, grid, block, 0, stream, s, list, hits, K); break;
   }
 }
 
@@ -445,8 +327,8 @@ extern "C" int aln_search_topk(aln_ctx* ctx, const aln_seqs* queries, const aln_
       STRY(hipStreamSynchronize(ctx->stream));
       for (int c = 1; c < 9; ++c) co.off[c] = co.off[c - 1] + cls_cnt[c - 1];
       const int n_slots = nr * K;
-      hipLaunchKernelGGL(hit_list_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, ctx->stream, dhits, n_slots, run.dto, (int)all_full,
-                         co, dcnt + 9, dlist);
+      const HitClass hc = {dhits, run.dto, (int)all_full};
+      hipLaunchKernelGGL(class_list_kernel<HitClass>, dim3((n_slots + 255) / 256), dim3(256), 0, ctx->stream, hc, n_slots, co, dcnt + 9, dlist);
       STRY(hipGetLastError());
     }
     if (debug) STRY(hipEventRecord(ev[2], ctx->stream));
@@ -456,7 +338,9 @@ extern "C" int aln_search_topk(aln_ctx* ctx, const aln_seqs* queries, const aln_
       s.q_begin = q_begin + r0;
       for (int c = 1; c <= 8; ++c) {
         if (cls_cnt[c] == 0) continue;
-        launch_end_kernel(c, cls_cnt[c], ctx->stream, s, dlist + co.off[c], dhits, K);
+        dispatch_r<8>(c, [&](auto rc) {
+          hipLaunchKernelGGL(score_local_end_kernel<decltype(rc)::value>, dim3(cls_cnt[c]), dim3(64), 0, ctx->stream, s, dlist + co.off[c], dhits, K);
+        });
         STRY(hipGetLastError());
         n_end += cls_cnt[c];
       }

@@ -4,12 +4,12 @@
 // with permutations of the query.  That is n_shuffles x (number of hits) score-only alignments — the work score_only.hip's
 // register-resident row sweep was built for — and nothing but two 64-bit sums per hit has to leave the device:
 //   shuffle_queries_kernel         one thread per (query row, shuffle): the permuted residue codes, sentinels in place
-//   zhit_list_kernel               the used hit slots listed by template length class R = ceil(T / 256) (search_topk.hip's
-//                                  hit_list_kernel over a plain array of template indices: any align type, any hit list)
+//   class_list_kernel              (score_common.h) the used hit slots listed by template length class R = ceil(T / 256), over
+//                                  a plain array of template indices: any align type, any hit list
 //   score_shuffled_kernel<R,LOCAL> one wave per (listed slot, group of shuffles): the template-side state of
-//                                  score_local_kernel<R> / score_global_kernel<R> is built ONCE, then the row sweep runs once
-//                                  per shuffle of the group; score and score^2 are summed in 64 bits and leave the wave as two
-//                                  atomic adds (integer addition: the result does not depend on the order)
+//                                  score_local_kernel<R> / score_global_kernel<R> is built ONCE, then the row sweep
+//                                  (score_sweep.h) runs once per shuffle of the group; score and score^2 are summed in 64 bits
+//                                  and leave the wave as two atomic adds (integer addition: the result does not depend on the order)
 // Query rows are handled a chunk at a time so that the shuffled strings and the accumulators stay below 1 GiB each.  Hits on
 // templates beyond 2048 columns go the way they go in aln_score_all_vs_all: the host materialises the same permutations (its
 // own statement of the rule) and score_through_batches scores them through full builds.
@@ -61,31 +61,17 @@ __global__ __launch_bounds__(256) void shuffle_queries_kernel(ShuffleArgs a) {
   }
 }
 
-struct ZClassOff { int off[9]; };
-
-// list[off[c] ..) = the chunk's used slots (row * K + k, slot_t >= 0) whose template is of length class c = ceil(T / 256),
-// c = 0: beyond 2048 columns (scored on the host side); in no particular order
-__global__ __launch_bounds__(256) void zhit_list_kernel(const int32_t* slot_t, int n_slots, const int64_t* toff, ZClassOff co,
-                                                        int32_t* fill, int32_t* list) {
-  __shared__ int lc[9], lb[9];
-  const int tid = threadIdx.x;
-  const int h = blockIdx.x * 256 + tid;
-  if (tid < 9) lc[tid] = 0;
-  __syncthreads();
-  int cls = -1, my = 0;
-  if (h < n_slots) {
+// slot (row * K + k) -> the length class of its template, 0: beyond 2048 columns (scored on the host side), -1: unused slot
+// (class_list_kernel, score_common.h)
+struct SlotClass {
+  const int32_t* slot_t; const int64_t* toff;
+  __device__ int operator()(int h) const {
     const int t = slot_t[h];
-    if (t >= 0) {
-      const int T = (int)(toff[t + 1] - toff[t]);
-      cls = T > 2048 ? 0 : (T + 255) / 256;
-      my = atomicAdd(&lc[cls], 1);
-    }
+    if (t < 0) return -1;
+    const int T = (int)(toff[t + 1] - toff[t]);
+    return T > 2048 ? 0 : (T + 255) / 256;
   }
-  __syncthreads();
-  if (tid < 9 && lc[tid]) lb[tid] = co.off[tid] + atomicAdd(&fill[tid], lc[tid]);
-  __syncthreads();
-  if (cls >= 0) list[lb[cls] + my] = h;
-}
+};
 
 struct ZScoreArgs {
   ScoreArgs a;                                  // a.q_begin: query index of the chunk's row 0; a.qcodes is not read
@@ -97,262 +83,8 @@ struct ZScoreArgs {
   int free_del, free_ins;
 };
 
-// score_local_kernel<R>'s sweep (score_only.hip), the template-side registers built once, the row state reset per shuffle
-template <int R>
-__device__ __forceinline__ void shuffled_local(const ZScoreArgs& z, const int* tab, const uint8_t* __restrict__ q0, int Q,
-                                               const uint8_t* __restrict__ tc, int T, int n_s, long long& sum, long long& sumsq) {
-  const int lane = threadIdx.x;
-  const int gi = z.a.gi, ge = z.a.ge;
-  const int cb = 4 * lane;
-  const int gime = gi - ge;
-  int code4[R][4], gec[R][4], ekc[R][4], inm[R][4];
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int x = 0; x < 4; ++x) {
-      const int c = cb + 256 * r + x;
-      int code = kCodeTail;
-      if (c < T) code = tc[c];
-      code4[r][x] = code * 4;
-      gec[r][x] = ge * c;
-      ekc[r][x] = ge * c + gime;
-      inm[r][x] = ((unsigned)(c - 1) < (unsigned)(T - 2)) ? -1 : 0;
-    }
-  auto tab_at = [&](int qrow, int c4) -> int {
-    return *reinterpret_cast<const int*>(reinterpret_cast<const char*>(tab) + qrow + c4);
-  };
-  for (int s = 0; s < n_s; ++s) {
-    const uint8_t* __restrict__ qc = q0 + (size_t)s * Q;
-    int d[R][4], gmx[R][4], cv[R], ak[R][4];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      cv[r] = kNegS;
-#pragma unroll
-      for (int x = 0; x < 4; ++x) { d[r][x] = 0; gmx[r][x] = kNegS; ak[r][x] = kNegS; }
-    }
-    int lmax = 0;
-    auto finish_row = [&]() {
-      int sk = kNegS;
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        int tk = kNegS;
-#pragma unroll
-        for (int x = 0; x < 4; ++x) {
-          int A = d[r][x] + gec[r][x];
-          if (r == 0 && x == 0) A = (lane == 0) ? kNegS : A;   // column 0 is never a source
-          ak[r][x] = A;
-          tk = max(tk, A);
-        }
-        lmax = max(max(lmax, d[r][0]), d[r][1]);
-        lmax = max(max(lmax, d[r][2]), d[r][3]);
-        const int ik = wave_incl_max_s(tk);
-        const int ek = sdpp<0x138>(kNegS, ik);
-        cv[r] = max(sk, ek);
-        sk = max(sk, __builtin_amdgcn_readlane(ik, 63));
-      }
-    };
-    if (Q >= 3) {
-      const int qrow = (int)qc[1] * 128;
-#pragma unroll
-      for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int x = 0; x < 4; ++x) {
-          const int h = max(tab_at(qrow, code4[r][x]), 0);
-          d[r][x] = h & inm[r][x];
-        }
-      finish_row();
-    }
-    int qcode_next = (Q >= 4) ? (int)qc[2] : 0;
-    for (int i = 2; i <= Q - 2; ++i) {
-      const int qrow = qcode_next * 128;
-      if (i + 1 <= Q - 2) qcode_next = (int)qc[i + 1];
-      const int roff = gi + ge * (i - 2);
-      const int rowB = ge * (i - 1);
-      int bk[R][4];
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        int pv = cv[r];
-#pragma unroll
-        for (int x = 0; x < 4; ++x) {
-          const int m = d[r][x];
-          const int A = ak[r][x];
-          const int e = pv - ekc[r][x];
-          const int f = gmx[r][x] - roff;
-          bk[r][x] = max(max(m, e), f);
-          pv = max(pv, A);
-          gmx[r][x] = max(gmx[r][x], m + rowB);
-        }
-      }
-      int prev_k = 0;
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        int uk = sdpp<0x138>(0, bk[r][3]);
-        if (r > 0) uk = (lane == 0) ? prev_k : uk;
-        prev_k = __builtin_amdgcn_readlane(bk[r][3], 63);
-        const bool masked = (r == 0) || (256 * (r + 1) > T - 1);
-#pragma unroll
-        for (int x = 0; x < 4; ++x) {
-          const int c = cb + 256 * r + x;
-          const int sv = tab_at(qrow, code4[r][x]);
-          int h = max(((x == 0) ? uk : bk[r][x - 1]) + sv, 0);
-          if (r == 0 && x == 1) h = (c == 1) ? max(sv, 0) : h;   // column 1 (lane 0 only): free insertion from the origin
-          if (masked) h &= inm[r][x];                            // columns 0 and >= T-1 stay 0
-          d[r][x] = h;
-        }
-      }
-      finish_row();
-    }
-    int m = lmax;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) m = max(m, __shfl_xor(m, o));
-    sum += m; sumsq += (long long)m * m;
-  }
-}
-
-// score_global_kernel<R>'s sweep (score_only.hip) in the same arrangement; the caller has dealt with Q == 2 and T == 2
-template <int R>
-__device__ __forceinline__ void shuffled_global(const ZScoreArgs& z, const int* tab, const uint8_t* __restrict__ q0, int Q,
-                                                const uint8_t* __restrict__ tc, int T, int n_s, long long& sum, long long& sumsq) {
-  const int lane = threadIdx.x;
-  const int gi = z.a.gi, ge = z.a.ge;
-  const int free_del = z.free_del, free_ins = z.free_ins;
-  const int cb = 4 * lane;
-  const int gime = gi - ge;
-  const int cl = T - 2;                                            // last interior column; its (wave-uniform) slot and lane
-  const int rs = cl / 256, xs = cl & 3, ls = (cl & 255) >> 2;
-  int code4[R][4], gec[R][4], ekc[R][4]; bool in[R][4];
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int x = 0; x < 4; ++x) {
-      const int c = cb + 256 * r + x;
-      int code = kCodeTail;
-      if (c < T) code = tc[c];
-      code4[r][x] = code * 4;
-      gec[r][x] = ge * c;
-      ekc[r][x] = ge * c + gime;
-      in[r][x] = (unsigned)(c - 1) < (unsigned)(T - 2);
-    }
-  auto tab_at = [&](int qrow, int c4) -> int {
-    return *reinterpret_cast<const int*>(reinterpret_cast<const char*>(tab) + qrow + c4);
-  };
-  auto pick = [&](const int (&v)[R][4]) -> int {                   // this lane's value in slot (rs, xs)
-    int o = kNegS;
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-      for (int x = 0; x < 4; ++x) o = (r == rs && x == xs) ? v[r][x] : o;
-    return o;
-  };
-  for (int s = 0; s < n_s; ++s) {
-    const uint8_t* __restrict__ qc = q0 + (size_t)s * Q;
-    int d[R][4], gmx[R][4], cv[R], ak[R][4];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      cv[r] = kNegS;
-#pragma unroll
-      for (int x = 0; x < 4; ++x) { d[r][x] = kNegS; gmx[r][x] = kNegS; ak[r][x] = kNegS; }
-    }
-    int clast = kNegS;                                             // max over rows of D[k][T-2] (free insertions into the final cell)
-    auto finish_row = [&]() {
-      int sk = kNegS;
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        int tk = kNegS;
-#pragma unroll
-        for (int x = 0; x < 4; ++x) {
-          const int A = d[r][x] + gec[r][x];                       // non-interior cells hold "minus infinity": never a source
-          ak[r][x] = A;
-          tk = max(tk, A);
-        }
-        const int ik = wave_incl_max_s(tk);
-        const int ek = sdpp<0x138>(kNegS, ik);
-        cv[r] = max(sk, ek);
-        sk = max(sk, __builtin_amdgcn_readlane(ik, 63));
-      }
-      const int v = pick(d);
-      clast = max(clast, lane == ls ? v : kNegS);
-    };
-    {
-      // row 1: one deletion from the origin, free if the template's head gap is
-      const int qrow = (int)qc[1] * 128;
-#pragma unroll
-      for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int x = 0; x < 4; ++x) {
-          const int c = cb + 256 * r + x;
-          const int cost = (c >= 2 && !free_del) ? gi + ge * (c - 2) : 0;
-          d[r][x] = in[r][x] ? tab_at(qrow, code4[r][x]) - cost : kNegS;
-        }
-      finish_row();
-    }
-    int qcode_next = (Q >= 4) ? (int)qc[2] : 0;
-    for (int i = 2; i <= Q - 2; ++i) {
-      const int qrow = qcode_next * 128;
-      if (i + 1 <= Q - 2) qcode_next = (int)qc[i + 1];
-      const int roff = gi + ge * (i - 2);
-      const int rowB = ge * (i - 1);
-      const int col1 = free_ins ? 0 : roff;                        // column 1: one insertion from the origin
-      int bk[R][4];
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        int pv = cv[r];
-#pragma unroll
-        for (int x = 0; x < 4; ++x) {
-          const int m = d[r][x];
-          const int A = ak[r][x];
-          const int e = pv - ekc[r][x];
-          const int f = gmx[r][x] - roff;
-          bk[r][x] = max(max(m, e), f);
-          pv = max(pv, A);
-          gmx[r][x] = max(gmx[r][x], m + rowB);
-        }
-      }
-      int prev_k = 0;
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        int uk = sdpp<0x138>(0, bk[r][3]);
-        if (r > 0) uk = (lane == 0) ? prev_k : uk;
-        prev_k = __builtin_amdgcn_readlane(bk[r][3], 63);
-#pragma unroll
-        for (int x = 0; x < 4; ++x) {
-          const int c = cb + 256 * r + x;
-          const int sv = tab_at(qrow, code4[r][x]);
-          int h = ((x == 0) ? uk : bk[r][x - 1]) + sv;
-          if (r == 0 && x == 1) h = (c == 1) ? sv - col1 : h;
-          d[r][x] = in[r][x] ? h : kNegS;
-        }
-      }
-      finish_row();
-    }
-    // the final cell: row Q-2 is in d[], gmx holds rows <= Q-3, clast every row of column T-2
-    int best = (lane == ls) ? pick(d) : kNegS;
-    {
-      int dl = kNegS;                                              // deletion from (Q-2, k), k = 1 .. T-2 (k = T-2 costs nothing)
-#pragma unroll
-      for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int x = 0; x < 4; ++x) {
-          const int c = cb + 256 * r + x;
-          const int len = T - 2 - c;
-          const int cost = (len < 1 || free_del) ? 0 : gi + ge * (len - 1);
-          dl = max(dl, in[r][x] ? d[r][x] - cost : kNegS);
-        }
-      best = max(best, dl);
-      int il;                                                      // insertion from (k, T-2), k = 1 .. Q-2
-      if (free_ins) il = clast;
-      else {
-        const int g = pick(gmx);                                   // max over k <= Q-3 of D[k][T-2] + ge k
-        il = (lane == ls && Q >= 4) ? g - (gi + ge * (Q - 3)) : kNegS;
-      }
-      best = max(best, il);
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) best = max(best, __shfl_xor(best, o));
-    sum += best; sumsq += (long long)best * best;
-  }
-}
-
+// The template-side state of score_local_kernel<R> / score_global_kernel<R> (score_sweep.h) is built once, the sweep runs once
+// per shuffle of the group.
 template <int R, bool LOCAL>
 __global__ __launch_bounds__(64) void score_shuffled_kernel(ZScoreArgs z) {
   __shared__ int tab[32 * 32];
@@ -366,32 +98,32 @@ __global__ __launch_bounds__(64) void score_shuffled_kernel(ZScoreArgs z) {
   const uint8_t* __restrict__ q0 = z.pool + z.poff[row] + (int64_t)s0 * Q;
   const uint8_t* __restrict__ tc = z.a.tcodes + z.a.toff[ti];
   long long sum = 0, sumsq = 0;
-  if constexpr (LOCAL) shuffled_local<R>(z, tab, q0, Q, tc, T, n_s, sum, sumsq);
-  else if (Q == 2 || T == 2) {
+  auto add = [&](int m) {                                      // one shuffle's score, reduced over the wave
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) m = max(m, __shfl_xor(m, o));
+    sum += m; sumsq += (long long)m * m;
+  };
+  if constexpr (LOCAL) {
+    LocalCols<R> cols;
+    cols.load(tc, T, z.a.gi, z.a.ge);
+    for (int s = 0; s < n_s; ++s) {
+      int d[R][4];
+      add(sweep_local<R>(tab, cols, q0 + (size_t)s * Q, Q - 2, d, NoObserver()));
+    }
+  } else if (Q == 2 || T == 2) {
     // degenerate shortcuts of score_global_kernel: one gap from the origin, the same for every shuffle
     int cost = 0;
     if (Q == 2) { const int len = T - 2; cost = (len < 1 || z.free_del) ? 0 : z.a.gi + z.a.ge * (len - 1); }
     else { const int len = Q - 2; cost = (len < 1 || z.free_ins) ? 0 : z.a.gi + z.a.ge * (len - 1); }
     sum = -(long long)cost * n_s; sumsq = (long long)cost * cost * n_s;
-  } else shuffled_global<R>(z, tab, q0, Q, tc, T, n_s, sum, sumsq);
+  } else {
+    GlobalCols<R> cols;
+    cols.load(tc, T, z.a.gi, z.a.ge);
+    for (int s = 0; s < n_s; ++s) add(sweep_global<R>(tab, cols, q0 + (size_t)s * Q, Q, z.free_del, z.free_ins));
+  }
   if (lane == 0) {
     atomicAdd(&z.acc[2 * (size_t)slot], (unsigned long long)sum);
     atomicAdd(&z.acc[2 * (size_t)slot + 1], (unsigned long long)sumsq);
-  }
-}
-
-template <bool LOCAL>
-static void launch_shuffled(int r, dim3 grid, hipStream_t stream, const ZScoreArgs& z) {
-  const dim3 block(64);
-  switch (r) {
-    case 1: hipLaunchKernelGGL((score_shuffled_kernel<1, LOCAL>), grid, block, 0, stream, z); break;
-    case 2: hipLaunchKernelGGL((score_shuffled_kernel<2, LOCAL>), grid, block, 0, stream, z); break;
-    case 3: hipLaunchKernelGGL((score_shuffled_kernel<3, LOCAL>), grid, block, 0, stream, z); break;
-    case 4: hipLaunchKernelGGL((score_shuffled_kernel<4, LOCAL>), grid, block, 0, stream, z); break;
-    case 5: hipLaunchKernelGGL((score_shuffled_kernel<5, LOCAL>), grid, block, 0, stream, z); break;
-    case 6: hipLaunchKernelGGL((score_shuffled_kernel<6, LOCAL>), grid, block, 0, stream, z); break;
-    case 7: hipLaunchKernelGGL((score_shuffled_kernel<7, LOCAL>), grid, block, 0, stream, z); break;
-    default: hipLaunchKernelGGL((score_shuffled_kernel<8, LOCAL>), grid, block, 0, stream, z); break;
   }
 }
 
@@ -519,7 +251,7 @@ extern "C" int aln_hits_zscores(aln_ctx* ctx, const aln_seqs* queries, const aln
       }
     }
     int n_used = 0;
-    ZClassOff co = {};
+    ClassOff co = {};
     for (int k = 0; k < 9; ++k) { if (k) co.off[k] = co.off[k - 1] + cls_cnt[k - 1]; n_used += cls_cnt[k]; }
     if (n_used > cls_cnt[0]) {
       STRY(hipMemcpyAsync(dpoff, poff.data(), (size_t)(nr + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -531,7 +263,8 @@ extern "C" int aln_hits_zscores(aln_ctx* ctx, const aln_seqs* queries, const aln
       const long long n_str = (long long)nr * S;
       hipLaunchKernelGGL(shuffle_queries_kernel, dim3((unsigned)((n_str + 255) / 256)), dim3(256), 0, ctx->stream, sh);
       STRY(hipGetLastError());
-      hipLaunchKernelGGL(zhit_list_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, ctx->stream, dslot, n_slots, run.dto, co, dfill, dlist);
+      const SlotClass sc = {dslot, run.dto};
+      hipLaunchKernelGGL(class_list_kernel<SlotClass>, dim3((n_slots + 255) / 256), dim3(256), 0, ctx->stream, sc, n_slots, co, dfill, dlist);
       STRY(hipGetLastError());
       ZScoreArgs z = {};
       z.a = run.a; z.a.q_begin = q_begin + r0;
@@ -541,8 +274,11 @@ extern "C" int aln_hits_zscores(aln_ctx* ctx, const aln_seqs* queries, const aln
         if (cls_cnt[k] == 0) continue;
         z.list = dlist + co.off[k];
         const dim3 grid(cls_cnt[k], n_groups);
-        if (run.local) launch_shuffled<true>(k, grid, ctx->stream, z);
-        else launch_shuffled<false>(k, grid, ctx->stream, z);
+        dispatch_r<8>(k, [&](auto rc) {
+          constexpr int R = decltype(rc)::value;
+          if (run.local) hipLaunchKernelGGL((score_shuffled_kernel<R, true>), grid, dim3(64), 0, ctx->stream, z);
+          else hipLaunchKernelGGL((score_shuffled_kernel<R, false>), grid, dim3(64), 0, ctx->stream, z);
+        });
         STRY(hipGetLastError());
       }
       STRY(hipMemcpyAsync(acc.data(), dacc, (size_t)n_slots * 16, hipMemcpyDeviceToHost, ctx->stream));

@@ -83,6 +83,31 @@ def test_non_local_scores_equal_plane_path_and_oracle(mode, blosum62):
     assert np.array_equal(blk, full[3:8])
 
 
+def test_scores_at_the_widest_template_classes(blosum62):
+    """Templates of 1536 / 1537 / 1791 / 1792 / 1793 / 2047 / 2048 columns (sentinels included): the class 6|7 and 7|8
+    boundaries and the last column the register-resident kernels take, so score_local_kernel<7,8>, score_local_pk_kernel<7,8>
+    and score_global_kernel<7,8> run.  A copy of the 90-residue query ends the 2046-residue template: the maximum and the
+    final cell's match sit in the last column group.  Bit for bit against the resident-plane path, gaps 11/1 and 3/0."""
+    alpha, table = blosum62
+    qs = make_set(87000, [0, 1, 2, 30, 90])
+    ts = make_set(88000, [1534, 1535, 1789, 1790, 1791, 2045, 2046])
+    ts[6] = ts[6][:2046 - 90] + qs[4]
+    ctx = gpu_util.ctx()
+    qi, ti = np.meshgrid(np.arange(len(qs)), np.arange(len(ts)), indexing="ij")
+    for gi, ge in ((11, 1), (3, 0)):
+        for mode in (aln_amd.LOCAL, 0, 1, 2, 4):
+            b = aln_amd.Batch(ctx, qs, ts, qi.reshape(-1), ti.reshape(-1))
+            b.dp_submatrix(alpha, table, mode, gi, ge)
+            want = (b.optimal(want_pairs=False)[0] if mode == aln_amd.LOCAL else b.corner_scores()).reshape(len(qs), len(ts))
+            b.close()
+            if mode == aln_amd.LOCAL:
+                assert want[4, 6] >= 90 * 4                                 # the planted copy (BLOSUM62's diagonal is >= 4)
+            for packed in ((1, 0) if mode == aln_amd.LOCAL else (1,)):     # only local scores have a packed kernel
+                with ctx.hints(score_packed=packed):
+                    got = aln_amd.score_all_vs_all(ctx, qs, ts, alpha, table, gi, ge, align_type=mode)
+                assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (mode, gi, packed, np.argwhere(got != want)[:5])
+
+
 def test_score_only_rejects_what_it_cannot_do(blosum62):
     alpha, table = blosum62
     ctx = gpu_util.ctx()
