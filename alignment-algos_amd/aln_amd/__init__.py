@@ -90,7 +90,7 @@ EXPORTS = [
     "aln_batch_optimal_strings", "aln_batch_optimal_strings_enqueue", "aln_batch_optimal_strings_collect", "aln_batch_last_exact_stats", "aln_batch_set_gap", "aln_ctx_set_hint", "aln_ctx_get_hint", "aln_batch_dp_contract_bytes", "aln_batch_plane_bytes_per_cell",
     "aln_deal_units", "aln_comm_unique_id", "aln_comm_create", "aln_ctx_create_multi", "aln_comm_destroy", "aln_comm_n_ranks",
     "aln_comm_last_error", "aln_gather_scores", "aln_gather_resident_enqueue", "aln_gather_resident_collect", "aln_search_topk",
-    "aln_hits_zscores", "aln_hits_align",
+    "aln_hits_zscores", "aln_hits_align", "aln_hits_align_last_routes",
 ]
 COMM_ID_BYTES = 128
 
@@ -162,6 +162,7 @@ def lib():
         L.aln_hits_align.argtypes = [C.c_void_p, C.POINTER(AlnSeqs), C.POINTER(AlnSeqs), C.POINTER(AlnSubmatrix), C.POINTER(AlnGap),
                                      C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.POINTER(AlnHitAlignment), _ip, C.c_int32,
                                      C.c_char_p, C.c_char_p, C.c_int32, _ip]
+        L.aln_hits_align_last_routes.argtypes = [C.c_void_p, _lp]
         L.aln_hmap2_gap_arrays.argtypes = [_fp, C.c_int64, C.c_float, C.c_float, C.c_float, _fp, _fp]
         L.aln_batch_plane_bytes_per_cell.argtypes = [C.c_void_p]
         L.aln_batch_optimal_strings.argtypes = [C.c_void_p, _fp, _fp, _ip, C.c_char_p, C.c_char_p, C.c_int32, _ip]
@@ -392,6 +393,14 @@ def hits_align(ctx, queries, templates, hits, n_hits, alphabet, table, gi, ge, q
                     for r in range(rows)]
         tlines, qlines = cut(tl), cut(ql)
     return rec, lists, tlines, qlines, lengths, rc
+
+
+def hits_align_routes(ctx):
+    """aln_hits_align_last_routes: the used slots the context's last hits_align call sent through a fused kernel and through
+    resident batches -> (fused, batched); (0, 0) before any call."""
+    out = np.zeros(2, dtype=np.int64)
+    _check(lib().aln_hits_align_last_routes(ctx.h, out.ctypes.data_as(_lp)), ctx.h)
+    return int(out[0]), int(out[1])
 
 
 def align_hits(ctx, queries, templates, hits, n_hits, alphabet, table, gi, ge, q_begin=0, align_type=LOCAL):

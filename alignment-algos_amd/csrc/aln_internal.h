@@ -101,6 +101,7 @@ struct aln_hints {
   int search_debug = 0;      // 1: aln_search_topk reports its slabs and the device time of scoring / selection / end cells on stderr
   int zscore_chunk_rows = 0; // aln_hits_zscores: query rows whose shuffled strings are resident at a time; 0 = by the 1 GiB budget
   int align_chunk_hits = 0;  // aln_hits_align: hit slots whose strips are resident at a time; 0 = by the 1 GiB budget (never lifts it)
+  int align_fused_nonlocal = 1;   // 0: aln_hits_align sends hits of the four non-local align types through resident batches
   int plane_row_align = 8;   // cells a plane row is padded to when a batch is created (8, 16, 32 or 64)
   int64_t enum_node_cap = 0; // trie nodes of aln_batch_enumerate (0 = default)
   int enum_keep_pools = 1;   // 1: aln_batch_enumerate_all keeps its device pools with the batch (freed with it); 0: frees them when it returns
@@ -119,6 +120,7 @@ struct aln_ctx {
   hipStream_t copy_stream = nullptr;   // device -> host copies that must not hold up the launch stream (created on first use)
   std::string last_error;
   aln_hints hints;
+  int64_t align_routes[2] = {0, 0};    // used slots the last aln_hits_align sent through a fused kernel / through batches
 };
 
 struct aln_batch {

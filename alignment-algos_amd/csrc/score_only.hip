@@ -64,7 +64,7 @@ __global__ __launch_bounds__(64) void score_global_kernel(ScoreArgs a, int free_
   }
   GlobalCols<R> cols;
   cols.load(tc, T, gi, ge);
-  int best = sweep_global<R>(tab, cols, qc, Q, free_del, free_ins);
+  int best = sweep_global<R>(tab, cols, qc, Q, free_del, free_ins, NoObserver());
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) best = max(best, __shfl_xor(best, o));
   if (lane == 0) *out = (float)best;

@@ -8,7 +8,7 @@
 //   GlobalCols<R> + sweep_global  the four non-local align types: no clip, "minus infinity" outside the interior,
 //                                 end gaps priced per align type, the final cell included                      (dpmatrix.h:375-534)
 // Users: score_only.hip (scores), search_topk.hip (end cells), search_zscore.hip (one sweep per shuffle), search_align.hip
-// (five bits per cell into a strip).  What a user sees of the local sweep beyond its result goes through an observer; the
+// (four or five bits per cell into a strip).  What a user sees of a sweep beyond its result goes through an observer; the
 // packed 16-bit kernel of score_only.hip has its own types and its own sweep.
 #pragma once
 #include "aln_internal.h"
@@ -37,7 +37,7 @@ __device__ __forceinline__ int sweep_tab_at(const int* tab, int qrow, int c4) {
   return *reinterpret_cast<const int*>(reinterpret_cast<const char*>(tab) + qrow + c4);
 }
 
-// What a user of sweep_local may watch.  The default watches nothing and compiles to nothing.
+// What a user of sweep_local or sweep_global may watch.  The default watches nothing and compiles to nothing.
 struct NoObserver {
   // cell(r, x, m, e, f, pv, A, gmx, key): a cell (group r, slot x) of row i-1 while row i is computed.  m, e, f are the three
   // maxima row i's cell to its right chooses from; pv >= A says an earlier column of row i-1 holds at least this cell's deletion
@@ -45,9 +45,13 @@ struct NoObserver {
   // of the group are through.
   __device__ __forceinline__ void cell(int, int, int, int, int, int, int, int, int) {}
   __device__ __forceinline__ void group(int, int) {}
-  // row(i, d, lane_max): row i is in d[]; lane_max is the lane's maximum over rows 1 .. i
+  // row(i, d, lane_max): row i is in d[]; lane_max is the lane's maximum over rows 1 .. i (sweep_global: over rows 1 .. i of
+  // column T-2, in the lane that owns it)
   template <int R>
   __device__ __forceinline__ void row(int, const int (&)[R][4], int) {}
+  // last(d), sweep_global only: the last row, Q-2, is in d[] and the final cell is next
+  template <int R>
+  __device__ __forceinline__ void last(const int (&)[R][4]) {}
 };
 
 // ---- local -------------------------------------------------------------------------------------------------------------------
@@ -216,10 +220,12 @@ struct GlobalCols {
 };
 
 // Rows 1 .. Q-2 and the final cell (Q >= 3 and T >= 3: the callers deal with the degenerate shapes).  Returns the lane's
-// candidate for the final cell's score; the maximum over the wave is the score.
-template <int R>
+// candidate for the final cell's score; the maximum over the wave is the score.  Both inner loops stay in this function, as in
+// sweep_local; the row array stays in it too, and an observer sees the last row through last(): handing d[] out by reference
+// moved the registers of score_global_kernel and score_shuffled_kernel.
+template <int R, class Obs>
 __device__ __forceinline__ int sweep_global(const int* tab, const GlobalCols<R>& k, const uint8_t* qc, int Q,
-                                            int free_del, int free_ins) {
+                                            int free_del, int free_ins, Obs&& obs) {
   const int lane = threadIdx.x;
   const int cb = 4 * lane;
   const int gi = k.gi, ge = k.ge, T = k.T, ls = k.ls;
@@ -262,6 +268,7 @@ __device__ __forceinline__ int sweep_global(const int* tab, const GlobalCols<R>&
         d[r][x] = k.in[r][x] ? sweep_tab_at(tab, qrow, k.code4[r][x]) - cost : kNegS;
       }
     finish_row();
+    obs.row(1, d, clast);
   }
   int qcode_next = (Q >= 4) ? (int)qc[2] : 0;
   for (int i = 2; i <= Q - 2; ++i) {                               // dpmatrix.h:447-486
@@ -281,9 +288,11 @@ __device__ __forceinline__ int sweep_global(const int* tab, const GlobalCols<R>&
         const int e = pv - k.ekc[r][x];
         const int f = gmx[r][x] - roff;
         bk[r][x] = max(max(m, e), f);
+        obs.cell(r, x, m, e, f, pv, A, gmx[r][x], m + rowB);
         pv = max(pv, A);
         gmx[r][x] = max(gmx[r][x], m + rowB);
       }
+      obs.group(i, r);
     }
     int prev_k = 0;
 #pragma unroll
@@ -301,8 +310,10 @@ __device__ __forceinline__ int sweep_global(const int* tab, const GlobalCols<R>&
       }
     }
     finish_row();
+    obs.row(i, d, clast);
   }
   // ---- the final cell (dpmatrix.h:505-534): row Q-2 is in d[], gmx holds rows <= Q-3, clast every row of column T-2 -----
+  obs.last(d);
   int best = (lane == ls) ? sweep_pick<R>(d, k.rs, k.xs, kNegS) : kNegS;   // match: D[Q-2][T-2] (the final cell's similarity is 0)
   int dl = kNegS;                                                  // deletion from (Q-2, k), k = 1 .. T-2 (k = T-2 costs nothing)
 #pragma unroll

@@ -21,8 +21,13 @@
 //   bit 4     D[i-1][c] > 0: Optimal's local walk stops BEFORE a cell whose score is <= 0 (optimal.h:100).
 // Bits 2-4 of row i describe row i-1, whose values the sweep holds while it computes row i: the last row the walk needs them
 // for is q_end - 1.  Rows 1 and columns 1 need no move: their cells point at the origin (dpmatrix.h:579-599).
-// Everything the kernel does not take — the four non-local align types, templates beyond 2048 columns, scoring systems ScoreRun
-// sends through full builds, pairs without an interior — goes through resident batches inside the call.
+//   align_global_hit_kernel<R>  the same for the four non-local align types (sweep_global): every row 1 .. Q-2 is swept, since
+//                               Optimal starts at (Q-1, T-1); the byte has bits 0-3 only (nothing is clipped, so the move rule is
+//                               the reference's at every interior cell, dpmatrix.h:447-486, and no walk stops at a score); the
+//                               final cell's pointer (dpmatrix.h:505-534) comes from row Q-2, still in registers, and from what
+//                               the row observer kept of column T-2; the walk always runs to a cell of row 1 or column 1, then (0,0).
+// Everything the kernels do not take — templates beyond 2048 columns, scoring systems ScoreRun sends through full builds, pairs
+// without an interior, a length class an instantiation was not kept for — goes through resident batches inside the call.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -34,12 +39,12 @@ namespace aln {
 
 constexpr size_t kAlignBudget = (size_t)1 << 30;   // bytes of strips (and of lists, and of lines) resident at a time
 
-struct HitDesc {            // one used slot the fused kernel takes, 32 bytes
+struct HitDesc {            // one used slot a fused kernel takes, 32 bytes
   int32_t q, t;             // sequence indices in the pools
-  int32_t q_end, t_end;     // the trusted end cell
-  float score;              // the slot's score: D[q_end][t_end] must equal it
+  int32_t q_end, t_end;     // local: the trusted end cell (non-local: unused, 0)
+  float score;              // local: the slot's score, D[q_end][t_end] must equal it (non-local: unused, 0)
   int32_t cls;              // template length class 1 .. 8
-  int64_t strip_off;        // first byte of the hit's strip: (q_end - 1) rows of 256 cls bytes
+  int64_t strip_off;        // first byte of the hit's strip: (q_end - 1) rows of 256 cls bytes (non-local: Q - 3 rows)
 };
 
 // hit of the chunk -> its length class (class_list_kernel, score_common.h)
@@ -58,15 +63,17 @@ struct AlignArgs {
   int32_t* same;            // identical aligned residues of the list (calcIdentity's count before its "- 2")
 };
 
-// sweep_local's observer: the strip byte of every cell (see the head of the file), one 32-bit store per lane and group
+// The sweeps' observer: the strip byte of every cell (see the head of the file), one 32-bit store per lane and group.
+// SCORE_BIT: bit 4, which only the local walk reads.
+template <bool SCORE_BIT>
 struct StripObserver : NoObserver {
-  uint8_t* strip; int pitch;                    // row i (2 .. q_end) at strip + (i - 2) * pitch
+  uint8_t* strip; int pitch;                    // row i (2 .. last) at strip + (i - 2) * pitch
   uint32_t w = 0;
   __device__ __forceinline__ void cell(int, int x, int m, int e, int f, int pv, int A, int gmx, int key) {
     uint32_t b = (m >= max(e, f)) ? 0u : (e >= f ? 1u : 2u);
     b |= (pv >= A) ? 4u : 0u;
     b |= (gmx >= key) ? 8u : 0u;
-    b |= (m > 0) ? 16u : 0u;
+    if (SCORE_BIT) b |= (m > 0) ? 16u : 0u;
     w = (x == 0 ? 0u : w) | (b << (8 * x));
   }
   __device__ __forceinline__ void group(int i, int r) {       // the lane's four columns: 256 contiguous bytes per wave
@@ -94,7 +101,7 @@ __global__ __launch_bounds__(64) void align_local_hit_kernel(ScoreArgs a, AlignA
   cols.load(tc, T, a.gi, a.ge);
   int d[R][4];
   __builtin_assume(q_end >= 1);                 // row 1 always runs, as the host guarantees: no path around it to keep registers for
-  StripObserver bytes;
+  StripObserver<true> bytes;
   bytes.strip = strip; bytes.pitch = kPitch;
   sweep_local<R>(tab, cols, qc, q_end, d, bytes);
   // D[q_end][t_end]: row q_end is in d[], column t_end in slot (rs, xs) of lane ls
@@ -173,9 +180,151 @@ __global__ __launch_bounds__(64) void align_local_hit_kernel(ScoreArgs a, AlignA
   }
 }
 
+// sweep_global's observer: the strip bytes, and what the final cell's pointer (dpmatrix.h:505-534) needs.
+//   row():  of column T-2 the first row k <= Q-3 holding the maximal insertion key D[k][T-2] + gek k (gek = ge, or 0 under a free
+//           tail insertion).  Row Q-2 costs nothing and equals the match candidate, which comes first: it never wins and is left out.
+//   last(): of row Q-2 the match candidate D[Q-2][T-2] and the best deletion with the smallest column holding it (column T-2
+//           costs nothing and ties the match).
+template <int R>
+struct GlobalObserver : StripObserver<false> {
+  const GlobalCols<R>& k;
+  int free_del, gek, lastk;                     // lastk = Q - 3
+  int ikey = kNegS, irow = 0;                   // irow == 0: no candidate (owning lane only)
+  int match = kNegS, dlv = kNegS, dlc = 0;      // after last(): wave-uniform
+  __device__ __forceinline__ GlobalObserver(const GlobalCols<R>& k_, int free_del_, int gek_, int lastk_)
+      : k(k_), free_del(free_del_), gek(gek_), lastk(lastk_) {}
+  __device__ __forceinline__ void row(int i, const int (&d)[R][4], int) {
+    const int key = sweep_pick<R>(d, k.rs, k.xs, kNegS) + gek * i;
+    const bool up = (int)threadIdx.x == k.ls && i <= lastk && key > ikey;   // strictly greater: the smallest row wins ties
+    ikey = up ? key : ikey;
+    irow = up ? i : irow;
+  }
+  __device__ __forceinline__ void last(const int (&d)[R][4]) {
+    match = __shfl(sweep_pick<R>(d, k.rs, k.xs, kNegS), k.ls);
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        const int c = 4 * (int)threadIdx.x + 256 * r + x;
+        const int len = k.T - 2 - c;
+        const int cost = (len < 1 || free_del) ? 0 : k.gi + k.ge * (len - 1);
+        const int v = k.in[r][x] ? d[r][x] - cost : kNegS;
+        const bool up = v > dlv;                // the lane's columns ascend
+        dlv = up ? v : dlv;
+        dlc = up ? c : dlc;
+      }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {   // value max, column min
+      const int ov = __shfl_xor(dlv, off), oc = __shfl_xor(dlc, off);
+      const bool take = ov > dlv || (ov == dlv && oc < dlc);
+      dlv = take ? ov : dlv;
+      dlc = take ? oc : dlc;
+    }
+  }
+};
+
+template <int R>
+__global__ __launch_bounds__(64) void align_global_hit_kernel(ScoreArgs a, AlignArgs g, int free_del, int free_ins) {
+  __shared__ int tab[32 * 32];
+  const int lane = threadIdx.x;
+  for (int k = lane; k < 32 * 32; k += 64) tab[k] = a.table32[k];
+  __syncthreads();
+  const int hit = g.list[blockIdx.x];
+  const HitDesc hd = g.desc[hit];
+  const int ti = hd.t, qi = hd.q;
+  const uint8_t* __restrict__ qc = a.qcodes + a.qoff[qi];
+  const uint8_t* __restrict__ tc = a.tcodes + a.toff[ti];
+  const int Q = (int)(a.qoff[qi + 1] - a.qoff[qi]), T = (int)(a.toff[ti + 1] - a.toff[ti]);   // Q >= 3, T >= 3: the host's routing
+  const int gi = a.gi, ge = a.ge;
+  constexpr int kPitch = 256 * R;
+  uint8_t* strip = g.strip + hd.strip_off;      // row i (2 .. Q-2) at strip + (i - 2) * kPitch
+
+  GlobalCols<R> cols;
+  cols.load(tc, T, gi, ge);
+  GlobalObserver<R> ob(cols, free_del, free_ins ? 0 : ge, Q - 3);
+  ob.strip = strip; ob.pitch = kPitch;
+  int score = sweep_global<R>(tab, cols, qc, Q, free_del, free_ins, ob);
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) score = max(score, __shfl_xor(score, off));
+
+  // ---- the final cell's pointer (dpmatrix.h:505-534): match, deletions from (Q-2, k) k ascending, insertions from (k, T-2) k
+  // ascending; a later candidate wins only when strictly greater ---------------------------------------------------------------
+  const int match = ob.match, dlv = ob.dlv;
+  const int irow = __shfl(ob.irow, cols.ls);
+  const int ikey = __shfl(ob.ikey, cols.ls);
+  const int ilv = irow == 0 ? kNegS : (free_ins ? ikey : ikey - (gi + ge * (Q - 3)));
+  int i = Q - 2, j = T - 2;
+  if (dlv > match) j = ob.dlc;
+  if (ilv > max(match, dlv)) { i = irow; j = T - 2; }
+  __threadfence();                                           // the walk's lanes read bytes other lanes stored
+  __syncthreads();
+
+  // ---- the walk back (optimal.h:56-74): it always runs to a cell of row 1 or column 1, which points at (0,0) -------------------
+  int32_t* o = g.trav + (size_t)hit * g.trav_stride * 2;
+  const int cap = g.trav_stride;
+  int n = 0, same = 0;
+  auto emit1 = [&](int q, int t) {
+    if (lane == 0 && n < cap) { o[2 * n] = q; o[2 * n + 1] = t; same += (qc[q] == tc[t]) ? 1 : 0; }
+    ++n;
+  };
+  auto at = [&](int ii, int c) -> uint32_t { return strip[(size_t)(ii - 2) * kPitch + c]; };
+  emit1(Q - 1, T - 1);
+  emit1(i, j);
+  while (i >= 2 && j >= 2) {
+    // lane l looks at cell (i - l, j - l): its byte holds the move into it
+    const int ci = i - lane, cj = j - lane;
+    const bool valid = ci >= 2 && cj >= 2;
+    const uint32_t b = valid ? at(ci, cj - 1) : 0u;
+    const bool go = valid && (b & 3u) == 0u;
+    const unsigned long long m = __ballot(go);
+    const int L = (~m == 0ull) ? 64 : __builtin_ctzll(~m);   // lanes 0 .. L-1 step diagonally
+    if (lane < L) {
+      const int k = n + lane;
+      if (k < cap) { o[2 * k] = ci - 1; o[2 * k + 1] = cj - 1; same += (qc[ci - 1] == tc[cj - 1]) ? 1 : 0; }
+    }
+    n += L; i -= L; j -= L;
+    if (L == 64) continue;
+    if (i < 2 || j < 2) break;
+    const uint32_t mv = (uint32_t)__shfl((int)b, L) & 3u;    // 1 or 2: lane L is valid and did not go
+    int pi, pj;
+    if (mv == 1u) {                                          // deletion: the smallest column of row i-1 holding the maximal key
+      pi = i - 1; pj = 0;
+      for (int k0 = j - 2; k0 >= 1; k0 -= 64) {
+        const int kk = k0 - lane;
+        const uint32_t bb = kk >= 1 ? at(i, kk) : 0u;
+        const unsigned long long clr = __ballot((bb & 4u) == 0u);
+        if (clr) { pj = k0 - __builtin_ctzll(clr); break; }
+      }
+    } else {                                                 // insertion: the smallest row of column j-1 holding the maximal key
+      pj = j - 1; pi = 0;
+      for (int k0 = i - 2; k0 >= 1; k0 -= 64) {
+        const int kk = k0 - lane;
+        const uint32_t bb = kk >= 1 ? at(kk + 1, pj) : 0u;
+        const unsigned long long clr = __ballot((bb & 8u) == 0u);
+        if (clr) { pi = k0 - __builtin_ctzll(clr); break; }
+      }
+    }
+    if (pi < 1 || pj < 1) break;                             // (cannot happen: row 1 and column 1 always clear their bits)
+    emit1(pi, pj);
+    i = pi; j = pj;
+  }
+  emit1(0, 0);
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) same += __shfl_xor(same, off);
+  if (lane == 0) {
+    PairResult res = {};
+    res.best = (float)score; res.corner = 0.f; res.best_q = Q - 1; res.best_t = T - 1;
+    res.n_path = n;
+    res.status = n <= cap ? 0 : ALN_E_OVERFLOW;
+    g.res[hit] = res;
+    g.same[hit] = same;
+  }
+}
+
 // The instantiations kept: every one compiles without scratch memory and without VGPR spills (DESIGN 4.8d has the table).
 // R = 8 (templates of 1793 .. 2048 columns) does not — 24 VGPRs spilled into AGPRs — so that class goes the batch route.
 constexpr unsigned kFusedClasses = 0x0FEu;                   // bit R set: class R runs in align_local_hit_kernel<R>
+constexpr unsigned kFusedGlobalClasses = 0x1FEu;             // bit R set: class R runs in align_global_hit_kernel<R>
 
 // Where the results of one slot go, and how they are written (the same for both routes)
 struct AlignOut {
@@ -261,6 +410,7 @@ extern "C" int aln_hits_align(aln_ctx* ctx, const aln_seqs* queries, const aln_s
                               const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K, const aln_hit* hits,
                               const int32_t* n_hits, aln_hit_alignment* out, int32_t* pairs, int32_t pair_stride, char* tlines,
                               char* qlines, int32_t line_stride, int32_t* lengths) {
+  if (ctx) ctx->align_routes[0] = ctx->align_routes[1] = 0;
   if (!hits || !n_hits || !out || K < 1 || K > 1024) return ALN_E_ARG;
   if (pairs ? pair_stride < 2 : false) return ALN_E_ARG;
   const bool want_lines = tlines || qlines;
@@ -270,7 +420,16 @@ extern "C" int aln_hits_align(aln_ctx* ctx, const aln_seqs* queries, const aln_s
   if (rc != ALN_OK) return rc;
   const int rows = run.rows, n_t = run.n_t;
   if (rows == 0) return ALN_OK;
-  const bool fused_ok = run.route == ScoreRun::kFast && run.local;
+  const bool fused_ok = run.route == ScoreRun::kFast && (run.local || ctx->hints.align_fused_nonlocal);
+  const unsigned fused_classes = run.local ? kFusedClasses : kFusedGlobalClasses;
+  // a fused hit's strip rows and the most entries its list can have
+  auto strip_rows = [&](const HitDesc& d) {
+    return run.local ? d.q_end - 1 : (int)(queries->offsets[d.q + 1] - queries->offsets[d.q]) - 3;
+  };
+  auto list_cap = [&](const HitDesc& d) {
+    if (run.local) return std::min(d.q_end, d.t_end) + 3;
+    return (int)std::min(queries->offsets[d.q + 1] - queries->offsets[d.q], templates->offsets[d.t + 1] - templates->offsets[d.t]) + 1;
+  };
 
   // one walk: validate every used slot, describe it for its route, count the classes (nothing is written before it ends)
   std::vector<HitDesc> fast;            // the fused kernel's hits, row-major
@@ -289,12 +448,14 @@ extern "C" int aln_hits_align(aln_ctx* ctx, const aln_seqs* queries, const aln_s
       const bool interior = Q >= 3 && T >= 3;
       if (run.local && interior && (h.q_end < 1 || h.q_end > Q - 2 || h.t_end < 1 || h.t_end > T - 2)) return ALN_E_ARG;
       const int cls = (int)((T + 255) / 256);
-      if (fused_ok && interior && T <= 2048 && ((kFusedClasses >> cls) & 1u)) {
-        HitDesc d = {q, h.t, h.q_end, h.t_end, h.score, cls, 0};
+      if (fused_ok && interior && T <= 2048 && ((fused_classes >> cls) & 1u)) {
+        HitDesc d = {q, h.t, 0, 0, 0.f, cls, 0};                 // non-local: the slot's end cell and score are ignored
+        if (run.local) { d.q_end = h.q_end; d.t_end = h.t_end; d.score = h.score; }
         fast.push_back(d); fast_slot.push_back(slot);
       } else { bq.push_back(q); bt.push_back(h.t); bslot.push_back(slot); }
     }
   }
+  ctx->align_routes[0] = (int64_t)fast.size(); ctx->align_routes[1] = (int64_t)bq.size();
   AlignOut ao = {out, pairs, pair_stride, tlines, qlines, line_stride, lengths};
   for (int r = 0; r < rows; ++r)
     for (int k = std::max(n_hits[r], 0); k < K; ++k) {
@@ -313,8 +474,8 @@ extern "C" int aln_hits_align(aln_ctx* ctx, const aln_seqs* queries, const aln_s
     Chunk c = {0, 0, 0, 4, {0, 0, 0, 0, 0, 0, 0, 0, 0}};
     for (size_t h = 0; h < fast.size(); ++h) {
       HitDesc& d = fast[h];
-      const size_t need = (size_t)std::max(d.q_end - 1, 1) * 256 * (size_t)d.cls;
-      const int ts = std::max(c.trav_stride, std::min(d.q_end, d.t_end) + 3);
+      const size_t need = (size_t)std::max(strip_rows(d), 1) * 256 * (size_t)d.cls;
+      const int ts = std::max(c.trav_stride, list_cap(d));
       const bool full = c.n >= forced || c.strip + need > kAlignBudget || (c.n + 1) * (size_t)ts * 8 > kAlignBudget ||
                         (want_lines && (c.n + 1) * 2 * (size_t)line_stride > kAlignBudget);
       if (c.n > 0 && full) {
@@ -323,7 +484,7 @@ extern "C" int aln_hits_align(aln_ctx* ctx, const aln_seqs* queries, const aln_s
       }
       d.strip_off = (int64_t)c.strip;
       c.strip += need; c.n++; c.cls_cnt[d.cls]++;
-      c.trav_stride = std::max(c.trav_stride, std::min(d.q_end, d.t_end) + 3);
+      c.trav_stride = std::max(c.trav_stride, list_cap(d));
     }
     if (c.n > 0) chunks.push_back(c);
   }
@@ -381,9 +542,15 @@ extern "C" int aln_hits_align(aln_ctx* ctx, const aln_seqs* queries, const aln_s
       for (int k = 1; k <= 8; ++k) {
         if (c.cls_cnt[k] == 0) continue;
         g.list = dlist + co.off[k];
-        dispatch_r<7>(k, [&](auto rc) {                         // (class 8 never gets here: kFusedClasses)
-          hipLaunchKernelGGL(align_local_hit_kernel<decltype(rc)::value>, dim3(c.cls_cnt[k]), dim3(64), 0, ctx->stream, run.a, g);
-        });
+        if (run.local)
+          dispatch_r<7>(k, [&](auto rc) {                       // (class 8 never gets here: kFusedClasses)
+            hipLaunchKernelGGL(align_local_hit_kernel<decltype(rc)::value>, dim3(c.cls_cnt[k]), dim3(64), 0, ctx->stream, run.a, g);
+          });
+        else
+          dispatch_r<8>(k, [&](auto rc) {                       // kFusedGlobalClasses
+            hipLaunchKernelGGL(align_global_hit_kernel<decltype(rc)::value>, dim3(c.cls_cnt[k]), dim3(64), 0, ctx->stream, run.a, g,
+                               run.free_del, run.free_ins);
+          });
         STRY(hipGetLastError());
       }
       if (want_lines) {
@@ -428,4 +595,10 @@ extern "C" int aln_hits_align(aln_ctx* ctx, const aln_seqs* queries, const aln_s
     if (rc != ALN_OK) return rc;
   }
   return ao.worst;
+}
+
+extern "C" int aln_hits_align_last_routes(const aln_ctx* ctx, int64_t out[2]) {
+  if (!ctx || !out) return ALN_E_ARG;
+  out[0] = ctx->align_routes[0]; out[1] = ctx->align_routes[1];
+  return ALN_OK;
 }

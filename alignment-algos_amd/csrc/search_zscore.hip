@@ -119,7 +119,7 @@ __global__ __launch_bounds__(64) void score_shuffled_kernel(ZScoreArgs z) {
   } else {
     GlobalCols<R> cols;
     cols.load(tc, T, z.a.gi, z.a.ge);
-    for (int s = 0; s < n_s; ++s) add(sweep_global<R>(tab, cols, q0 + (size_t)s * Q, Q, z.free_del, z.free_ins));
+    for (int s = 0; s < n_s; ++s) add(sweep_global<R>(tab, cols, q0 + (size_t)s * Q, Q, z.free_del, z.free_ins, NoObserver()));
   }
   if (lane == 0) {
     atomicAdd(&z.acc[2 * (size_t)slot], (unsigned long long)sum);

@@ -214,6 +214,9 @@ int aln_has_gfx950(void);
  *                                   accumulators (16 B x K per row) below 1 GiB each; a larger value is cut to that
  *   "align_chunk_hits"              aln_hits_align: hit slots whose 1 B/cell strips are resident on the device at a time; 0 (default) = as
  *                                   many as keep the strips, the lists and the lines below 1 GiB each; a value never lifts that budget
+ *   "align_fused_nonlocal"          aln_hits_align: 1 (default) = hits of the four non-local align types are aligned by the fused
+ *                                   kernel where it applies; 0 = they all go through resident batches (environment default
+ *                                   ALN_ALIGN_FUSED_NONLOCAL).  Same results.
  * Unknown key -> ALN_E_ARG.  No hint changes any result. */
 int aln_ctx_set_hint(aln_ctx* ctx, const char* key, int64_t value);
 int aln_ctx_get_hint(const aln_ctx* ctx, const char* key, int64_t* value);
@@ -412,9 +415,14 @@ typedef struct {
  * With an integer table and gaps and a template of up to 2048 columns one wave per hit sweeps rows 1 .. q_end with the state
  * in registers, writes 1 byte per cell into a transient strip and walks back through it (csrc/search_align.hip): no batch, no
  * planes, no find_max.  When the sweep's D[q_end][t_end] differs from the slot's .score the slot reports status ALN_E_ARG and
- * n_pairs 0 and the call goes on.  The four other align types ignore q_end / t_end.  They, longer templates, fractional
- * scoring systems and pairs without an interior go through resident batches inside the call (~12 GB of planes at a time), so
- * the call accepts what aln_search_topk accepts.
+ * n_pairs 0 and the call goes on.
+ * The four other align types ignore the slot's q_end, t_end and score: Optimal starts at (Q-1, T-1).  Under the same conditions
+ * (integer table and gaps, template of up to 2048 columns, Q >= 3 and T >= 3) one wave per hit sweeps every row 1 .. Q-2,
+ * writes 1 byte per cell into a transient strip of Q-3 rows, takes the final cell's pointer from the last row and the last
+ * column and walks back to the origin; hint "align_fused_nonlocal" = 0 sends them through batches instead.
+ * Longer templates, fractional scoring systems, pairs without an interior and, ALN_LOCAL, templates of 1793 .. 2048 columns go
+ * through resident batches inside the call (~12 GB of planes at a time), so the call accepts what aln_search_topk accepts.
+ * aln_hits_align_last_routes tells how many slots went which way.
  * Checks, in this order, nothing written when one fails: NULL hits / n_hits / out, K outside 1..1024, pairs with
  * pair_stride < 2, the line group given in part or line_stride < 1 (ALN_E_ARG); aln_score_all_vs_all's, in its order; every
  * n_hits[r] in 0..K, every used slot's t in [0, n_templates) and, local, its end cell in range (ALN_E_ARG).
@@ -427,6 +435,9 @@ int aln_hits_align(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templa
                    aln_hit_alignment* out /* (q_end-q_begin) x K */,
                    int32_t* pairs, int32_t pair_stride /* NULL, or rows x K x pair_stride x 2 int32 */,
                    char* tlines, char* qlines, int32_t line_stride, int32_t* lengths /* all NULL, or as aln_batch_optimal_strings */);
+/* out[0]: the used slots the last aln_hits_align call on this context sent through a fused kernel, out[1]: through resident
+ * batches; { 0, 0 } before any call and after a call that failed its checks.  NULL argument: ALN_E_ARG. */
+int aln_hits_align_last_routes(const aln_ctx* ctx, int64_t out[2]);
 
 /* ---- multi-GPU: a length-sorted deal of independent units + ONE collective (RCCL all-gather of scores) ----------- */
 /* The reference is one thread, one DPMatrix at a time; pairs are independent (dpmatrix.h:104-111), so ranks own disjoint pair

@@ -9,7 +9,14 @@ U[400,600] (seed 5000+s), against all of them, local 11/1 BLOSUM62, the K best t
 Each timed as the median of 5 repetitions after a warm-up (min and max are printed too).  Both routes must give the same pair
 lists (checked).  Bytes written per cell: (a) 1 B over rows <= q_end of 256 ceil(T/256) columns, (b) the plane bytes
 aln_batch_plane_bytes_per_cell reports over all Q x T cells.  Prints one JSON line.
-usage: bench_align_hits.py [Q] [T] [K]"""
+
+With a fourth argument, an align type other than local (global_local, global, local_global, semi_local), the search and both
+routes run under that type and
+  (a) fused  is aln_hits_align as it stands: one wave per hit sweeps every row 1..Q-2, 1 byte per cell into a strip of Q-3 rows
+  (b) batch  is the same aln_hits_align call with hint align_fused_nonlocal = 0: every hit through resident batches inside the
+             call, lines included — what the call did before the non-local fused kernel existed
+and the two calls' outputs must be byte-identical (checked).  aln_hits_align_last_routes is reported for both.
+usage: bench_align_hits.py [Q] [T] [K] [align type, default local]"""
 import ctypes as C
 import json
 import os
@@ -52,9 +59,61 @@ def host_lines(q, t, pl):
     return tl.value.decode(), ql.value.decode()
 
 
+ALIGN_TYPES = {"global_local": aln_amd.GLOBAL_LOCAL, "global": aln_amd.GLOBAL, "local_global": aln_amd.LOCAL_GLOBAL,
+               "local": aln_amd.LOCAL, "semi_local": aln_amd.SEMI_LOCAL}
+
+
+def nonlocal_main(ctx, pool, seqs, alphabet, table, rows, n, K, name):
+    mode = ALIGN_TYPES[name]
+
+    def search():
+        return aln_amd.search_topk(ctx, pool, pool, alphabet, table, 11, 1, K, q_end=rows, align_type=mode)
+
+    hits, n_hits = search()
+    routes = {}
+
+    def fused():
+        res = aln_amd.hits_align(ctx, pool, pool, hits, n_hits, alphabet, table, 11, 1, align_type=mode)
+        routes["a"] = aln_amd.hits_align_routes(ctx)
+        return res
+
+    def batch():
+        with ctx.hints(align_fused_nonlocal=0):
+            res = aln_amd.hits_align(ctx, pool, pool, hits, n_hits, alphabet, table, 11, 1, align_type=mode)
+            routes["b"] = aln_amd.hits_align_routes(ctx)
+        return res
+
+    t_search, t_a, t_b = timed(search), timed(fused), timed(batch)
+    a, b = fused(), batch()
+    assert a[5] == 0 and b[5] == 0 and a[0].tobytes() == b[0].tobytes() and np.array_equal(a[4], b[4])
+    assert a[2] == b[2] and a[3] == b[3]
+    assert all(np.array_equal(x, y) for ra, rb in zip(a[1], b[1]) for x, y in zip(ra, rb))
+    used = [(r, c) for r in range(rows) for c in range(K) if c < n_hits[r]]
+    cells_all = strip = 0
+    for r, c in used:
+        Qn, Tn = len(seqs[r]) + 2, len(seqs[hits["t"][r, c]]) + 2
+        cells_all += Qn * Tn
+        strip += max(Qn - 3, 1) * 256 * ((Tn + 255) // 256)
+    bt = aln_amd.Batch(ctx, pool, pool, [0], [int(hits["t"][0, 0])])
+    bt.dp_submatrix(alphabet, table, mode, 11, 1)
+    plane_b = bt.plane_bytes_per_cell()
+    bt.close()
+    med = lambda v: float(np.median(v))   # noqa: E731
+    print(json.dumps({"align_type": name, "n_queries": rows, "n_templates": n, "K": K, "hits": len(used), "outputs_equal": True,
+                      "a_routes_fused_batched": routes["a"], "b_routes_fused_batched": routes["b"],
+                      "search_topk": stat(t_search), "a_hits_align": stat(t_a), "b_hits_align_through_batches": stat(t_b),
+                      "a_total_median_ms": 1e3 * (med(t_search) + med(t_a)), "b_total_median_ms": 1e3 * (med(t_search) + med(t_b)),
+                      "a_bytes_written": strip, "a_bytes_per_matrix_cell": strip / float(cells_all),
+                      "b_bytes_written": plane_b * cells_all, "b_bytes_per_matrix_cell": plane_b}))
+    return 0
+
+
 def main():
     arg = lambda k, d: int(sys.argv[k]) if len(sys.argv) > k else d   # noqa: E731
     rows, n, K = arg(1, 512), arg(2, 4096), arg(3, 10)
+    align_type = sys.argv[4] if len(sys.argv) > 4 else "local"
+    if align_type not in ALIGN_TYPES:
+        sys.exit("align type: one of " + ", ".join(ALIGN_TYPES))
     lines = open(os.path.join(ROOT, "tests", "golden", "BLOSUM62")).read().split("\n")
     k = 0
     while lines[k].startswith("#"):
@@ -67,6 +126,8 @@ def main():
         seqs.append(residues(g, 400 + int(g.draw(1)[0] % 201)))
     pool = aln_amd.SeqPool(seqs)
     ctx = aln_amd.Context(0)
+    if align_type != "local":
+        return nonlocal_main(ctx, pool, seqs, alphabet, table, rows, n, K, align_type)
 
     def search():
         return aln_amd.search_topk(ctx, pool, pool, alphabet, table, 11, 1, K, q_end=rows)
