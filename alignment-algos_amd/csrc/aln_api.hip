@@ -192,8 +192,9 @@ static int64_t matrix_cells(const aln_batch* b) {
   for (const PairDesc& d : b->h_pairs) n += (int64_t)d.Q * d.T;
   return n;
 }
-// score element + pointer element of the layout the last build chose (aln_device.h load_score / load_ptr_word)
-int32_t aln_batch_plane_bytes_per_cell(const aln_batch* b) { return b ? (b->h_mode ? 2 : 4) + (b->ptr_mode ? 2 : 4) : 0; }
+// score element + pointer element of the layout the last build chose (aln_device.h load_score / load_ptr_word); a lean build
+// writes flagged pointer words only
+int32_t aln_batch_plane_bytes_per_cell(const aln_batch* b) { return b ? (b->planes_lean ? 2 : (b->h_mode ? 2 : 4) + (b->ptr_mode ? 2 : 4)) : 0; }
 int64_t aln_batch_dp_algorithmic_bytes(const aln_batch* b) { return b ? matrix_cells(b) * aln_batch_plane_bytes_per_cell(b) : 0; }
 int64_t aln_batch_dp_contract_bytes(const aln_batch* b) { return b ? matrix_cells(b) * 8 : 0; }   // fp32 score + packed pointer
 int64_t aln_batch_device_bytes(const aln_batch* b) {
@@ -382,7 +383,8 @@ int upload_tgaps(aln_batch* b, const aln_gap* gap) {
   return ALN_OK;
 }
 
-int run_dp(aln_batch* b, bool simplane_integral) {
+// lean: the caller (aln_batch_reevaluate) allows a lean build; whether this launch can make one is launch_tag_variant's decision
+int run_dp(aln_batch* b, bool simplane_integral, bool lean = false) {
   aln_ctx* ctx = b->ctx;
   if (b->n_pairs == 0) { b->have_dp = true; b->kernel_name = "(empty batch)"; return ALN_OK; }   // nothing to launch
   const bool sub = b->sim_kind == ALN_SIM_SUBMATRIX;
@@ -392,6 +394,7 @@ int run_dp(aln_batch* b, bool simplane_integral) {
     tagged = fast && sub && tag_path_legal(b, b->h_table.data(), b->alpha_n, &b->gap) && ctx->hints.tag_kernel;
   }
   if (b->algo == ALN_DP_FAST && !fast) return (b->maxld > 8192 && b->gap.model == ALN_GAP_AFFINE_CONST) ? ALN_E_TOO_LONG : ALN_E_NOT_INTEGRAL;
+  b->lean_request = lean; b->planes_lean = false; b->optimal_since_build = false; b->score_read_since_build = false;
   // pointer dialect of the P plane (aln_device.h decode_ptr): 0 = packed 32-bit, 1 / 2 = 16-bit tagged words with 11 / 12 tag bits
   b->ptr_mode = tagged ? (tag_path_bits(b, b->h_table.data(), b->alpha_n, &b->gap) == 12 ? 2 : 1) : 0;
   b->h_mode = (tagged && b->islocal && ctx->hints.h16 && tag_h16_legal(b)) ? 1 : 0;   // local scores of the tagged path are integers in [0, 65535]
@@ -414,6 +417,19 @@ int run_dp(aln_batch* b, bool simplane_integral) {
 }
 
 }  // namespace
+
+namespace aln {
+int ensure_full(aln_batch* b) {
+  if (!b->planes_lean) { b->score_read_since_build = true; return ALN_OK; }
+  // the same build again, full this time.  Optimal results already enqueued are stream-ordered copies and stay valid; the
+  // traceback is repeated where the lean build had it, so that d_res / d_path describe the planes that are resident now.
+  const bool had_optimal = b->optimal_build == b->n_builds;
+  int rc = run_dp(b, b->simplane_integral);
+  if (rc == ALN_OK && had_optimal) rc = launch_traceback(b, false);
+  b->score_read_since_build = true;
+  return rc;
+}
+}  // namespace aln
 
 extern "C" {
 
@@ -511,7 +527,11 @@ int aln_batch_set_gap(aln_batch* b, const aln_gap* gap) {
 int aln_batch_reevaluate(aln_batch* b) {
   if (!b) return ALN_E_ARG;
   if (!b->have_dp) return ALN_E_STATE;
-  return run_dp(b, b->simplane_integral);      // the resident similarity planes are the ones the first build proved integral (or not)
+  // lean (2 B/cell, dp_affine_tag.hip) when the build being replaced served Optimal and nothing that reads scores: a caller that
+  // enumerates or reads cells after every reevaluate never pays for a lean build it would have to repeat
+  const int h = b->ctx->hints.lean_reevaluate;
+  const bool lean = h == 2 || (h == 1 && b->optimal_since_build && !b->score_read_since_build);
+  return run_dp(b, b->simplane_integral, lean);      // the resident similarity planes are the ones the first build proved integral (or not)
 }
 
 int aln_batch_dp_sub(aln_batch* b, const aln_sim* sim, const aln_gap* gap, int32_t direction, const int32_t* bounds) {
@@ -573,6 +593,7 @@ int aln_batch_get_cells(aln_batch* b, int32_t pair, float* score, int32_t* prev_
   if (!b || pair < 0 || pair >= b->n_pairs) return ALN_E_ARG;
   if (!b->have_dp) return ALN_E_STATE;
   aln_ctx* ctx = b->ctx;
+  { const int rc = ensure_full(b); if (rc) return rc; }
   const PairDesc& d = b->h_pairs[pair];
   const size_t n = (size_t)d.Q * d.ld;
   std::vector<float> h(score ? n : 0);
@@ -727,7 +748,9 @@ int aln_batch_optimal_subali(aln_batch* b, float* scores, int32_t* n, int32_t* p
   if (!b) return ALN_E_ARG;
   if (!b->have_dp || !b->have_sub) return ALN_E_STATE;
   if (b->n_pairs == 0) return ALN_OK;
-  int rc = launch_traceback(b, true);
+  int rc = ensure_full(b);
+  if (rc) return rc;
+  rc = launch_traceback(b, true);
   if (rc) return rc;
   return fetch_paths(b, scores, n, pairs, pair_stride, status, true, true);
 }

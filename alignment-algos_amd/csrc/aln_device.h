@@ -151,6 +151,9 @@ __host__ __device__ __forceinline__ float load_score(const float* Hbase, int64_t
   if (hmode == 0) return Hbase[e];
   return (float)reinterpret_cast<const uint16_t*>(Hbase)[e];
 }
+// Lean planes (dp_affine_tag.hip LEAN): no score plane; bit 15 of a cell's pointer word (dialect 1 uses bits 0..12) is set when its
+// score is > 0, which is all the local traceback asks.  1 / 0 stand in for the score.
+__host__ __device__ __forceinline__ float flag_score(uint32_t w) { return (w != 0xFFFFFFFFu && (w & 0x8000u)) ? 1.f : 0.f; }
 __host__ __device__ __forceinline__ void store_score(float* Hbase, int64_t plane_off, int ld, int i, int j, int hmode, float v) {
   const size_t e = (size_t)plane_off + (size_t)i * ld + j;
   if (hmode == 0) Hbase[e] = v;

@@ -28,6 +28,7 @@ const HintDef kDefs[] = {
     {"tag_solo", "ALN_TAG_SOLO", false, &aln_hints::tag_solo},
     {"tag_bits", "ALN_TAG_BITS", false, &aln_hints::tag_bits},
     {"tag_occupancy", "ALN_TAG_OCCUPANCY", false, &aln_hints::tag_occupancy},
+    {"lean_reevaluate", "ALN_LEAN_REEVALUATE", false, &aln_hints::lean_reevaluate},
     {"dp_variant_nw", nullptr, false, &aln_hints::dp_nw},
     {"dp_variant_r", nullptr, false, &aln_hints::dp_r},
     {"dp_variant_x", nullptr, false, &aln_hints::dp_x},

@@ -85,6 +85,8 @@ struct aln_hints {
   int tag_occupancy = 0;     // tagged kernel, 16-cell lanes: waves per SIMD it is compiled for: 2, 3, or 0 = three when the launch alone has >= 3 per SIMD
   int tag_bits = 0;          // 12: the 12-tag-bit layout (pointer dialect 2) also for sequences of up to 2048 residues (tests); 0 = by length
   int tag_solo = 0;          // 1: pairs of 1025..2048 columns run in dp_affine_solo (one wave per pair, no barriers; wants >= 2048 pairs in flight)
+  int lean_reevaluate = 1;   // aln_batch_reevaluate builds lean where the launch allows it: 0 = never, 1 = when the build it replaces was used by
+                             // Optimal and by nothing that reads scores, 2 = always
   int tag_segments = 0;      // tagged kernel: (pair, row segment) work items handed out by a queue (dp_affine_tag.hip "Segment queue"):
                              // K in 2..8 = long pairs are cut into K segments when the batch alone fills the GPU (>= 512 pairs), -K = whenever
                              // pairs are long, 0 = one workgroup per pair
@@ -168,6 +170,11 @@ struct aln_batch {
   bool simplane_integral = false;              // ALN_SIM_MATRIX planes of the last dp were all small integers (kept for reevaluate)
   int32_t ptr_mode;                            // encoding of the P plane words (aln_device.h decode_ptr)
   int32_t h_mode;                              // score plane element type: 0 fp32, 1 uint16 (aln_device.h load_score)
+  // lean builds (dp_affine_tag.hip LEAN): aln_batch_reevaluate may leave planes that serve the Optimal family only
+  bool lean_request = false;                   // the build being launched may be lean (run_dp sets it, launch_tag_variant decides)
+  bool planes_lean = false;                    // the resident planes are lean: flagged pointer words, score plane undefined but for the corner's cells
+  bool optimal_since_build = false;            // Optimal's traceback ran on the current build ...
+  bool score_read_since_build = false;         // ... and so did something that reads scores or plain pointer words (ensure_full)
   std::string kernel_name;
   hipEvent_t ev0, ev1;                          // around the DP kernel(s) of the latest build
   static const int kEvRing = 64;               // ... and of the builds before it (aln_batch_dp_ms_history)
@@ -226,6 +233,9 @@ bool dp_affine_solo_legal(const aln_batch* b);
 int launch_dp_affine_solo(aln_batch* b);
 // dp_corner.hip
 int launch_dp_corner(aln_batch* b);
+// aln_api.hip: every reader of the planes other than Optimal's traceback calls this first: a lean build is replaced by the full one
+// (DP + corner kernels on the batch's stream, counted as a build) and the read is remembered
+int ensure_full(aln_batch* b);
 // traceback.hip
 int launch_traceback(aln_batch* b, bool subali);
 // gapped_strings.hip

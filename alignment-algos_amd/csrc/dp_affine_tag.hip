@@ -42,7 +42,10 @@ __device__ __forceinline__ void setprio_dyn(int p) {     // s_setprio takes an i
 }
 
 // SEGQ: workgroups take (pair, row segment) items from the queue instead of building pair blockIdx.x from first to last row.
-template <int NW, int R, bool LOCAL, bool H16, int KBT, int X, bool SEGQ, int TB, int OCC>
+// LEAN: the build of a caller that only walks the optimal path afterwards (aln_batch_reevaluate).  Bit 15 of a
+// stored pointer word says "this cell's score is > 0" (all the local traceback ever asks of a score), and of the score plane only
+// what dp_corner_kernel reads is written: row Q-2 and, in every row, the 16-byte chunk that holds column T-2.  2 bytes per cell.
+template <int NW, int R, bool LOCAL, bool H16, int KBT, int X, bool SEGQ, int TB, int OCC, bool LEAN = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(R * X == 16 ? OCC : 1, R * X == 16 ? OCC : 8))) void dp_affine_tag_kernel(
     const PairDesc* __restrict__ pairs, const uint8_t* __restrict__ qcodes, const uint8_t* __restrict__ tcodes,
     const int32_t* __restrict__ table32, float* __restrict__ Hbase, uint32_t* __restrict__ Pbase,
@@ -56,6 +59,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(R * X =
   static_assert(KBT == 13 || (KBT == 16 && LOCAL && H16), "the 16-bit key layout needs non-negative 15-bit scores");
   static_assert(TB == 11 || TB == 12, "11 or 12 tag bits");
   static_assert(X == 4 || X == 8, "a lane owns 4 or 8 consecutive columns of each group");
+  static_assert(!LEAN || (NW == 2 && R == 2 && X == 8 && LOCAL && H16 && KBT == 16 && TB == 11 && !SEGQ), "one lean shape: the 16-bit key layout, whole pairs");
   constexpr int GW = 64 * X;            // columns of one group (one lane-contiguous stretch of a row)
   __shared__ int tab[32 * 32];          // substitution scores << KB
   __shared__ uint8_t qcs[1 << TB];      // the query's residue codes (Q <= 2^TB): one LDS byte per row instead of a global load
@@ -168,10 +172,40 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(R * X =
     if constexpr (X == 4) { const u32x2 v = {wd[0], wd[1]}; __builtin_amdgcn_raw_buffer_store_b64(v, rs, off, 0, 0); }
     else { const u32x4 v = {wd[0], wd[1], wd[2], wd[3]}; __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, 0); }
   };
-  auto store_row = [&](int i) {
+  // LEAN: column T-2 lies in the X-cell chunk (T-2) / X of a row; chunk 64 R w + 64 r + lane is this lane's in group r.
+  int own_r = -1;                       // the group whose chunk of column T-2 this lane stores in every row (-1: none)
+  // two constants of the lean stores, pinned in VGPRs: v_and_or_b32 and v_perm_b32 take no literal, and as SGPRs they made the
+  // full scalar file spill
+  uint32_t flag_bits = 0x80008000u, sel_high = 0x07060302u;
+  if constexpr (LEAN) {
+    asm volatile("" : "+v"(flag_bits), "+v"(sel_high));
+    const int tchunk = (T - 2) / X;
+    own_r = ((tchunk & 63) == lane) ? (tchunk >> 6) - w * R : -1;
+  }
+  auto store_row = [&](int i, bool border = false) {    // border: row 0 or Q-1 (LEAN: no chunk of column T-2 there)
     const size_t ro = (size_t)i * ld + cb;
     const __amdgpu_buffer_rsrc_t rsP = __builtin_amdgcn_make_buffer_rsrc(P + (size_t)i * ld, 0, ld * 2, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsH = __builtin_amdgcn_make_buffer_rsrc(H16p + (size_t)i * ld, 0, ld * 2, 0x00020000);
+    if constexpr (LEAN) {
+      const bool whole = i == Q - 2;          // scalar: the corner cell scans this row
+      asm volatile("" : "+v"(own_r));         // compared in every row: hoisted out of the loop the two tests cost two SGPR pairs
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        uint32_t pw[X / 2], hw[X / 2];
+#pragma unroll
+        for (int x = 0; x < X; x += 2) {
+          pw[x / 2] = __builtin_amdgcn_perm(pf[r][x + 1], pf[r][x], 0x05040100u);
+          hw[x / 2] = __builtin_amdgcn_perm((uint32_t)dk[r][x + 1], (uint32_t)dk[r][x], sel_high);
+          // both flags at once: a score is < 2^15 in the 16-bit key layout (tag_key16_legal), so score + 0x7FFF has bit 15 set
+          // exactly when score > 0 and never carries into the other half.  An OR: border and untouched cells have score 0 and
+          // keep 0xFFFF, every other word has bits 13..15 clear.  One v_add_u32 + one v_and_or_b32 per two cells.
+          pw[x / 2] |= (hw[x / 2] + 0x7FFF7FFFu) & flag_bits;
+        }
+        if (whole || (!border && own_r == r)) store_words(hw, rsH, vo16 + 2 * GW * r);   // exec-masked: usually one lane of the pair
+        store_words(pw, rsP, vo16 + 2 * GW * r);
+      }
+      return;
+    }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       // low halves of two pointer words (at KB = 16: of two whole keys): one v_perm_b32 per pair of cells
@@ -310,7 +344,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(R * X =
 #pragma unroll
       for (int x = 0; x < X; ++x) ak[r][x] = dk[r][x] + GK[r][x];
   }
-  if (seg == 0) store_row(0);   // untouched cells: score 0, null pointer (dpmatrix.cpp:17-25)
+  if (seg == 0) store_row(0, true);   // untouched cells: score 0, null pointer (dpmatrix.cpp:17-25)
   if (seg == 0 && Q >= 3) {
     // row 1 (dpmatrix.h:409-418 / :579-590): match at (1,1), otherwise one deletion from the origin -> pointer (0,0)
     const int qrow = (int)qcs[1] * 128;
@@ -483,7 +517,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(R * X =
     for (int r = 0; r < R; ++r)
 #pragma unroll
       for (int x = 0; x < X; ++x) { dk[r][x] = P_MATCH; pf[r][x] = kNullPtr; }
-    store_row(Q - 1);
+    store_row(Q - 1, true);
   }
 
   // ---- find_max partial (optimal.h:108-124): value and first row-major position over interior cells ----------
@@ -597,6 +631,9 @@ static int launch_tag_variant(aln_batch* b, const TagParams& prm_in) {
   const long wps = ((long)b->n_pairs * NW + 1023) / 1024;
   const bool auto3 = ((wps + 2) / 3) * 45 < ((wps + 1) / 2) * 32;
   const bool occ3 = R * X == 16 && !segq && (occ_hint == 3 || (occ_hint == 0 && auto3));
+  // the lean build (see the kernel) exists for one instantiation; aln_batch_reevaluate asks, this launch decides
+  constexpr bool kLeanShape = NW == 2 && R == 2 && X == 8 && TB == 11;
+  const bool lean = kLeanShape && b->lean_request && k16 && !segq;
 #define ALN_TAG_LAUNCH_O(LOC_, H16_, KB_, SQ_, OCC_)                                                                                 \
   hipLaunchKernelGGL((dp_affine_tag_kernel<NW, R, LOC_, H16_, KB_, X, SQ_, TB, OCC_>), grid, block, 0, st, b->d_pairs, b->d_qcodes, b->d_tcodes, \
                      b->d_table32, b->d_H, b->d_P, b->d_res, prm)
@@ -605,7 +642,16 @@ static int launch_tag_variant(aln_batch* b, const TagParams& prm_in) {
     else ALN_TAG_LAUNCH_O(LOC_, H16_, KB_, SQ_, 2);                                                                                  \
   } while (0)
 #define ALN_TAG_LAUNCH_Q(LOC_, H16_, KB_) do { if (segq) ALN_TAG_LAUNCH(LOC_, H16_, KB_, true); else ALN_TAG_LAUNCH(LOC_, H16_, KB_, false); } while (0)
-  if (k16) ALN_TAG_LAUNCH_Q(true, true, 16);
+  if constexpr (kLeanShape) {
+    if (lean) {
+      if (occ3) hipLaunchKernelGGL((dp_affine_tag_kernel<NW, R, true, true, 16, X, false, TB, 3, true>), grid, block, 0, st, b->d_pairs, b->d_qcodes,
+                                   b->d_tcodes, b->d_table32, b->d_H, b->d_P, b->d_res, prm);
+      else hipLaunchKernelGGL((dp_affine_tag_kernel<NW, R, true, true, 16, X, false, TB, 2, true>), grid, block, 0, st, b->d_pairs, b->d_qcodes,
+                              b->d_tcodes, b->d_table32, b->d_H, b->d_P, b->d_res, prm);
+    }
+  }
+  if (lean) {}
+  else if (k16) ALN_TAG_LAUNCH_Q(true, true, 16);
   else if (b->islocal && b->h_mode == 1) ALN_TAG_LAUNCH_Q(true, true, 13);
   else if (b->islocal) ALN_TAG_LAUNCH_Q(true, false, 13);
   else ALN_TAG_LAUNCH_Q(false, false, 13);
@@ -613,9 +659,10 @@ static int launch_tag_variant(aln_batch* b, const TagParams& prm_in) {
 #undef ALN_TAG_LAUNCH
 #undef ALN_TAG_LAUNCH_O
   char nm[96];
-  snprintf(nm, sizeof nm, "dp_affine_tag_kernel<NW=%d,R=%d,%s%s%s%s%s%s>%s", NW, R, X == 8 ? "X=8," : "", b->islocal ? "local" : "global",
-           b->h_mode == 1 ? ",h16" : "", k16 ? ",key16" : "", TB == 12 ? ",tag12" : "", occ3 ? ",occ3" : "", segq ? "+segq" : "");
+  snprintf(nm, sizeof nm, "dp_affine_tag_kernel<NW=%d,R=%d,%s%s%s%s%s%s%s>%s", NW, R, X == 8 ? "X=8," : "", b->islocal ? "local" : "global",
+           b->h_mode == 1 ? ",h16" : "", k16 ? ",key16" : "", TB == 12 ? ",tag12" : "", lean ? ",lean" : "", occ3 ? ",occ3" : "", segq ? "+segq" : "");
   b->kernel_name = nm;
+  b->planes_lean = lean;
   ALN_HIP_CHECK(b->ctx, hipGetLastError());
   return ALN_OK;
 }

@@ -422,6 +422,7 @@ extern "C" int aln_batch_enumerate(aln_batch* b, int32_t pair, const aln_noa* no
   if (noa->kind != ALN_ENUM_CW && noa->kind != ALN_ENUM_UCW && !ks) return ALN_E_ARG;
   aln_ctx* ctx = b->ctx;
   ALN_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  { const int rc = ensure_full(b); if (rc) return rc; }      // the searches read scores and plain pointer words
   const PairDesc& d = b->h_pairs[pair];
   // n_existing < 0: the set starts with the pair's Optimal alignment, like the drivers (aa_ali.cpp:83);
   // otherwise the caller's set already holds n_existing alignments whose scores take part in sortSet.
@@ -701,8 +702,10 @@ extern "C" int aln_batch_enumerate_all(aln_batch* b, const aln_noa* noa, const u
   ALN_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const int n = b->n_pairs;
   if (n == 0) return ALN_OK;
+  int rc = ensure_full(b);                                    // the searches read scores and plain pointer words
+  if (rc) return rc;
   // every set starts with the pair's Optimal alignment (aa_ali.cpp:83)
-  int rc = launch_traceback(b, false);
+  rc = launch_traceback(b, false);
   if (rc) return rc;
   EnumArgs a0 = {};
   a0.kind = noa->kind; a0.user_limit = default_user_limit(noa); a0.delta_ratio = noa->delta_ratio; a0.first_slot = 1;

@@ -18,7 +18,7 @@ struct TbParams {
   int rev;          // pointers lead towards larger indices (reverse build, Optimal_Rev)
   int stride;       // capacity in pairs of each pair's output list
   int ptr_mode;     // pointer word encoding of the P plane
-  int h_mode;       // score plane element type (aln_device.h load_score)
+  int h_mode;       // score plane element type (aln_device.h load_score); 2 = no score plane: bit 15 of a pointer word says "score > 0"
 };
 
 __global__ __launch_bounds__(64) void traceback_kernel(const PairDesc* __restrict__ pairs, const float* __restrict__ Hbase,
@@ -50,7 +50,10 @@ __global__ __launch_bounds__(64) void traceback_kernel(const PairDesc* __restric
     const int cq = q + sg * lane, ct = t + sg * lane;
     const bool valid = cq >= 0 && ct >= 0 && cq < Q && ct < T;
     uint32_t p = kNullPtr; float h = 0.f;
-    if (valid) { p = load_ptr_word(Pbase, pd.plane_off, ld, cq, ct, prm.ptr_mode); h = load_score(Hbase, pd.plane_off, ld, cq, ct, prm.h_mode); }
+    if (valid) {
+      p = load_ptr_word(Pbase, pd.plane_off, ld, cq, ct, prm.ptr_mode);
+      h = prm.h_mode == 2 ? flag_score(p) : load_score(Hbase, pd.plane_off, ld, cq, ct, prm.h_mode);
+    }
     const float hnext = __shfl_down(h, 1);      // score of the diagonal neighbour (lane+1's cell)
     const bool active = valid && before_stop(cq);   // the while loop would process this cell
     const int nq_ = cq + sg, nt_ = ct + sg;
@@ -80,7 +83,8 @@ __global__ __launch_bounds__(64) void traceback_kernel(const PairDesc* __restric
     const int nq = jq, nt = jt;
     if (pL == kNullPtr) { lq = -1; lt = -1; if (!prm.islocal) status = ALN_E_STARTPAIR; break; }
     if (prm.islocal) {
-      const float hn = load_score(Hbase, pd.plane_off, ld, nq, nt, prm.h_mode);
+      const float hn = prm.h_mode == 2 ? flag_score(load_ptr_word(Pbase, pd.plane_off, ld, nq, nt, prm.ptr_mode))
+                                       : load_score(Hbase, pd.plane_off, ld, nq, nt, prm.h_mode);
       if (hn <= 0.f) { lq = nq; lt = nt; break; }
     }
     emit1(nq, nt);
@@ -105,11 +109,11 @@ int launch_traceback(aln_batch* b, bool subali) {
   prm.rev = (b->direction == ALN_REV && !subali) ? 1 : 0;
   prm.stride = b->path_stride;
   prm.ptr_mode = b->ptr_mode;
-  prm.h_mode = b->h_mode;
+  prm.h_mode = b->planes_lean ? 2 : b->h_mode;
   hipLaunchKernelGGL(traceback_kernel, dim3(b->n_pairs), dim3(64), 0, b->ctx->stream, b->d_pairs, b->d_H, b->d_P,
                      b->d_res, b->d_path, prm);
   ALN_HIP_CHECK(b->ctx, hipGetLastError());
-  if (!subali) b->optimal_build = b->n_builds;
+  if (!subali) { b->optimal_build = b->n_builds; b->optimal_since_build = true; }
   return ALN_OK;
 }
 

@@ -238,7 +238,14 @@ int64_t aln_batch_device_bytes(const aln_batch* b);
  * Asynchronous on the ctx stream.  bug_b4 != 0 reproduces dpmatrix.h:868 in reverse global builds. */
 int aln_batch_dp(aln_batch* b, const aln_sim* sim, const aln_gap* gap,
                  int32_t direction, int32_t algo, int32_t bug_b4);
-/* DPMatrix::reevaluate (dpmatrix.h:213-218): rebuild with the parameters of the last aln_batch_dp. */
+/* DPMatrix::reevaluate (dpmatrix.h:213-218): rebuild with the parameters of the last aln_batch_dp.
+ * Lean rebuilds: when the build being replaced was used by the Optimal family (aln_batch_optimal, _enqueue, _strings*) and by
+ * nothing that reads scores (aln_batch_get_cells, aln_batch_enumerate*), and the launch is the 2048-column local tagged kernel
+ * (16-bit keys), the rebuild writes 2 B/cell: pointer words whose bit 15 says "score > 0" and, of the score plane, only what the
+ * final cell needs.  Optimal gives the same scores, lists and status on it.  The first other reader of the planes runs the full
+ * build again on the batch's stream (one more DP launch, counted in aln_batch_dp_ms_history) and the reevaluate after it is
+ * full; results already enqueued stay valid.  Context hint "lean_reevaluate" (ALN_LEAN_REEVALUATE): 0 never, 1 this rule
+ * (default), 2 every eligible reevaluate.  aln_batch_dp and aln_batch_dp_sub are always full. */
 int aln_batch_reevaluate(aln_batch* b);
 /* Replace the gap description of the resident batch (constants, per-position arrays, deletion / insertion tables are uploaded
  * again; the similarity source stays resident); the next aln_batch_reevaluate builds with it.  The engine-side half of the
@@ -255,7 +262,8 @@ int aln_batch_dp_sub(aln_batch* b, const aln_sim* sim, const aln_gap* gap,
                      int32_t direction, const int32_t* bounds);
 
 /* DPMatrix::getCell for a whole pair (dpmatrix.h:230-232): score, prev_query_idx, prev_template_idx
- * planes, Q x T row-major, untouched cells read 0 / -1 / -1 (dpmatrix.cpp:17-25).  Any pointer may be NULL. */
+ * planes, Q x T row-major, untouched cells read 0 / -1 / -1 (dpmatrix.cpp:17-25).  Any pointer may be NULL.
+ * After a lean aln_batch_reevaluate this first rebuilds the full planes (see there): the values are those of a full build. */
 int aln_batch_get_cells(aln_batch* b, int32_t pair, float* score, int32_t* prev_q, int32_t* prev_t);
 /* DPMatrix::getSim (dpmatrix.h:72-73) for a whole pair. */
 int aln_batch_get_sim(aln_batch* b, int32_t pair, float* sim);
@@ -511,7 +519,8 @@ int aln_batch_dp_ms_history(aln_batch* b, float* ms, int32_t max_n);
 /* Bytes one DP launch MUST write to HBM with the plane layout the last aln_batch_dp chose: per cell of the Q x T matrices
  * the score element (fp32, or uint16 in local tagged builds) + the pointer element (32-bit, or 16-bit tagged words):
  * 8, 6 or 4 B/cell.  This is what a roofline fraction is computed from.  _contract_bytes is SURVEY.md 8(d)'s figure for the
- * reference's layout, 8 B per cell (fp32 score + 32-bit packed pointer), whatever was chosen; _plane_bytes_per_cell the factor. */
+ * reference's layout, 8 B per cell (fp32 score + 32-bit packed pointer), whatever was chosen; _plane_bytes_per_cell the factor.
+ * While the resident planes are those of a lean aln_batch_reevaluate the factor is 2 (flagged pointer words only). */
 int64_t aln_batch_dp_algorithmic_bytes(const aln_batch* b);
 int64_t aln_batch_dp_contract_bytes(const aln_batch* b);
 int32_t aln_batch_plane_bytes_per_cell(const aln_batch* b);

@@ -11,7 +11,9 @@ shapes = []
 for spec in sys.argv[1:]:
     tag, pairs, kernel = spec.split(":", 2)
     summ = json.load(open("profiles/%s_pmc_summary.json" % tag))
-    occ = ", 3>" if "occ3" in kernel else ", 2>"          # the template's last parameter = waves per SIMD it was compiled for
+    # the template's last parameters = waves per SIMD it was compiled for, then LEAN (profiles from before the lean build lack it)
+    o = "3" if "occ3" in kernel else "2"
+    occ = (", %s, true>" % o,) if ",lean" in kernel else (", %s>" % o, ", %s, false>" % o)
     name, k = max(((n, v) for n, v in summ["kernels"].items() if "dp_affine_tag_kernel" in n and n.endswith(occ) and "WRITE_SIZE" in v),
                   key=lambda nv: nv[1]["WRITE_SIZE"]["mean"])
     w = k["WRITE_SIZE"]["mean"] * 1024.0
