@@ -10,11 +10,11 @@ import pytest
 import aln_amd
 import gpu_util
 import orc
+from lean_cases import SHAPES, VARIANT, assert_full, assert_lean, same_optimal
 from aln_amd.synth import MT19937, homolog_pair, residues
 
 pytestmark = pytest.mark.gpu
 
-VARIANT = dict(dp_variant_nw=2, dp_variant_r=2, dp_variant_x=8)
 LOCAL = aln_amd.LOCAL
 _ORACLE = {}
 
@@ -49,10 +49,8 @@ def make_pair(seed, qlen, tlen, at_end):
     return "".join(q), t
 
 
-# (residues of the query, T = template residues + 2): column T-2 is 296 / 303 (inside group 0 of wave 0, first / last cell of a
-# lane's chunk), 511 | 512 (groups 0 | 1 of wave 0), 1023 | 1024 (wave 0 | wave 1, whose first column the exchange delivers),
-# 1535 | 1536 (groups of wave 1), 2046 (the last lane of all)
-SHAPES = [(0, 5), (1, 298), (2, 305), (40, 298), (7, 513), (33, 514), (17, 1025), (40, 1026), (25, 1537), (3, 1538), (40, 2048), (0, 2048)]
+# SHAPES (tests/lean_cases.py): column T-2 in every (wave, group) of the layout and on their edges.  The sequences of this file are
+# its own (make_pair below draws them from MT19937; lean_cases.make_pair gives the same shapes a weak head instead)
 
 
 def shape_pairs():
@@ -66,29 +64,11 @@ def lean_name_ok(name, full_name):
     return "lean" in name and name.replace(",lean", "") == full_name
 
 
-def assert_lean(b):
-    assert "lean" in b.kernel_name(), b.kernel_name()
-    assert b.plane_bytes_per_cell() == 2
-
-
-def assert_full(b, bytes_per_cell=4):
-    assert "lean" not in b.kernel_name(), b.kernel_name()
-    assert b.plane_bytes_per_cell() == bytes_per_cell
-
-
 def new_batch(pairs, blosum62, gi=11, ge=1, mode=LOCAL):
     alpha, table = blosum62
     b = aln_amd.Batch(gpu_util.ctx(), [p[0] for p in pairs], [p[1] for p in pairs])
     b.dp_submatrix(alpha, table, mode, gi, ge)
     return b
-
-
-def same_optimal(got, want):
-    assert np.array_equal(got[0].view(np.uint32), want[0].view(np.uint32))
-    assert np.array_equal(got[2], want[2])
-    assert len(got[1]) == len(want[1])
-    for a, c in zip(got[1], want[1]):
-        assert np.array_equal(a, c)
 
 
 def check_against_oracle(blosum62, pairs, res, gi=11, ge=1):
