@@ -4,7 +4,6 @@ The reference of every sum is the dense path: the shuffled strings come from aln
 from aln_amd.score_all_vs_all against the templates, the sums are taken over Python integers; `sum`, `sumsq` and `n` are
 compared for equality and `z` bit for bit with a Python restatement of the header's formula."""
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ import pytest
 import aln_amd
 import gpu_util
 from aln_amd.synth import MT19937, homolog_pair, residues
+from search_cases import z_restated
 
 pytestmark = pytest.mark.gpu
 
@@ -55,16 +55,6 @@ def background(key, q_index, q, ts, blosum62, n, seed=SEED, mode=aln_amd.LOCAL, 
         d.setflags(write=False)
         _REF[k] = d
     return _REF[k][:n]
-
-
-def z_restated(n, score, s, ss):
-    if n < 2:
-        return np.float32(0.0)
-    D = n * ss - s * s
-    if D == 0:
-        return np.float32(0.0)
-    N = n * int(score) - s
-    return np.float32(float(N) * math.sqrt(float(n - 1) / (float(n) * float(D))))
 
 
 def check_stats(stats, hits, n_hits, ref_of_row, n):
