@@ -36,6 +36,10 @@ class AlnSubmatrix(C.Structure):
     _fields_ = [("n", C.c_int32), ("alphabet", C.c_char_p), ("table", _fp)]
 
 
+class AlnQProfiles(C.Structure):
+    _fields_ = [("n_seqs", C.c_int32), ("offsets", _lp), ("rows", _fp), ("n", C.c_int32), ("alphabet", C.c_char_p)]
+
+
 class AlnProfiles(C.Structure):
     _fields_ = [("aa", _fp), ("sse", _fp), ("conf", _fp)]
 
@@ -90,7 +94,7 @@ EXPORTS = [
     "aln_batch_optimal_strings", "aln_batch_optimal_strings_enqueue", "aln_batch_optimal_strings_collect", "aln_batch_last_exact_stats", "aln_batch_set_gap", "aln_ctx_set_hint", "aln_ctx_get_hint", "aln_batch_dp_contract_bytes", "aln_batch_plane_bytes_per_cell",
     "aln_deal_units", "aln_comm_unique_id", "aln_comm_create", "aln_ctx_create_multi", "aln_comm_destroy", "aln_comm_n_ranks",
     "aln_comm_last_error", "aln_gather_scores", "aln_gather_resident_enqueue", "aln_gather_resident_collect", "aln_search_topk",
-    "aln_hits_zscores", "aln_hits_align", "aln_hits_align_last_routes",
+    "aln_hits_zscores", "aln_hits_align", "aln_hits_align_last_routes", "aln_score_profiles_vs_all", "aln_search_topk_profiles",
 ]
 COMM_ID_BYTES = 128
 
@@ -156,6 +160,10 @@ def lib():
                                            C.c_int32, C.c_int32, _fp]
         L.aln_search_topk.argtypes = [C.c_void_p, C.POINTER(AlnSeqs), C.POINTER(AlnSeqs), C.POINTER(AlnSubmatrix), C.POINTER(AlnGap),
                                       C.c_int32, C.c_int32, C.c_int32, C.c_float, C.POINTER(AlnHit), _ip]
+        L.aln_score_profiles_vs_all.argtypes = [C.c_void_p, C.POINTER(AlnQProfiles), C.POINTER(AlnSeqs), C.POINTER(AlnGap), C.c_int32, C.c_int32,
+                                                _fp]
+        L.aln_search_topk_profiles.argtypes = [C.c_void_p, C.POINTER(AlnQProfiles), C.POINTER(AlnSeqs), C.POINTER(AlnGap), C.c_int32, C.c_int32,
+                                               C.c_int32, C.c_float, C.POINTER(AlnHit), _ip]
         L.aln_hits_zscores.argtypes = [C.c_void_p, C.POINTER(AlnSeqs), C.POINTER(AlnSeqs), C.POINTER(AlnSubmatrix), C.POINTER(AlnGap),
                                        C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.c_int32, C.c_uint32,
                                        C.POINTER(AlnHitStats)]
@@ -298,6 +306,81 @@ def search_topk(ctx, queries, templates, alphabet, table, gi, ge, K, min_score=-
     n_hits = np.zeros(rows, dtype=np.int32)
     _check(lib().aln_search_topk(ctx.h, C.byref(qpool.c), C.byref(tpool.c), C.byref(sub), C.byref(g), q_begin, q_end, int(K),
                                  float(min_score), hits.ctypes.data_as(C.POINTER(AlnHit)), _i(n_hits)), ctx.h)
+    return hits, n_hits
+
+
+class QueryProfiles:
+    """A pool of position-specific queries (aln_qprofiles).  Each entry is an L x n array — row i holds the similarity of query
+    position i and every letter of `alphabet`, the TEMPLATES' alphabet — given WITHOUT sentinels and stored with a zero row in
+    front and behind, as SeqPool stores '^' + s + '$'."""
+
+    def __init__(self, profiles, alphabet):
+        n = len(alphabet)
+        self.alphabet = alphabet
+        self.profiles = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1, n) for p in profiles]
+        self.offsets = np.zeros(len(self.profiles) + 1, dtype=np.int64)
+        np.cumsum([len(p) + 2 for p in self.profiles], out=self.offsets[1:])
+        self.rows = np.zeros((int(self.offsets[-1]), n), dtype=np.float32)
+        for k, p in enumerate(self.profiles):
+            self.rows[self.offsets[k] + 1:self.offsets[k + 1] - 1] = p
+        self._ab = alphabet.encode()
+        self.c = AlnQProfiles(len(self.profiles), self.offsets.ctypes.data_as(_lp), _f(self.rows), n, self._ab)
+
+    def __len__(self):
+        return len(self.profiles)
+
+
+def profiles_from_sequences(seqs, alphabet, table):
+    """The profiles that score like the residue strings `seqs` under `table`: row i is the table row of residue i."""
+    tab = np.asarray(table, dtype=np.float32).reshape(len(alphabet), len(alphabet))
+    idx = {ch: k for k, ch in enumerate(alphabet)}
+    return QueryProfiles([tab[[idx[ch] for ch in s]].reshape(len(s), len(alphabet)) for s in seqs], alphabet)
+
+
+def profile_planes(profile, template, alphabet):
+    """The (L + 2) x (T + 2) float32 similarity plane of one profile (L x n, no sentinel rows) against one template (a string,
+    no sentinels): what Batch.dp_simmatrix takes for the pair.  A hit of a profile search is aligned through a resident batch
+    with it; the batch's query residues are placeholders (any string of L letters)."""
+    prof = np.asarray(profile, dtype=np.float32).reshape(-1, len(alphabet))
+    idx = {ch: k for k, ch in enumerate(alphabet)}
+    S = np.zeros((len(prof) + 2, len(template) + 2), dtype=np.float32)
+    if len(prof) and len(template):
+        S[1:-1, 1:-1] = prof[:, [idx[ch] for ch in template]]
+    return S
+
+
+def _const_gap(align_type, gi, ge):
+    g = AlnGap()
+    g.model = GAP_AFFINE_CONST
+    g.align_type = int(align_type)
+    g.gap_init = float(np.float32(gi))
+    g.gap_extn = float(np.float32(ge))
+    return g
+
+
+def score_profiles_vs_all(ctx, profiles, templates, gi, ge, q_begin=0, q_end=None, align_type=LOCAL):
+    """aln_score_profiles_vs_all: the score Optimal(align_type) reports for profiles[q_begin:q_end] (a QueryProfiles) against
+    every template, no planes -> float32 [rows, n_templates]."""
+    tpool = templates if isinstance(templates, SeqPool) else SeqPool(templates)
+    if q_end is None:
+        q_end = len(profiles)
+    g = _const_gap(align_type, gi, ge)
+    out = np.empty((q_end - q_begin, len(tpool.seqs)), dtype=np.float32)
+    _check(lib().aln_score_profiles_vs_all(ctx.h, C.byref(profiles.c), C.byref(tpool.c), C.byref(g), q_begin, q_end, _f(out)), ctx.h)
+    return out
+
+
+def search_topk_profiles(ctx, profiles, templates, gi, ge, K, min_score=-np.inf, q_begin=0, q_end=None, align_type=LOCAL):
+    """aln_search_topk_profiles: search_topk for position-specific queries (a QueryProfiles) -> hits[rows, K], n_hits[rows]."""
+    tpool = templates if isinstance(templates, SeqPool) else SeqPool(templates)
+    if q_end is None:
+        q_end = len(profiles)
+    g = _const_gap(align_type, gi, ge)
+    rows = max(q_end - q_begin, 0)
+    hits = np.zeros((rows, max(int(K), 0)), dtype=HIT_DTYPE)
+    n_hits = np.zeros(rows, dtype=np.int32)
+    _check(lib().aln_search_topk_profiles(ctx.h, C.byref(profiles.c), C.byref(tpool.c), C.byref(g), q_begin, q_end, int(K),
+                                          float(min_score), hits.ctypes.data_as(C.POINTER(AlnHit)), _i(n_hits)), ctx.h)
     return hits, n_hits
 
 

@@ -4,6 +4,7 @@
 // steps so that a caller can leave the scores of a slab of query rows in a device buffer of its own.
 #pragma once
 #include <deque>
+#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -12,7 +13,8 @@
 namespace aln {
 
 struct ScoreArgs {
-  const uint8_t* qcodes; const int64_t* qoff;   // query pool, offsets (n_q + 1)
+  const uint8_t* qcodes; const int64_t* qoff;   // query pool, offsets (n_q + 1); profile kernels: the device rows, 128 bytes each,
+                                                // biased so that pool row r starts at qcodes + 128 r, and offsets in rows
   const uint8_t* tcodes; const int64_t* toff;   // template pool
   const int32_t* table32;                       // 32 x 32
   const int32_t* tsel;                          // blockIdx.x -> template index (templates are launched by length class)
@@ -53,14 +55,42 @@ __global__ __launch_bounds__(256) void class_list_kernel(ClassOf cls_of, int n_s
   if (cls >= 0) list[lb[cls] + my] = h;
 }
 
+// What Optimal::find_max (optimal.h:108-124) needs of a local sweep (score_local_end_kernel, search_topk.hip, tells how it is
+// reduced): per lane the row at which the running maximum last strictly improved and — inside that rare branch — the smallest
+// of the lane's columns holding it.
+struct FirstMaxObserver : NoObserver {
+  int seen = 0, lrow = 0, lcol = 0;
+  // the lane's maximum rose in row i exactly when row i's maximum exceeds the old one, and then equals it
+  template <int R>
+  __device__ __forceinline__ void row(int i, const int (&d)[R][4], int lane_max) {
+    if (lane_max > seen) {
+      seen = lane_max; lrow = i;
+#pragma unroll
+      for (int r = R - 1; r >= 0; --r)
+#pragma unroll
+        for (int x = 3; x >= 0; --x) lcol = (d[r][x] == lane_max) ? 4 * (int)threadIdx.x + 256 * r + x : lcol;
+    }
+  }
+};
+
+// score_profile.hip: the profile twins of score_local_kernel / score_global_kernel for the templates of class r (grid: templates
+// of the class x query rows), and of score_local_end_kernel for the n hit slots of `list`
+void launch_score_prof(int r, bool local, dim3 grid, hipStream_t stream, const ScoreArgs& s, int free_del, int free_ins);
+void launch_score_local_end_prof(int r, int n, hipStream_t stream, const ScoreArgs& s, const int32_t* list, aln_hit* hits, int K);
+
 // One all-vs-all scoring call (the arguments of aln_score_all_vs_all): prepare() checks them and decides the route, upload()
 // puts what the register-resident kernels read on the device, launch() enqueues those kernels for a block of query rows
 // into a device buffer of the caller.  Nothing here synchronises; the object must outlive the stream work it enqueued.
+// The query side is either a residue pool scored through `sub` or a pool of position-specific profiles (aln_qprofiles: `prof`
+// set, no `sub`).  For profiles `queries` is a placeholder pool the run makes itself — the profiles' offsets, every interior
+// residue alphabet[0] — so that lengths are read in one place and the full-build route has residues to create batches with.
 struct ScoreRun {
   enum Route { kNothing, kAllFull, kFast };
   aln_ctx* ctx = nullptr;
   const aln_seqs* queries = nullptr; const aln_seqs* templates = nullptr;
   const aln_submatrix* sub = nullptr; const aln_gap* gap = nullptr;
+  const aln_qprofiles* prof = nullptr;          // the query side is profiles
+  std::string ph_res; aln_seqs ph = {};         // ... and their placeholder pool
   int32_t q_begin = 0, q_end = 0;
   int rows = 0, n_t = 0;
   bool local = false, packed = false;
@@ -77,13 +107,18 @@ struct ScoreRun {
   ScoreArgs a = {};
   uint8_t *dq = nullptr, *dt = nullptr; int64_t *dqo = nullptr, *dto = nullptr; int32_t* dtab = nullptr;
   int32_t *dsel = nullptr, *dqsel = nullptr;
+  int32_t* dprows = nullptr; size_t dprows_bytes = 0;   // profiles: the resident rows, 32 int32 each (upload_profile_rows)
+  std::vector<int32_t> hrows;                   // ... their host image, alive until the caller has synchronised
+  bool rows_per_slab = false;                   // profiles: launch() uploads the rows of its own block (set before upload())
   std::deque<std::vector<int32_t>> qorders;     // the packed kernel's length orders: alive until the caller has synchronised
 
   // the argument checks of aln_score_all_vs_all, in its order; ALN_OK with route == kNothing: no pair to score
+  // (profiles: queries and sub NULL; the checks of aln_score_profiles_vs_all, in its order)
   int prepare(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub, const aln_gap* gap,
-              int32_t q_begin, int32_t q_end);
+              int32_t q_begin, int32_t q_end, const aln_qprofiles* prof = nullptr);
   int upload_offsets();                         // qoff / toff only (all a caller of the kAllFull route needs on the device)
-  int upload();                                 // kFast: residue codes, offsets, table, class order
+  int upload();                                 // kFast: residue codes (or profile rows), offsets, table, class order
+  int upload_profile_rows(int32_t qa, int32_t qb);   // kFast, profiles: the rows of profiles [qa, qb) become the resident ones
   // kFast: scores of query rows [q_begin + row0, q_begin + row0 + nr) against the templates of `order` -> dscores[nr x n_t]
   int launch(int row0, int nr, float* dscores);
   void release();
@@ -91,9 +126,22 @@ struct ScoreRun {
 };
 
 // scores[(q - q_begin) * ld + col[t]] for the templates of `tlist` through resident batches of full builds
-// (col == nullptr: column t, ld == 0: n_t — the layout of aln_score_all_vs_all's result)
+// (col == nullptr: column t, ld == 0: n_t — the layout of aln_score_all_vs_all's result).  prof != nullptr: `queries` is the
+// profiles' placeholder pool, `sub` is not read and every batch is built from ALN_SIM_MATRIX planes expanded on the host.
 int score_through_batches(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
                           const aln_gap* gap, int32_t q_begin, int32_t q_end, const std::vector<int32_t>& tlist, float* scores,
-                          const int32_t* col = nullptr, size_t ld = 0);
+                          const int32_t* col = nullptr, size_t ld = 0, const aln_qprofiles* prof = nullptr);
+
+// The similarity source of one resident batch of the full-build route: the table, or (prof != nullptr) the Q x T planes of the
+// batch's pairs expanded on the host — S[i][j] = rows[(off + i) * n + index(t[j])] inside, 0 on the sentinel rows and columns.
+// The object owns the planes and must outlive the aln_batch_dp call that reads `sim`.
+struct BatchSim {
+  aln_sim sim = aln_sim();
+  std::vector<float> planes; std::vector<int64_t> plane_off;
+  void set(const aln_submatrix* sub, const aln_qprofiles* prof, const aln_seqs* templates, size_t n_pairs, const int32_t* qi,
+           const int32_t* ti);
+};
+// bytes of planes a Q x T pair of such a batch holds on the device (score + pointer planes, padded rows; + the similarity plane)
+inline size_t batch_pair_bytes(size_t Q, size_t T, bool with_sim_plane) { return Q * (T + 16) * (with_sim_plane ? 12 : 8); }
 
 }  // namespace aln

@@ -237,20 +237,19 @@ __global__ __launch_bounds__(64) void score_local_pk_kernel(ScoreArgs a, int n_r
 // or gaps.  Pairs are grouped so that one group's planes stay below ~12 GB.
 int score_through_batches(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
                           const aln_gap* gap, int32_t q_begin, int32_t q_end, const std::vector<int32_t>& tlist, float* scores,
-                          const int32_t* col, size_t ld) {
+                          const int32_t* col, size_t ld, const aln_qprofiles* prof) {
   if (ld == 0) ld = (size_t)templates->n_seqs;
   const size_t budget = (size_t)12 << 30;
-  aln_sim sim = aln_sim();
-  sim.kind = ALN_SIM_SUBMATRIX;
-  sim.sub = *sub;
   std::vector<int32_t> qi, tix;
   std::vector<float> sc;
   std::vector<int32_t> st;
   auto flush = [&]() -> int {
     if (qi.empty()) return ALN_OK;
     aln_batch* bb = nullptr;
+    BatchSim bs;
+    bs.set(sub, prof, templates, qi.size(), qi.data(), tix.data());
     int rc = aln_batch_create(ctx, queries, templates, (int32_t)qi.size(), qi.data(), tix.data(), 0, &bb);
-    if (rc == ALN_OK) rc = aln_batch_dp(bb, &sim, gap, ALN_FWD, ALN_DP_AUTO, 0);
+    if (rc == ALN_OK) rc = aln_batch_dp(bb, &bs.sim, gap, ALN_FWD, ALN_DP_AUTO, 0);
     sc.resize(qi.size()); st.resize(qi.size());
     if (rc == ALN_OK) rc = aln_batch_optimal(bb, sc.data(), nullptr, nullptr, 0, st.data());
     if (bb) aln_batch_destroy(bb);
@@ -267,7 +266,7 @@ int score_through_batches(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs*
     const size_t T = (size_t)(templates->offsets[t + 1] - templates->offsets[t]);
     for (int32_t q = q_begin; q < q_end; ++q) {
       const size_t Q = (size_t)(queries->offsets[q + 1] - queries->offsets[q]);
-      const size_t need = Q * (T + 16) * 8;
+      const size_t need = batch_pair_bytes(Q, T, prof != nullptr);
       if (!qi.empty() && bytes + need > budget) { int rc = flush(); if (rc) return rc; bytes = 0; }
       qi.push_back(q); tix.push_back(t); bytes += need;
     }
@@ -275,17 +274,51 @@ int score_through_batches(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs*
   return flush();
 }
 
+void BatchSim::set(const aln_submatrix* sub, const aln_qprofiles* prof, const aln_seqs* templates, size_t n_pairs,
+                   const int32_t* qi, const int32_t* ti) {
+  if (!prof) { sim.kind = ALN_SIM_SUBMATRIX; sim.sub = *sub; return; }
+  int idx[256];
+  for (int i = 0; i < 256; ++i) idx[i] = -1;
+  for (int i = 0; i < prof->n; ++i) idx[(unsigned char)prof->alphabet[i]] = i;
+  plane_off.assign(n_pairs + 1, 0);
+  for (size_t p = 0; p < n_pairs; ++p) {
+    const int64_t Q = prof->offsets[qi[p] + 1] - prof->offsets[qi[p]], T = templates->offsets[ti[p] + 1] - templates->offsets[ti[p]];
+    plane_off[p + 1] = plane_off[p] + Q * T;
+  }
+  planes.assign((size_t)plane_off[n_pairs], 0.f);
+  for (size_t p = 0; p < n_pairs; ++p) {
+    const int64_t off = prof->offsets[qi[p]], Q = prof->offsets[qi[p] + 1] - off;
+    const int64_t t0 = templates->offsets[ti[p]], T = templates->offsets[ti[p] + 1] - t0;
+    float* S = planes.data() + plane_off[p];
+    for (int64_t i = 1; i <= Q - 2; ++i) {
+      const float* row = prof->rows + (size_t)(off + i) * prof->n;
+      for (int64_t j = 1; j <= T - 2; ++j) S[i * T + j] = row[idx[(unsigned char)templates->residues[t0 + j]]];   // checked by prepare()
+    }
+  }
+  sim.kind = ALN_SIM_MATRIX;
+  sim.planes = planes.data();
+  sim.plane_off = plane_off.data();
+}
+
 int ScoreRun::prepare(aln_ctx* ctx_, const aln_seqs* queries_, const aln_seqs* templates_, const aln_submatrix* sub_,
-                      const aln_gap* gap_, int32_t q_begin_, int32_t q_end_) {
-  ctx = ctx_; queries = queries_; templates = templates_; sub = sub_; gap = gap_; q_begin = q_begin_; q_end = q_end_;
+                      const aln_gap* gap_, int32_t q_begin_, int32_t q_end_, const aln_qprofiles* prof_) {
+  ctx = ctx_; queries = queries_; templates = templates_; sub = sub_; gap = gap_; q_begin = q_begin_; q_end = q_end_; prof = prof_;
   route = kNothing;
-  if (!ctx || !queries || !templates || !sub || !gap) return ALN_E_ARG;
-  if (q_begin < 0 || q_end > queries->n_seqs || q_begin > q_end) return ALN_E_ARG;
+  if (!ctx || !templates || !gap || (prof ? false : (!queries || !sub))) return ALN_E_ARG;
+  if (q_begin < 0 || q_end > (prof ? prof->n_seqs : queries->n_seqs) || q_begin > q_end) return ALN_E_ARG;
   if (gap->model != ALN_GAP_AFFINE_CONST || gap->align_type < 0 || gap->align_type > 4) return ALN_E_ARG;
   local = gap->align_type == ALN_LOCAL;
   free_del = (gap->align_type == ALN_LOCAL || gap->align_type == ALN_SEMI_LOCAL || gap->align_type == ALN_LOCAL_GLOBAL);
   free_ins = (gap->align_type == ALN_LOCAL || gap->align_type == ALN_SEMI_LOCAL || gap->align_type == ALN_GLOBAL_LOCAL);
-  if (!sub->alphabet || !sub->table || sub->n < 1 || sub->n > 30) return ALN_E_ARG;
+  if (prof) {
+    if (prof->n < 1 || prof->n > 30 || !prof->alphabet || !prof->rows || !prof->offsets || prof->n_seqs < 0) return ALN_E_ARG;
+    for (int s = 0; s < prof->n_seqs; ++s)
+      if (prof->offsets[s + 1] - prof->offsets[s] < 2) return ALN_E_ARG;
+    ph_res.assign((size_t)prof->offsets[prof->n_seqs], prof->alphabet[0]);
+    for (int s = 0; s < prof->n_seqs; ++s) { ph_res[(size_t)prof->offsets[s]] = '^'; ph_res[(size_t)prof->offsets[s + 1] - 1] = '$'; }
+    ph.n_seqs = prof->n_seqs; ph.offsets = prof->offsets; ph.residues = ph_res.data();
+    queries = &ph;
+  } else if (!sub->alphabet || !sub->table || sub->n < 1 || sub->n > 30) return ALN_E_ARG;
   ALN_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const float gi = gap->gap_init, ge = gap->gap_extn;
   rows = q_end - q_begin; n_t = templates->n_seqs;
@@ -293,19 +326,33 @@ int ScoreRun::prepare(aln_ctx* ctx_, const aln_seqs* queries_, const aln_seqs* t
   for (int t = 0; t < n_t; ++t) every_t[t] = t;
   if (q_begin == q_end || n_t == 0) return ALN_OK;
   // fractional gaps or table values: full builds in the exact-order kernels (the reference's arithmetic), batch by batch
-  if (!(gi == (float)(int)gi) || !(ge == (float)(int)ge) || gi < 0 || ge < 0) { route = kAllFull; return ALN_OK; }
+  // (a profile run first finishes its checks: no batch would look at the templates' letters for it)
+  bool integral = (gi == (float)(int)gi) && (ge == (float)(int)ge) && gi >= 0 && ge >= 0;
+  if (!integral && !prof) { route = kAllFull; return ALN_OK; }
+  const int n_alpha = prof ? prof->n : sub->n;
+  const char* alphabet = prof ? prof->alphabet : sub->alphabet;
   int idx[256];
   for (int i = 0; i < 256; ++i) idx[i] = -1;
-  for (int i = 0; i < sub->n; ++i) idx[(unsigned char)sub->alphabet[i]] = i;
+  for (int i = 0; i < n_alpha; ++i) idx[(unsigned char)alphabet[i]] = i;
   maxs = 0;
   for (int i = 0; i < 32 * 32; ++i) ti[i] = 0;
-  for (int i = 0; i < sub->n; ++i)
-    for (int j = 0; j < sub->n; ++j) {
-      float v = sub->table[i * sub->n + j];
-      if (!(v == (float)(int)v)) { route = kAllFull; return ALN_OK; }
-      ti[i * 32 + j] = (int32_t)v;
-      maxs = std::max(maxs, fabs((double)v));
-    }
+  if (prof) {
+    // maxs over the interior rows of the whole pool (a sentinel row's values are never read)
+    for (int s = 0; s < prof->n_seqs && integral; ++s)
+      for (int64_t k = (prof->offsets[s] + 1) * prof->n; k < (prof->offsets[s + 1] - 1) * prof->n; ++k) {
+        const float v = prof->rows[k];
+        if (!(v == (float)(int)v)) { integral = false; break; }
+        maxs = std::max(maxs, fabs((double)v));
+      }
+  } else {
+    for (int i = 0; i < sub->n; ++i)
+      for (int j = 0; j < sub->n; ++j) {
+        float v = sub->table[i * sub->n + j];
+        if (!(v == (float)(int)v)) { route = kAllFull; return ALN_OK; }
+        ti[i * 32 + j] = (int32_t)v;
+        maxs = std::max(maxs, fabs((double)v));
+      }
+  }
   auto encode = [&](const aln_seqs* s, std::vector<uint8_t>& codes, int& maxlen) -> int {
     const int64_t total = s->offsets[s->n_seqs];
     codes.resize((size_t)total);
@@ -327,6 +374,7 @@ int ScoreRun::prepare(aln_ctx* ctx_, const aln_seqs* queries_, const aln_seqs* t
   if ((rc = encode(queries, qc, maxQ)) != ALN_OK) return rc;
   if ((rc = encode(templates, tc, maxT)) != ALN_OK) return rc;
   if (maxT > kMaxLen || maxQ > kMaxLen) return ALN_E_TOO_LONG;
+  if (!integral) { route = kAllFull; return ALN_OK; }              // profiles: a fractional entry or gap
   if ((maxs + ge) * ((double)maxQ + std::min(maxT, 2048)) + gi + maxs >= 8388608.0) { route = kAllFull; return ALN_OK; }
   route = kFast;
   // Templates are launched by length class: a wave sweeps 256 R columns, so a template of T columns needs
@@ -346,13 +394,13 @@ int ScoreRun::prepare(aln_ctx* ctx_, const aln_seqs* queries_, const aln_seqs* t
   // A keys add ge * column, the "minus infinity" -12000 must stay below every real candidate and clear of wrap-around
   const int fastT = std::min(maxT, 2048);                // (longer templates do not run in these kernels)
   const double L = (double)std::max(maxQ, fastT), best = maxs * (double)std::min(maxQ, fastT);
-  packed = local && best + ge * L + maxs < 30000.0 && ge * L + gi + maxs < 8000.0 && maxs < 2048.0 && ctx->hints.score_packed;
+  packed = !prof && local && best + ge * L + maxs < 30000.0 && ge * L + gi + maxs < 8000.0 && maxs < 2048.0 && ctx->hints.score_packed;
   return ALN_OK;
 }
 
 void ScoreRun::release() {
-  hipFree(dq); hipFree(dt); hipFree(dqo); hipFree(dto); hipFree(dtab); hipFree(dsel); hipFree(dqsel);
-  dq = dt = nullptr; dqo = dto = nullptr; dtab = dsel = dqsel = nullptr;
+  hipFree(dq); hipFree(dt); hipFree(dqo); hipFree(dto); hipFree(dtab); hipFree(dsel); hipFree(dqsel); hipFree(dprows);
+  dq = dt = nullptr; dqo = dto = nullptr; dtab = dsel = dqsel = nullptr; dprows = nullptr; dprows_bytes = 0;
 }
 
 #define STRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(e_); hipStreamSynchronize(ctx->stream); release(); return ALN_E_HIP; } } while (0)
@@ -364,15 +412,39 @@ int ScoreRun::upload_offsets() {
   return ALN_OK;
 }
 
+// Profiles: rows [offsets[qa], offsets[qb]) of the pool, widened to 32 int32 (letters n .. 31 and both sentinel rows 0), 128-byte
+// aligned (hipMalloc's alignment, 128 bytes per row).  INVARIANT: the allocation ends kProfilePadRows rows (zeros) behind the last
+// row — a sweep requests the 8-row chunks its rows 1 .. Q-2 lie in plus the one after (ProfileRows, score_sweep.h), i.e. at most
+// rows .. Q + 13 of its profile, of which the last profile's reach past the pool's end.
+int ScoreRun::upload_profile_rows(int32_t qa, int32_t qb) {
+  const int64_t r0 = prof->offsets[qa], r1 = prof->offsets[qb];
+  const size_t n_rows = (size_t)(r1 - r0) + kProfilePadRows;
+  if (n_rows * 128 > dprows_bytes) {
+    hipFree(dprows); dprows = nullptr; dprows_bytes = 0;
+    STRY(hipMalloc((void**)&dprows, n_rows * 128));
+    dprows_bytes = n_rows * 128;
+  }
+  hrows.assign(n_rows * 32, 0);
+  for (int32_t s = qa; s < qb; ++s)
+    for (int64_t r = prof->offsets[s] + 1; r < prof->offsets[s + 1] - 1; ++r)
+      for (int k = 0; k < prof->n; ++k) hrows[(size_t)(r - r0) * 32 + k] = (int32_t)prof->rows[(size_t)r * prof->n + k];
+  STRY(hipMemcpyAsync(dprows, hrows.data(), n_rows * 128, hipMemcpyHostToDevice, ctx->stream));
+  a.qcodes = reinterpret_cast<const uint8_t*>(dprows) - r0 * 128;
+  return ALN_OK;
+}
+
 int ScoreRun::upload() {
-  STRY(hipMalloc((void**)&dq, qc.size())); STRY(hipMalloc((void**)&dt, tc.size()));
-  STRY(hipMalloc((void**)&dtab, sizeof ti));
-  STRY(hipMemcpyAsync(dq, qc.data(), qc.size(), hipMemcpyHostToDevice, ctx->stream));
+  STRY(hipMalloc((void**)&dt, tc.size()));
+  if (!prof) {
+    STRY(hipMalloc((void**)&dq, qc.size())); STRY(hipMalloc((void**)&dtab, sizeof ti));
+    STRY(hipMemcpyAsync(dq, qc.data(), qc.size(), hipMemcpyHostToDevice, ctx->stream));
+  }
   STRY(hipMemcpyAsync(dt, tc.data(), tc.size(), hipMemcpyHostToDevice, ctx->stream));
   int rc = upload_offsets();
   if (rc != ALN_OK) return rc;
-  STRY(hipMemcpyAsync(dtab, ti, sizeof ti, hipMemcpyHostToDevice, ctx->stream));
+  if (!prof) STRY(hipMemcpyAsync(dtab, ti, sizeof ti, hipMemcpyHostToDevice, ctx->stream));
   a.qcodes = dq; a.qoff = dqo; a.tcodes = dt; a.toff = dto; a.table32 = dtab;
+  if (prof && !rows_per_slab && (rc = upload_profile_rows(q_begin, q_end)) != ALN_OK) return rc;
   a.q_begin = q_begin; a.n_t = n_t; a.gi = (int)gap->gap_init; a.ge = (int)gap->gap_extn;
   STRY(hipMalloc((void**)&dsel, (size_t)n_t * 4));
   if (!order.empty()) STRY(hipMemcpyAsync(dsel, order.data(), order.size() * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -400,6 +472,10 @@ int ScoreRun::launch(int row0, int nrows, float* dscores) {
     }
     STRY(hipMemcpyAsync(dqsel + row0, qo_all.data(), (size_t)nrows * 4, hipMemcpyHostToDevice, ctx->stream));
   }
+  if (prof && rows_per_slab) {
+    int rc = upload_profile_rows(q_begin + row0, q_begin + row0 + nrows);
+    if (rc != ALN_OK) return rc;
+  }
   for (int r0 = 0; r0 < nrows; r0 += 32768) {
     const int nr = std::min(32768, nrows - r0);
     for (int r = 1; r <= 8; ++r) {
@@ -411,7 +487,8 @@ int ScoreRun::launch(int row0, int nrows, float* dscores) {
       s.tsel = dsel + cls_begin[r];
       s.qsel = dqsel ? dqsel + row0 + r0 : nullptr;
       const dim3 grid(nc, packed ? (nr + 1) / 2 : nr);   // packed: two query rows per wave
-      dispatch_r<8>(r, [&](auto rc) {
+      if (prof) launch_score_prof(r, local, grid, ctx->stream, s, free_del, free_ins);
+      else dispatch_r<8>(r, [&](auto rc) {
         constexpr int R = decltype(rc)::value;
         if (packed) hipLaunchKernelGGL(score_local_pk_kernel<R>, grid, block, 0, ctx->stream, s, nr);
         else if (!local) hipLaunchKernelGGL(score_global_kernel<R>, grid, block, 0, ctx->stream, s, free_del, free_ins);
@@ -428,6 +505,27 @@ int ScoreRun::launch(int row0, int nrows, float* dscores) {
 
 using namespace aln;
 
+// The shared body of aln_score_all_vs_all and aln_score_profiles_vs_all (run: prepared)
+static int score_block(ScoreRun& run, float* scores) {
+  aln_ctx* ctx = run.ctx;
+  if (run.route == ScoreRun::kAllFull)
+    return score_through_batches(ctx, run.queries, run.templates, run.sub, run.gap, run.q_begin, run.q_end, run.every_t, scores, nullptr, 0, run.prof);
+  const int rows = run.rows, n_t = run.n_t;
+  float* dsc = nullptr;
+  int rc;
+#define STRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(e_); hipFree(dsc); return ALN_E_HIP; } } while (0)
+  STRY(hipMalloc((void**)&dsc, (size_t)rows * n_t * 4));
+  if ((rc = run.upload()) != ALN_OK || (rc = run.launch(0, rows, dsc)) != ALN_OK) { hipFree(dsc); return rc; }
+  STRY(hipMemcpyAsync(scores, dsc, (size_t)rows * n_t * 4, hipMemcpyDeviceToHost, ctx->stream));
+  STRY(hipStreamSynchronize(ctx->stream));
+#undef STRY
+  hipFree(dsc);
+  run.release();
+  if (!run.long_t.empty())
+    return score_through_batches(ctx, run.queries, run.templates, run.sub, run.gap, run.q_begin, run.q_end, run.long_t, scores, nullptr, 0, run.prof);
+  return ALN_OK;
+}
+
 // The score Optimal reports for queries[q_begin .. q_end) against every template: scores[(q - q_begin) * n_t + t].
 // Replaces (q_end - q_begin) x n_t constructions of DPMatrix(q, t, AASubstitutionEval, fwd, align_type) + Optimal(align_type):
 // find_max for local alignments, the final cell's score for the four other align types.
@@ -437,17 +535,16 @@ extern "C" int aln_score_all_vs_all(aln_ctx* ctx, const aln_seqs* queries, const
   ScoreRun run;
   int rc = run.prepare(ctx, queries, templates, sub, gap, q_begin, q_end);
   if (rc != ALN_OK || run.route == ScoreRun::kNothing) return rc;
-  if (run.route == ScoreRun::kAllFull) return score_through_batches(ctx, queries, templates, sub, gap, q_begin, q_end, run.every_t, scores);
-  const int rows = run.rows, n_t = run.n_t;
-  float* dsc = nullptr;
-#define STRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(e_); hipFree(dsc); return ALN_E_HIP; } } while (0)
-  STRY(hipMalloc((void**)&dsc, (size_t)rows * n_t * 4));
-  if ((rc = run.upload()) != ALN_OK || (rc = run.launch(0, rows, dsc)) != ALN_OK) { hipFree(dsc); return rc; }
-  STRY(hipMemcpyAsync(scores, dsc, (size_t)rows * n_t * 4, hipMemcpyDeviceToHost, ctx->stream));
-  STRY(hipStreamSynchronize(ctx->stream));
-#undef STRY
-  hipFree(dsc);
-  run.release();
-  if (!run.long_t.empty()) return score_through_batches(ctx, queries, templates, sub, gap, q_begin, q_end, run.long_t, scores);
-  return ALN_OK;
+  return score_block(run, scores);
+}
+
+// The same for position-specific queries: replaces as many fills of a Q x T SimilarityMatrix from a position-dependent
+// Evaluator::similarity + DPMatrix + Optimal constructions.
+extern "C" int aln_score_profiles_vs_all(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_seqs* templates, const aln_gap* gap,
+                                         int32_t q_begin, int32_t q_end, float* scores) {
+  if (!scores || !profiles) return ALN_E_ARG;
+  ScoreRun run;
+  int rc = run.prepare(ctx, nullptr, templates, nullptr, gap, q_begin, q_end, profiles);
+  if (rc != ALN_OK || run.route == ScoreRun::kNothing) return rc;
+  return score_block(run, scores);
 }

@@ -8,8 +8,9 @@
 //   GlobalCols<R> + sweep_global  the four non-local align types: no clip, "minus infinity" outside the interior,
 //                                 end gaps priced per align type, the final cell included                      (dpmatrix.h:375-534)
 // Users: score_only.hip (scores), search_topk.hip (end cells), search_zscore.hip (one sweep per shuffle), search_align.hip
-// (four or five bits per cell into a strip).  What a user sees of a sweep beyond its result goes through an observer; the
-// packed 16-bit kernel of score_only.hip has its own types and its own sweep.
+// (four or five bits per cell into a strip), score_profile.hip (queries given as position-specific rows).  What a user sees of
+// a sweep beyond its result goes through an observer, where a row's similarities come from through a row source; the packed
+// 16-bit kernel of score_only.hip has its own types and its own sweep.
 #pragma once
 #include "aln_internal.h"
 
@@ -32,10 +33,53 @@ __device__ __forceinline__ int wave_incl_max_s(int v) {
   return v;
 }
 
-// S[q][c] from the 32 x 32 LDS table: qrow = 128 * query code, c4 = 4 * template code (byte offsets)
+// ---- row sources ---------------------------------------------------------------------------------------------------------------
+// A sweep reads S[i][c] as one LDS word at base + (byte offset of row i's 32 ints, wave-uniform) + 4 * (template code of column
+// c).  Where the offset comes from is the row source, a policy of sweep_local / sweep_global (template parameter Rows; Src is
+// what the global pointer handed to the sweep points to):
+//   first(lds, src)     the offset of row 1; called once, before anything else
+//   row(lds, src, i)    the offset of row i >= 2, called once per row in ascending order: the hook in which a source stages
+//                       what later rows need
 __device__ __forceinline__ int sweep_tab_at(const int* tab, int qrow, int c4) {
   return *reinterpret_cast<const int*>(reinterpret_cast<const char*>(tab) + qrow + c4);
 }
+
+// The default: a 32 x 32 substitution table in LDS, row i is the table row of query code qc[i] (128 bytes per code), and the
+// code of row i + 1 is fetched while row i is computed.  kInSweep: its three lines stay spelled out in the sweeps, under
+// `if constexpr`, and this struct only names them.  Routed through first() / row() like any other source the same loads reach
+// the optimiser in another shape (the address of qc[i + 1] is formed differently) and nine instantiations of
+// score_global_kernel, score_shuffled_kernel and align_global_hit_kernel change their SGPR spills.
+struct TableRows {
+  typedef uint8_t Src;
+  static constexpr bool kInSweep = true;
+};
+
+// A position-specific query (score_profile.hip): the device holds row i of the profile as 32 int32 (128 bytes; letters n .. 31
+// and the two sentinel rows are 0), rows contiguous, so 8 rows are the 1 KiB that ONE 16-byte-per-lane global -> LDS copy writes
+// lane-linearly.  LDS holds a ring of 32 rows (4 chunks of 8, the 4 KiB of the table it replaces): row i sits in slot i & 31.
+// Chunk c + 1 is requested when the sweep enters chunk c, then the source waits until at most that one copy is outstanding, i.e.
+// until chunk c has landed (copies complete in order; the loop holds no other global load that would make the compiler drain
+// them early).  The slot chunk c + 1 overwrites was last read three chunks ago.  The copy of the chunk after the last row's is
+// requested as well and never read: the buffer is padded by kProfilePadRows rows for it (ScoreRun::upload_profile_rows).
+constexpr int kProfilePadRows = 16;
+struct ProfileRows {
+  typedef int4 Src;
+  static constexpr bool kInSweep = false;
+  static __device__ __forceinline__ void fill(const int* ring, const int4* src, int c) {
+    typedef __attribute__((address_space(3))) void* lds_t;
+    typedef __attribute__((address_space(1))) void* glb_t;
+    __builtin_amdgcn_global_load_lds((glb_t)(src + c * 64 + (int)threadIdx.x), (lds_t)(ring + (c & 3) * 256), 16, 0, 0);
+  }
+  static __device__ __forceinline__ void landed() { asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); }
+  static __device__ __forceinline__ int first(const int* ring, const int4* src) {
+    fill(ring, src, 0); fill(ring, src, 1); landed();
+    return 128;
+  }
+  static __device__ __forceinline__ int row(const int* ring, const int4* src, int i) {
+    if ((i & 7) == 0) { fill(ring, src, (i >> 3) + 1); landed(); }
+    return (i & 31) * 128;
+  }
+};
 
 // What a user of sweep_local or sweep_global may watch.  The default watches nothing and compiles to nothing.
 struct NoObserver {
@@ -82,8 +126,8 @@ struct LocalCols {
 // returns the lane's maximum over every cell it computed.  The sweep owns that maximum and both inner loops stay in this
 // function: an observer that keeps the maximum by reference, or a helper that takes the row arrays by reference, costs
 // registers and with them waves per SIMD.
-template <int R, class Obs>
-__device__ __forceinline__ int sweep_local(const int* tab, const LocalCols<R>& k, const uint8_t* qc, int last,
+template <int R, class Rows = TableRows, class Obs>
+__device__ __forceinline__ int sweep_local(const int* tab, const LocalCols<R>& k, const typename Rows::Src* qc, int last,
                                            int (&d)[R][4], Obs&& obs) {
   const int lane = threadIdx.x;
   const int cb = 4 * lane;
@@ -120,7 +164,9 @@ __device__ __forceinline__ int sweep_local(const int* tab, const LocalCols<R>& k
   };
   if (last >= 1) {
     // row 1 (dpmatrix.h:579-590): local mode -> end gaps are free: clip(S[1][c])
-    const int qrow = (int)qc[1] * 128;
+    int qrow;
+    if constexpr (Rows::kInSweep) qrow = (int)qc[1] * 128;
+    else qrow = Rows::first(tab, qc);
 #pragma unroll
     for (int r = 0; r < R; ++r)
 #pragma unroll
@@ -131,10 +177,14 @@ __device__ __forceinline__ int sweep_local(const int* tab, const LocalCols<R>& k
     finish_row();
     obs.row(1, d, lmax);
   }
-  int qcode_next = (last >= 2) ? (int)qc[2] : 0;
+  int qcode_next = 0;
+  if constexpr (Rows::kInSweep) qcode_next = (last >= 2) ? (int)qc[2] : 0;
   for (int i = 2; i <= last; ++i) {                         // dpmatrix.h:607-649
-    const int qrow = qcode_next * 128;
-    if (i + 1 <= last) qcode_next = (int)qc[i + 1];
+    int qrow;
+    if constexpr (Rows::kInSweep) {
+      qrow = qcode_next * 128;
+      if (i + 1 <= last) qcode_next = (int)qc[i + 1];
+    } else qrow = Rows::row(tab, qc, i);
     const int roff = gi + ge * (i - 2);
     const int rowB = ge * (i - 1);
     int bk[R][4];
@@ -223,8 +273,8 @@ struct GlobalCols {
 // candidate for the final cell's score; the maximum over the wave is the score.  Both inner loops stay in this function, as in
 // sweep_local; the row array stays in it too, and an observer sees the last row through last(): handing d[] out by reference
 // moved the registers of score_global_kernel and score_shuffled_kernel.
-template <int R, class Obs>
-__device__ __forceinline__ int sweep_global(const int* tab, const GlobalCols<R>& k, const uint8_t* qc, int Q,
+template <int R, class Rows = TableRows, class Obs>
+__device__ __forceinline__ int sweep_global(const int* tab, const GlobalCols<R>& k, const typename Rows::Src* qc, int Q,
                                             int free_del, int free_ins, Obs&& obs) {
   const int lane = threadIdx.x;
   const int cb = 4 * lane;
@@ -258,7 +308,9 @@ __device__ __forceinline__ int sweep_global(const int* tab, const GlobalCols<R>&
   };
   {
     // row 1 (dpmatrix.h:409-418): one deletion from the origin, free if the template's head gap is
-    const int qrow = (int)qc[1] * 128;
+    int qrow;
+    if constexpr (Rows::kInSweep) qrow = (int)qc[1] * 128;
+    else qrow = Rows::first(tab, qc);
 #pragma unroll
     for (int r = 0; r < R; ++r)
 #pragma unroll
@@ -270,10 +322,14 @@ __device__ __forceinline__ int sweep_global(const int* tab, const GlobalCols<R>&
     finish_row();
     obs.row(1, d, clast);
   }
-  int qcode_next = (Q >= 4) ? (int)qc[2] : 0;
+  int qcode_next = 0;
+  if constexpr (Rows::kInSweep) qcode_next = (Q >= 4) ? (int)qc[2] : 0;
   for (int i = 2; i <= Q - 2; ++i) {                               // dpmatrix.h:447-486
-    const int qrow = qcode_next * 128;
-    if (i + 1 <= Q - 2) qcode_next = (int)qc[i + 1];
+    int qrow;
+    if constexpr (Rows::kInSweep) {
+      qrow = qcode_next * 128;
+      if (i + 1 <= Q - 2) qcode_next = (int)qc[i + 1];
+    } else qrow = Rows::row(tab, qc, i);
     const int roff = gi + ge * (i - 2);
     const int rowB = ge * (i - 1);
     const int col1 = free_ins ? 0 : roff;                          // column 1: one insertion from the origin (:421-426)

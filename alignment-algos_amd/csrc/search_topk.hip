@@ -143,21 +143,7 @@ __global__ __launch_bounds__(256) void scatter_cols_kernel(float* slab, int n_t,
 // row-major order does.  Per lane: the row at which the running maximum last strictly improved and — inside that rare
 // branch — the smallest of the lane's columns holding it; the wave reduces by (value max, row min, column min); then the seed
 // exception: D[Q-2][T-2] is in the registers when the sweep ends.  A maximum of 0 (no positive cell, or no interior) is the seed's.
-struct FirstMaxObserver : NoObserver {
-  int seen = 0, lrow = 0, lcol = 0;
-  // the lane's maximum rose in row i exactly when row i's maximum exceeds the old one, and then equals it
-  template <int R>
-  __device__ __forceinline__ void row(int i, const int (&d)[R][4], int lane_max) {
-    if (lane_max > seen) {
-      seen = lane_max; lrow = i;
-#pragma unroll
-      for (int r = R - 1; r >= 0; --r)
-#pragma unroll
-        for (int x = 3; x >= 0; --x) lcol = (d[r][x] == lane_max) ? 4 * (int)threadIdx.x + 256 * r + x : lcol;
-    }
-  }
-};
-
+// (FirstMaxObserver: score_common.h, shared with the profile twin of this kernel.)
 template <int R>
 __global__ __launch_bounds__(64) void score_local_end_kernel(ScoreArgs a, const int32_t* __restrict__ list, aln_hit* hits, int K) {
   __shared__ int tab[32 * 32];
@@ -199,14 +185,11 @@ __global__ __launch_bounds__(64) void score_local_end_kernel(ScoreArgs a, const 
 
 // End cells of local hits whose pair went the full-build route: resident batches over just those hits, Optimal's pair list —
 // enumerate_local (optimal.h:79-105) appends (Q-1, T-1) and prepends find_max's cell, so the entry before the last is that cell.
-// Groups stay below the plane budget of score_through_batches.
+// Groups stay below the plane budget of score_through_batches; prof != nullptr: as there, planes expanded on the host.
 static int end_cells_through_batches(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
                                      const aln_gap* gap, const std::vector<int32_t>& qi_all, const std::vector<int32_t>& ti_all,
-                                     const std::vector<aln_hit*>& where) {
+                                     const std::vector<aln_hit*>& where, const aln_qprofiles* prof) {
   const size_t budget = (size_t)12 << 30, max_pairs = 65536;
-  aln_sim sim = aln_sim();
-  sim.kind = ALN_SIM_SUBMATRIX;
-  sim.sub = *sub;
   std::vector<int32_t> n, st, pairs;
   size_t g0 = 0;
   while (g0 < qi_all.size()) {
@@ -215,15 +198,17 @@ static int end_cells_through_batches(aln_ctx* ctx, const aln_seqs* queries, cons
     while (g1 < qi_all.size() && g1 - g0 < max_pairs) {
       const int64_t Q = queries->offsets[qi_all[g1] + 1] - queries->offsets[qi_all[g1]];
       const int64_t T = templates->offsets[ti_all[g1] + 1] - templates->offsets[ti_all[g1]];
-      const size_t need = (size_t)Q * (size_t)(T + 16) * 8;
+      const size_t need = batch_pair_bytes((size_t)Q, (size_t)T, prof != nullptr);
       if (g1 > g0 && bytes + need > budget) break;
       bytes += need; mq = std::max(mq, Q); mt = std::max(mt, T); ++g1;
     }
     const int32_t np = (int32_t)(g1 - g0), stride = (int32_t)std::max<int64_t>(std::min(mq, mt) + 3, 4);
     n.assign((size_t)np, 0); st.assign((size_t)np, 0); pairs.assign((size_t)np * stride * 2, 0);
     aln_batch* bb = nullptr;
+    BatchSim bs;
+    bs.set(sub, prof, templates, (size_t)np, qi_all.data() + g0, ti_all.data() + g0);
     int rc = aln_batch_create(ctx, queries, templates, np, qi_all.data() + g0, ti_all.data() + g0, 0, &bb);
-    if (rc == ALN_OK) rc = aln_batch_dp(bb, &sim, gap, ALN_FWD, ALN_DP_AUTO, 0);
+    if (rc == ALN_OK) rc = aln_batch_dp(bb, &bs.sim, gap, ALN_FWD, ALN_DP_AUTO, 0);
     if (rc == ALN_OK) rc = aln_batch_optimal(bb, nullptr, n.data(), pairs.data(), stride, st.data());
     if (bb) aln_batch_destroy(bb);
     if (rc != ALN_OK) return rc;
@@ -238,17 +223,12 @@ static int end_cells_through_batches(aln_ctx* ctx, const aln_seqs* queries, cons
   return ALN_OK;
 }
 
-}  // namespace aln
-
-using namespace aln;
-
-extern "C" int aln_search_topk(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
-                               const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K, float min_score,
-                               aln_hit* hits, int32_t* n_hits) {
-  if (!hits || !n_hits || K < 1 || K > kSelKeep) return ALN_E_ARG;
-  ScoreRun run;
-  int rc = run.prepare(ctx, queries, templates, sub, gap, q_begin, q_end);
-  if (rc != ALN_OK) return rc;
+// The shared body of aln_search_topk and aln_search_topk_profiles (run: prepared): slabs, selection, end cells
+static int search_block(ScoreRun& run, int32_t K, float min_score, aln_hit* hits, int32_t* n_hits, const char* entry) {
+  aln_ctx* ctx = run.ctx;
+  const aln_seqs *queries = run.queries, *templates = run.templates;
+  const aln_submatrix* sub = run.sub; const aln_gap* gap = run.gap; const aln_qprofiles* prof = run.prof;
+  const int32_t q_begin = run.q_begin;
   const int rows = run.rows, n_t = run.n_t;
   if (rows == 0) return ALN_OK;
   if (n_t == 0) {
@@ -274,6 +254,8 @@ extern "C" int aln_search_topk(aln_ctx* ctx, const aln_seqs* queries, const aln_
   };
 #define STRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(e_); cleanup(); return ALN_E_HIP; } } while (0)
 #define RTRY(expr) do { int r_ = (expr); if (r_ != ALN_OK) { hipStreamSynchronize(ctx->stream); cleanup(); return r_; } } while (0)
+  // profiles: the block's device rows (128 B each) stay below the slab budget too, else every slab brings its own
+  run.rows_per_slab = prof && (size_t)(prof->offsets[run.q_end] - prof->offsets[q_begin]) * 128 > kSlabBudget;
   RTRY(all_full ? run.upload_offsets() : run.upload());
   STRY(hipMalloc((void**)&dslab, (size_t)slab_rows * n_t * 4));
   STRY(hipMalloc((void**)&dhits, (size_t)slab_rows * K * sizeof(aln_hit)));
@@ -303,7 +285,7 @@ extern "C" int aln_search_topk(aln_ctx* ctx, const aln_seqs* queries, const aln_
     if (!all_full) RTRY(run.launch(r0, nr, dslab));
     if (n_full) {
       RTRY(score_through_batches(ctx, queries, templates, sub, gap, q_begin + r0, q_begin + r0 + nr, full_t, hfull.data(),
-                                 all_full ? nullptr : fcol.data(), (size_t)n_full));
+                                 all_full ? nullptr : fcol.data(), (size_t)n_full, prof));
       if (all_full) STRY(hipMemcpyAsync(dslab, hfull.data(), (size_t)nr * n_t * 4, hipMemcpyHostToDevice, ctx->stream));
       else {
         const long long ne = (long long)nr * n_full;
@@ -338,7 +320,8 @@ extern "C" int aln_search_topk(aln_ctx* ctx, const aln_seqs* queries, const aln_
       s.q_begin = q_begin + r0;
       for (int c = 1; c <= 8; ++c) {
         if (cls_cnt[c] == 0) continue;
-        dispatch_r<8>(c, [&](auto rc) {
+        if (prof) launch_score_local_end_prof(c, cls_cnt[c], ctx->stream, s, dlist + co.off[c], dhits, K);
+        else dispatch_r<8>(c, [&](auto rc) {
           hipLaunchKernelGGL(score_local_end_kernel<decltype(rc)::value>, dim3(cls_cnt[c]), dim3(64), 0, ctx->stream, s, dlist + co.off[c], dhits, K);
         });
         STRY(hipGetLastError());
@@ -365,7 +348,7 @@ extern "C" int aln_search_topk(aln_ctx* ctx, const aln_seqs* queries, const aln_
           aln_hit* h = &out[(size_t)r * K + k];
           if (is_full[h->t]) { qi.push_back(q_begin + r0 + r); tix.push_back(h->t); where.push_back(h); }
         }
-      RTRY(end_cells_through_batches(ctx, queries, templates, sub, gap, qi, tix, where));
+      RTRY(end_cells_through_batches(ctx, queries, templates, sub, gap, qi, tix, where, prof));
       n_full_end += (long long)qi.size();
       ms_full_end += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
@@ -374,7 +357,30 @@ extern "C" int aln_search_topk(aln_ctx* ctx, const aln_seqs* queries, const aln_
 #undef RTRY
   cleanup();
   if (debug)
-    fprintf(stderr, "aln_search_topk: rows %d n_t %d K %d slabs %d (%d rows each) score_ms %.3f select_ms %.3f end_ms %.3f (%lld hits) "
-            "full_end_ms %.3f (%lld hits)\n", rows, n_t, K, n_slabs, slab_rows, ms_score, ms_select, ms_end, n_end, ms_full_end, n_full_end);
+    fprintf(stderr, "%s: rows %d n_t %d K %d slabs %d (%d rows each) score_ms %.3f select_ms %.3f end_ms %.3f (%lld hits) "
+            "full_end_ms %.3f (%lld hits)\n", entry, rows, n_t, K, n_slabs, slab_rows, ms_score, ms_select, ms_end, n_end, ms_full_end, n_full_end);
   return ALN_OK;
+}
+
+}  // namespace aln
+
+using namespace aln;
+
+extern "C" int aln_search_topk(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
+                               const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K, float min_score,
+                               aln_hit* hits, int32_t* n_hits) {
+  if (!hits || !n_hits || K < 1 || K > kSelKeep) return ALN_E_ARG;
+  ScoreRun run;
+  int rc = run.prepare(ctx, queries, templates, sub, gap, q_begin, q_end);
+  if (rc != ALN_OK) return rc;
+  return search_block(run, K, min_score, hits, n_hits, "aln_search_topk");
+}
+
+extern "C" int aln_search_topk_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_seqs* templates, const aln_gap* gap,
+                                        int32_t q_begin, int32_t q_end, int32_t K, float min_score, aln_hit* hits, int32_t* n_hits) {
+  if (!hits || !n_hits || !profiles || K < 1 || K > kSelKeep) return ALN_E_ARG;
+  ScoreRun run;
+  int rc = run.prepare(ctx, nullptr, templates, nullptr, gap, q_begin, q_end, profiles);
+  if (rc != ALN_OK) return rc;
+  return search_block(run, K, min_score, hits, n_hits, "aln_search_topk_profiles");
 }

@@ -206,9 +206,9 @@ int aln_has_gfx950(void);
  *                                   (allocating tens of GB costs seconds); 0: frees them when it returns
  *   "enum_pool_retries"             aln_batch_enumerate_all: how often a pair whose pools overflowed is searched again with four
  *                                   times the capacity (default 2)
- *   "search_slab_rows"              aln_search_topk: query rows whose scores are resident on the device at a time; 0 (default) = as many as
+ *   "search_slab_rows"              aln_search_topk, aln_search_topk_profiles: query rows whose scores are resident on the device at a time; 0 (default) = as many as
  *                                   keep the slab's scores (4 B x n_templates per row) and hits (16 B x K per row) below 1 GiB each
- *   "search_debug"                  1: aln_search_topk reports its slabs and the device time of scoring / selection / end cells on stderr
+ *   "search_debug"                  1: aln_search_topk / aln_search_topk_profiles report their slabs and the device time of scoring / selection / end cells on stderr
  *   "zscore_chunk_rows"             aln_hits_zscores: query rows whose shuffled strings and accumulators are resident on the device at a
  *                                   time; 0 (default) = as many as keep the shuffled pool (n_shuffles x |q| bytes per row with a hit) and the
  *                                   accumulators (16 B x K per row) below 1 GiB each; a larger value is cut to that
@@ -368,6 +368,46 @@ typedef struct {
 int aln_search_topk(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
                     const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K, float min_score,
                     aln_hit* hits /* (q_end-q_begin) x K */, int32_t* n_hits /* q_end-q_begin */);
+
+/* ---- position-specific queries: all-vs-all scoring and search for profiles (PSSMs), no planes ---------------------- */
+/* A pool of query profiles.  The reference builds a DPMatrix from any SimilarityMatrix, and a user Evaluator may return a
+ * similarity that depends on the query POSITION, not on the query letter (evaluator.h:20-97): one score per template letter
+ * for every query position — the second-round query of an iterative search, the query form of family databases.  Such a query
+ * has no residue string to send through a substitution table. */
+typedef struct {
+  int32_t n_seqs;
+  const int64_t* offsets;       /* n_seqs + 1, in ROWS: profile s owns rows offsets[s] .. offsets[s+1); its first and last row stand
+                                   for '^' and '$' (as aln_seqs INCLUDES them) and their values are never read; >= 2 rows each */
+  const float* rows;            /* offsets[n_seqs] x n, row-major: rows[r * n + a] = similarity of position r and letter alphabet[a] */
+  int32_t n;                    /* 1 .. 30 */
+  const char* alphabet;         /* the TEMPLATES' alphabet */
+} aln_qprofiles;
+/* aln_score_all_vs_all and aln_search_topk for such queries.  For a profile of Q rows at row offset `off` and a template of T
+ * residues (sentinels counted) S is the Q x T plane with S[i][j] = rows[(off + i) * n + index(t[j])] for 1 <= i <= Q-2 and
+ * 1 <= j <= T-2, and 0 on the sentinel rows and columns; every reported value is what aln_batch_create over the pair (any
+ * placeholder query of Q - 2 residues) + aln_batch_dp(ALN_SIM_MATRIX with that plane, gap, ALN_FWD, ALN_DP_AUTO) +
+ * aln_batch_optimal give, bit for bit: find_max for local alignments, the final cell for the four other align types.
+ * aln_score_profiles_vs_all replaces (q_end - q_begin) x n_templates such plane fills (4 B/cell) and full builds, and has
+ * aln_score_all_vs_all's result layout; aln_search_topk_profiles replaces them and the host's sort of the dense result, and has
+ * aln_search_topk's: the layout of hits / n_hits, the order (score descending, ties by template index, -0.0 = +0.0), min_score,
+ * the padding { -1, 0, -1, -1 }, the end-cell rule with its (Q-2, T-2) seed, K in 1..1024, q_begin == q_end (ALN_OK, nothing
+ * written), n_templates == 0, the slabs (hint "search_slab_rows") and "search_debug" are those of aln_search_topk, word for word.
+ * Checks, in this order, nothing written when one fails: NULL arguments and (search) K; the row range; the gap model
+ * (ALN_GAP_AFFINE_CONST) and align type; n outside 1..30, NULL alphabet / rows / offsets, a profile of fewer than 2 rows
+ * (ALN_E_ARG); a template letter outside the alphabet (ALN_E_RESIDUE); more than 65534 rows or residues (ALN_E_TOO_LONG).
+ * Routes: integer entries (of the interior rows of the whole pool) and gaps inside aln_score_all_vs_all's 2^23 bound, templates
+ * of up to 2048 columns — register-resident kernels (csrc/score_profile.hip): the device holds the rows of [q_begin, q_end) as
+ * 32 x int32 each (the search uploads them slab by slab when they exceed 1 GiB) and nothing per cell touches HBM.  Everything
+ * else — a fractional entry or gap, the bound exceeded, longer templates — goes through resident batches inside the call and so
+ * accepts what aln_batch_dp accepts; the Q x T planes of a batch are expanded ON THE HOST for this fallback (it is the 4 B/cell
+ * path the entries exist to avoid), and the ~12 GB budget of a batch counts them.
+ * The hits of a profile search are aligned today through a resident batch over the hits with the same planes
+ * (aln_amd.profile_planes); aln_hits_zscores and aln_hits_align take residue queries only. */
+int aln_score_profiles_vs_all(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_seqs* templates, const aln_gap* gap,
+                              int32_t q_begin, int32_t q_end, float* scores);
+int aln_search_topk_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_seqs* templates, const aln_gap* gap,
+                             int32_t q_begin, int32_t q_end, int32_t K, float min_score,
+                             aln_hit* hits /* (q_end-q_begin) x K */, int32_t* n_hits /* q_end-q_begin */);
 
 /* ---- shuffle z-scores of search hits: the background of every hit scored and reduced on the device ------------------- */
 /* The reference has the hook (AlignedPairList::calcSignificance takes a Significance<Model> functor, significance.h) and ships
