@@ -151,9 +151,16 @@ __host__ __device__ __forceinline__ float load_score(const float* Hbase, int64_t
   if (hmode == 0) return Hbase[e];
   return (float)reinterpret_cast<const uint16_t*>(Hbase)[e];
 }
-// Lean planes (dp_affine_tag.hip LEAN): no score plane; bit 15 of a cell's pointer word (dialect 1 uses bits 0..12) is set when its
-// score is > 0, which is all the local traceback asks.  1 / 0 stand in for the score.
-__host__ __device__ __forceinline__ float flag_score(uint32_t w) { return (w != 0xFFFFFFFFu && (w & 0x8000u)) ? 1.f : 0.f; }
+// Lean planes (dp_affine_tag.hip LEAN): no score plane; a cell's pointer word (dialect 1 uses bits 0..12) also says whether its
+// score is 0, which is all the local traceback asks.  Score 0: an untouched, border or masked cell (0xFFFF); an interior cell the
+// clip key won, which leaves "match, tag bit 0" (no candidate carries that word: match candidates have tag 0); a cell of row 1 or
+// column 1, whose word is its real origin pointer, with bit 15 set.  Every other word: score > 0.  1 / 0 stand in for the score.
+// decode_ptr reads bits 0..12 and ignores a match word's tag, so it decodes a lean word as it decodes the full build's.
+constexpr uint32_t kLeanZeroBit = 0x8000u;
+constexpr uint32_t kLeanZeroMatch = (3u << 11) | 1u;
+__host__ __device__ __forceinline__ float lean_score(uint32_t w) {
+  return (w == 0xFFFFFFFFu || w == kLeanZeroMatch || (w & kLeanZeroBit)) ? 0.f : 1.f;
+}
 __host__ __device__ __forceinline__ void store_score(float* Hbase, int64_t plane_off, int ld, int i, int j, int hmode, float v) {
   const size_t e = (size_t)plane_off + (size_t)i * ld + j;
   if (hmode == 0) Hbase[e] = v;

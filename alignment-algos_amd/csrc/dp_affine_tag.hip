@@ -27,6 +27,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "aln_device.h"
 #include "aln_internal.h"
 #include "dp_tag_common.h"
 
@@ -42,9 +43,12 @@ __device__ __forceinline__ void setprio_dyn(int p) {     // s_setprio takes an i
 }
 
 // SEGQ: workgroups take (pair, row segment) items from the queue instead of building pair blockIdx.x from first to last row.
-// LEAN: the build of a caller that only walks the optimal path afterwards (aln_batch_reevaluate).  Bit 15 of a
-// stored pointer word says "this cell's score is > 0" (all the local traceback ever asks of a score), and of the score plane only
-// what dp_corner_kernel reads is written: row Q-2 and, in every row, the 16-byte chunk that holds column T-2.  2 bytes per cell.
+// LEAN: the build of a caller that only walks the optimal path afterwards (aln_batch_reevaluate).  A stored
+// pointer word also says whether the cell's score is 0 (all the local traceback ever asks of a score; aln_device.h::lean_score):
+// the clip key carries tag bit 0, so interior cells that score 0 hold P_MATCH | 1, a word no winning candidate has; the cells of
+// row 1 and column 1, which are not clipped against a key, get bit 15 when they score 0.  Of the score plane only what
+// dp_corner_kernel reads is written: row Q-2 and, in rows 1 .. Q-2, the 16-byte chunk that holds column T-2.  2 bytes per cell.
+// The lean form has no skewed exchange (lag is 0) and one priority form (alt_prio 1 or off): DESIGN.md 4.1 measured the others slower.
 template <int NW, int R, bool LOCAL, bool H16, int KBT, int X, bool SEGQ, int TB, int OCC, bool LEAN = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(R * X == 16 ? OCC : 1, R * X == 16 ? OCC : 8))) void dp_affine_tag_kernel(
     const PairDesc* __restrict__ pairs, const uint8_t* __restrict__ qcodes, const uint8_t* __restrict__ tcodes,
@@ -56,6 +60,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(R * X =
   constexpr int KB = (KBT == 16) ? 16 : TB + 2;                // KBT: 13 = "value right above the tag bits", 16 = score in the high half
   constexpr int LOW = (1 << KB) - 1;
   constexpr int NEGK = (KBT == 16) ? -(1 << 29) : tag::NEGK;   // value -8192 at KB = 16
+  // the clip of local builds.  LEAN: (0, match, tag bit 0) beats every candidate of value 0 as ZKEY does (match candidates carry tag
+  // 0) and loses to every value >= 1, so exactly the interior cells that score 0 keep the word P_MATCH | 1; decode_ptr ignores a
+  // match word's tag, and the next row never sees the mark (dk and dB keep the key's high half only)
+  constexpr int CLIPK = LEAN ? (ZKEY | 1) : ZKEY;
+  constexpr uint32_t ZBIT = LEAN ? kLeanZeroBit : 0u;          // row 1 / column 1: "scores 0" beside the cell's real origin pointer
   static_assert(KBT == 13 || (KBT == 16 && LOCAL && H16), "the 16-bit key layout needs non-negative 15-bit scores");
   static_assert(TB == 11 || TB == 12, "11 or 12 tag bits");
   static_assert(X == 4 || X == 8, "a lane owns 4 or 8 consecutive columns of each group");
@@ -158,7 +167,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(R * X =
   // (slot = row mod 16; L * (NW-1) + L <= 16).  The LDS write -> wait -> barrier -> read -> wait chain that sat inside every row
   // is gone: the reads are issued at the top of an iteration from a slot that has long been written.  lag = 0 keeps the
   // synchronous form (write, barrier, read in every row); row 1 always uses it.
-  const int lag = (NW > 1) ? prm.lag : 0;
+  const int lag = (NW > 1 && !LEAN) ? prm.lag : 0;
 
   // 16-bit planes are stored through buffer descriptors that cover ONE ROW (base = the row, num_records = 2*ld bytes),
   // rebuilt per row with scalar instructions: lanes of a partial last group (columns >= ld) are dropped by the memory
@@ -173,35 +182,33 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(R * X =
     else { const u32x4 v = {wd[0], wd[1], wd[2], wd[3]}; __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, 0); }
   };
   // LEAN: column T-2 lies in the X-cell chunk (T-2) / X of a row; chunk 64 R w + 64 r + lane is this lane's in group r.
+  int whole_row = Q - 2;                // LEAN: the row the corner cell scans, stored whole
   int own_r = -1;                       // the group whose chunk of column T-2 this lane stores in every row (-1: none)
-  // two constants of the lean stores, pinned in VGPRs: v_and_or_b32 and v_perm_b32 take no literal, and as SGPRs they made the
-  // full scalar file spill
-  uint32_t flag_bits = 0x80008000u, sel_high = 0x07060302u;
   if constexpr (LEAN) {
-    asm volatile("" : "+v"(flag_bits), "+v"(sel_high));
     const int tchunk = (T - 2) / X;
     own_r = ((tchunk & 63) == lane) ? (tchunk >> 6) - w * R : -1;
+    // opaque: knowing that only the last iteration stores a whole row, the compiler peels it off the row loop, and the six scalars
+    // the peeled copy needs are parked in VGPR lanes across the loop (SGPRs Spill: 6, 167 VGPRs); one s_cmp per row instead
+    asm volatile("" : "+s"(whole_row));
   }
   auto store_row = [&](int i, bool border = false) {    // border: row 0 or Q-1 (LEAN: no chunk of column T-2 there)
     const size_t ro = (size_t)i * ld + cb;
     const __amdgpu_buffer_rsrc_t rsP = __builtin_amdgcn_make_buffer_rsrc(P + (size_t)i * ld, 0, ld * 2, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsH = __builtin_amdgcn_make_buffer_rsrc(H16p + (size_t)i * ld, 0, ld * 2, 0x00020000);
     if constexpr (LEAN) {
-      const bool whole = i == Q - 2;          // scalar: the corner cell scans this row
+      const bool whole = i == whole_row;      // scalar
       asm volatile("" : "+v"(own_r));         // compared in every row: hoisted out of the loop the two tests cost two SGPR pairs
 #pragma unroll
       for (int r = 0; r < R; ++r) {
-        uint32_t pw[X / 2], hw[X / 2];
+        uint32_t pw[X / 2];
 #pragma unroll
-        for (int x = 0; x < X; x += 2) {
-          pw[x / 2] = __builtin_amdgcn_perm(pf[r][x + 1], pf[r][x], 0x05040100u);
-          hw[x / 2] = __builtin_amdgcn_perm((uint32_t)dk[r][x + 1], (uint32_t)dk[r][x], sel_high);
-          // both flags at once: a score is < 2^15 in the 16-bit key layout (tag_key16_legal), so score + 0x7FFF has bit 15 set
-          // exactly when score > 0 and never carries into the other half.  An OR: border and untouched cells have score 0 and
-          // keep 0xFFFF, every other word has bits 13..15 clear.  One v_add_u32 + one v_and_or_b32 per two cells.
-          pw[x / 2] |= (hw[x / 2] + 0x7FFF7FFFu) & flag_bits;
+        for (int x = 0; x < X; x += 2) pw[x / 2] = __builtin_amdgcn_perm(pf[r][x + 1], pf[r][x], 0x05040100u);
+        if (whole || (!border && own_r == r)) {              // exec-masked: usually one lane of the pair, and only it packs the scores
+          uint32_t hw[X / 2];
+#pragma unroll
+          for (int x = 0; x < X; x += 2) hw[x / 2] = __builtin_amdgcn_perm((uint32_t)dk[r][x + 1], (uint32_t)dk[r][x], 0x07060302u);
+          store_words(hw, rsH, vo16 + 2 * GW * r);
         }
-        if (whole || (!border && own_r == r)) store_words(hw, rsH, vo16 + 2 * GW * r);   // exec-masked: usually one lane of the pair
         store_words(pw, rsP, vo16 + 2 * GW * r);
       }
       return;
@@ -354,7 +361,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(R * X =
       if (LOCAL) v = max(v, 0);
       const bool in = (unsigned)(c - 1) < (unsigned)(T - 2);
       dkv = (in ? v : 0) | P_MATCH;
-      pv = in ? (uint32_t)(c == 1 ? P_MATCH : ORIGIN_DEL) : kNullPtr;
+      pv = in ? (uint32_t)(c == 1 ? P_MATCH : ORIGIN_DEL) | (v == 0 ? ZBIT : 0u) : kNullPtr;
     };
 #pragma unroll
     for (int r = 0; r < R; ++r)
@@ -390,7 +397,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(R * X =
     // the wave's hardware slot) evens that out: -3...-6 % on a lone launch.  Launches that overlap on several streams
     // (bench.py) fill those gaps better and lose with it; launch_dp_affine_tag decides (one context alive -> on).
     const int par = (i ^ hwslot) & 1;
-    if (prm.alt_prio & 0x100) {               // experiment: explicit levels, bits 0-1 / 4-5 = the row's bulk for even / odd parity
+    if constexpr (LEAN) {                     // one form; every other value of the hint means off
+      if (prm.alt_prio == 1) { if (par) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0); }
+    } else if (prm.alt_prio & 0x100) {        // experiment: explicit levels, bits 0-1 / 4-5 = the row's bulk for even / odd parity
       setprio_dyn(par ? (prm.alt_prio >> 4) & 3 : prm.alt_prio & 3);
     } else if (prm.alt_prio == 1) {
       if (par) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0);
@@ -432,7 +441,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(R * X =
     int dB = P_MATCH; uint32_t pB = kNullPtr;
     if (NW > 1) {
       int kh = bk[R - 1][X - 1] + svB;
-      if (LOCAL) kh = max(kh, ZKEY);
+      if (LOCAL) kh = max(kh, CLIPK);
       const bool in = CB <= T - 2;
       dB = in ? ((kh & ~LOW) | P_MATCH) : P_MATCH;
       pB = in ? (uint32_t)(kh & LOW) : kNullPtr;
@@ -459,7 +468,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(R * X =
         const int sK = sv[r][x];
         if (r == 0 && x == 1) sK1 = sK;
         int kh = ((x == 0) ? uk : bk[r][x - 1]) + sK;
-        if (LOCAL) kh = max(kh, ZKEY);
+        if (LOCAL) kh = max(kh, CLIPK);
         dk[r][x] = (kh & ~LOW) | P_MATCH;                    // v_and_or_b32
         pf[r][x] = (KBT == 16) ? (uint32_t)kh : (uint32_t)(kh & LOW);   // KB = 16: the store takes the low half of the whole key
       }
@@ -469,7 +478,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(R * X =
           int v1 = sK1 - colK;
           if (LOCAL) v1 = max(v1, 0);
           const bool is1 = cb == 0;
-          dk[0][1] = is1 ? (v1 | P_MATCH) : dk[0][1]; pf[0][1] = is1 ? (uint32_t)ORIGIN_INS : pf[0][1];
+          dk[0][1] = is1 ? (v1 | P_MATCH) : dk[0][1]; pf[0][1] = is1 ? ((uint32_t)ORIGIN_INS | (v1 == 0 ? ZBIT : 0u)) : pf[0][1];
         }
 #pragma unroll
         for (int x = 0; x < X; ++x) {
@@ -478,7 +487,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(R * X =
         }
       }
     }
-    if (prm.alt_prio & 0x100) setprio_dyn(par ? (prm.alt_prio >> 6) & 3 : (prm.alt_prio >> 2) & 3);   // bits 2-3 / 6-7 = the row's end
+    if constexpr (LEAN) {}
+    else if (prm.alt_prio & 0x100) setprio_dyn(par ? (prm.alt_prio >> 6) & 3 : (prm.alt_prio >> 2) & 3);   // bits 2-3 / 6-7 = the row's end
     else if (prm.alt_prio == 2) __builtin_amdgcn_s_setprio(3);
     else if (prm.alt_prio == 3) { if (par) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(2); }
     finish_row(i, dB, pB, sync, xin);

@@ -18,7 +18,7 @@ struct TbParams {
   int rev;          // pointers lead towards larger indices (reverse build, Optimal_Rev)
   int stride;       // capacity in pairs of each pair's output list
   int ptr_mode;     // pointer word encoding of the P plane
-  int h_mode;       // score plane element type (aln_device.h load_score); 2 = no score plane: bit 15 of a pointer word says "score > 0"
+  int h_mode;       // score plane element type (aln_device.h load_score); 2 = no score plane: the pointer word says "score is 0" (lean_score)
 };
 
 __global__ __launch_bounds__(64) void traceback_kernel(const PairDesc* __restrict__ pairs, const float* __restrict__ Hbase,
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(64) void traceback_kernel(const PairDesc* __restric
     uint32_t p = kNullPtr; float h = 0.f;
     if (valid) {
       p = load_ptr_word(Pbase, pd.plane_off, ld, cq, ct, prm.ptr_mode);
-      h = prm.h_mode == 2 ? flag_score(p) : load_score(Hbase, pd.plane_off, ld, cq, ct, prm.h_mode);
+      h = prm.h_mode == 2 ? lean_score(p) : load_score(Hbase, pd.plane_off, ld, cq, ct, prm.h_mode);
     }
     const float hnext = __shfl_down(h, 1);      // score of the diagonal neighbour (lane+1's cell)
     const bool active = valid && before_stop(cq);   // the while loop would process this cell
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(64) void traceback_kernel(const PairDesc* __restric
     const int nq = jq, nt = jt;
     if (pL == kNullPtr) { lq = -1; lt = -1; if (!prm.islocal) status = ALN_E_STARTPAIR; break; }
     if (prm.islocal) {
-      const float hn = prm.h_mode == 2 ? flag_score(load_ptr_word(Pbase, pd.plane_off, ld, nq, nt, prm.ptr_mode))
+      const float hn = prm.h_mode == 2 ? lean_score(load_ptr_word(Pbase, pd.plane_off, ld, nq, nt, prm.ptr_mode))
                                        : load_score(Hbase, pd.plane_off, ld, nq, nt, prm.h_mode);
       if (hn <= 0.f) { lq = nq; lt = nt; break; }
     }

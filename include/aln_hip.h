@@ -241,8 +241,9 @@ int aln_batch_dp(aln_batch* b, const aln_sim* sim, const aln_gap* gap,
 /* DPMatrix::reevaluate (dpmatrix.h:213-218): rebuild with the parameters of the last aln_batch_dp.
  * Lean rebuilds: when the build being replaced was used by the Optimal family (aln_batch_optimal, _enqueue, _strings*) and by
  * nothing that reads scores (aln_batch_get_cells, aln_batch_enumerate*), and the launch is the 2048-column local tagged kernel
- * (16-bit keys), the rebuild writes 2 B/cell: pointer words whose bit 15 says "score > 0" and, of the score plane, only what the
- * final cell needs.  Optimal gives the same scores, lists and status on it.  The first other reader of the planes runs the full
+ * (16-bit keys), the rebuild writes 2 B/cell: pointer words that also say "this cell scores 0" (the word the clip key leaves in
+ * an interior cell, bit 15 in row 1 and column 1) and, of the score plane, only what the final cell needs.  The hints "tag_lag" and
+ * "tag_alt_prio" values other than 1 are accepted and ignored by the lean kernel.  Optimal gives the same scores, lists and status on it.  The first other reader of the planes runs the full
  * build again on the batch's stream (one more DP launch, counted in aln_batch_dp_ms_history) and the reevaluate after it is
  * full; results already enqueued stay valid.  Context hint "lean_reevaluate" (ALN_LEAN_REEVALUATE): 0 never, 1 this rule
  * (default), 2 every eligible reevaluate.  aln_batch_dp and aln_batch_dp_sub are always full. */
@@ -560,7 +561,7 @@ int aln_batch_dp_ms_history(aln_batch* b, float* ms, int32_t max_n);
  * the score element (fp32, or uint16 in local tagged builds) + the pointer element (32-bit, or 16-bit tagged words):
  * 8, 6 or 4 B/cell.  This is what a roofline fraction is computed from.  _contract_bytes is SURVEY.md 8(d)'s figure for the
  * reference's layout, 8 B per cell (fp32 score + 32-bit packed pointer), whatever was chosen; _plane_bytes_per_cell the factor.
- * While the resident planes are those of a lean aln_batch_reevaluate the factor is 2 (flagged pointer words only). */
+ * While the resident planes are those of a lean aln_batch_reevaluate the factor is 2 (marked pointer words only). */
 int64_t aln_batch_dp_algorithmic_bytes(const aln_batch* b);
 int64_t aln_batch_dp_contract_bytes(const aln_batch* b);
 int32_t aln_batch_plane_bytes_per_cell(const aln_batch* b);
