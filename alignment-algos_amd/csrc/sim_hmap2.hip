@@ -10,8 +10,8 @@
 // Three kernels:
 //  hmap2_sim_kernel    one thread per template column, rows in chunks: the column's profile sits in
 //                      registers, the row's profile is broadcast from LDS; expf is the host libm's algorithm
-//                      (glibc flt-32/e_expf.c: 32-entry 2^(i/32) table, degree-3 polynomial in double) so the
-//                      bits match the CPU evaluator;
+//                      (glibc flt-32/e_expf.c: 32-entry 2^(i/32) table, degree-3 polynomial in double) over its
+//                      whole range, so the bits match the CPU evaluator;
 //  hmap2_stats_kernel  two waves per pair (one per sum); 64 coalesced elements per step, each fp32 sum is
 //                      accumulated one element at a time in the reference's order (a parallel reduction would
 //                      round differently) by a value that rotates through the lanes;
@@ -33,9 +33,16 @@ __device__ const unsigned long long kExp2fTab[32] = {
     0x3fefa4afa2a490daull, 0x3fefd0765b6e4540ull};
 
 // expf as glibc computes it (sysdeps/ieee754/flt-32/e_expf.c, the table-driven double-precision algorithm);
-// validated bit-for-bit against the host libm on 350 k samples.  Outside |x| < 88 fall back to ocml.
+// validated bit-for-bit against the host libm on 350 k samples.  |x| >= 88 and NaN get e_expf.c's special cases —
+// NaN and +inf pass through, -inf is 0, x > log(2^128) overflows to +inf, x < log(2^-150) underflows to +0 — and everything
+// between takes the table path like the rest: its double result converts into the denormal range with one rounding.
 __device__ __forceinline__ float expf_glibc(float x) {
-  if (!(fabsf(x) < 88.0f)) return expf(x);
+  if (!(fabsf(x) < 88.0f)) {
+    if (x != x || x == __builtin_inff()) return x + x;
+    if (x == -__builtin_inff()) return 0.0f;
+    if (x > 0x1.62e42ep6f) return __builtin_inff();
+    if (x < -0x1.9fe368p6f) return 0.0f;
+  }
   const double InvLn2N = 0x1.71547652b82fep+0 * 32.0;
   const double Shift = 0x1.8p+52;
   const double C0 = 0x1.c6af84b912394p-5 / 32.0 / 32.0 / 32.0;

@@ -6,6 +6,9 @@ Runs oracle/_ref/ref_harness (christang/alignment-algos compiled in place from
 
   tests/golden/aa_cases.json   metadata, scores (as uint32 bit patterns), pair lists, gapped strings
   tests/golden/aa_cases.npz    full score / pointer / similarity matrices of the small cases
+  tests/golden/profile_cases.*        the profile path at its default parameters (oracle/_ref/ref_profile)
+  tests/golden/profile_param_cases.*  the profile path off them; `gen_golden.py profile_params` rewrites these two alone,
+                                      byte for byte
 
 Only this container has /root/reference; the fixtures are what travels.  Inputs are
 regenerated from seeds by aln_amd.synth (std::mt19937-compatible), but the sequences are
@@ -201,6 +204,51 @@ def gen_profiles():
     print("profile cases", len(meta))
 
 
+def save_npz_stable(path, arrays):
+    """np.savez_compressed stamps every member with the current time; this writes the same container (np.load reads it) with a
+    fixed stamp and the members in sorted order, so that the file regenerates byte for byte."""
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for name in sorted(arrays):
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            with z.open(info, "w") as f:
+                np.lib.format.write_array(f, np.ascontiguousarray(arrays[name]), version=(1, 0), allow_pickle=False)
+
+
+def gen_profile_params():
+    """The profile path off its default parameters: every set of tests/hmap2_cases.PARAMS on the 5 x 11 and the 19 x 14 inputs of
+    profile_cases.npz (in01, in02: the same seeds; the inputs are not stored again), global and local, forward."""
+    from aln_amd.synth import random_profile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from hmap2_cases import PARAMS
+    shapes = {1: (3, 9), 2: (17, 12)}
+    arrays = {}
+    meta = []
+    for n, (ql, tl) in sorted(shapes.items()):
+        qp, tp = random_profile(9700 + n, ql), random_profile(9800 + n, tl)
+        for pname, pr in PARAMS.items():
+            for mode in (1, 3):
+                name = "par%02d_%s_m%d" % (n, pname, mode)
+                r = refrun.run_profile(qp, tp, mode, pr["alpha"], pr["beta"], pr["zero_shift"], pr["gi"], pr["ge"], 1)
+                for k in ("S", "H", "PQ", "PT", "TGI", "TGE"):
+                    arrays[name + "/" + k] = r[k]
+                a = r["sets"]["OPT"]["alis"][0]
+                meta.append({"name": name, "inputs": "in%02d" % n, "params": pname, "mode": mode, "dir": 1, "alpha": pr["alpha"],
+                             "beta": pr["beta"], "zero_shift": pr["zero_shift"], "gi": pr["gi"], "ge": pr["ge"],
+                             "opt": {"score": bits(a["score"]), "pairs": a["pairs"].reshape(-1).tolist()}})
+    with open(os.path.join(GOLD, "profile_param_cases.json"), "w") as f:
+        json.dump({"generator": "oracle/gen_golden.py via oracle/_ref/ref_profile (real hmath.h/DPMatrix/Optimal + plugin evaluator)",
+                   "inputs": "tests/golden/profile_cases.npz", "cases": meta}, f, separators=(",", ":"), sort_keys=True)
+    save_npz_stable(os.path.join(GOLD, "profile_param_cases.npz"), arrays)
+    print("profile parameter cases", len(meta))
+
+
 if __name__ == "__main__":
-    main()
-    gen_profiles()
+    if sys.argv[1:] == ["profile_params"]:
+        gen_profile_params()
+    else:
+        main()
+        gen_profiles()
+        gen_profile_params()
