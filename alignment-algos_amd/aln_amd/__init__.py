@@ -95,6 +95,7 @@ EXPORTS = [
     "aln_deal_units", "aln_comm_unique_id", "aln_comm_create", "aln_ctx_create_multi", "aln_comm_destroy", "aln_comm_n_ranks",
     "aln_comm_last_error", "aln_gather_scores", "aln_gather_resident_enqueue", "aln_gather_resident_collect", "aln_search_topk",
     "aln_hits_zscores", "aln_hits_align", "aln_hits_align_last_routes", "aln_score_profiles_vs_all", "aln_search_topk_profiles",
+    "aln_hits_align_profiles",
 ]
 COMM_ID_BYTES = 128
 
@@ -170,6 +171,9 @@ def lib():
         L.aln_hits_align.argtypes = [C.c_void_p, C.POINTER(AlnSeqs), C.POINTER(AlnSeqs), C.POINTER(AlnSubmatrix), C.POINTER(AlnGap),
                                      C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.POINTER(AlnHitAlignment), _ip, C.c_int32,
                                      C.c_char_p, C.c_char_p, C.c_int32, _ip]
+        L.aln_hits_align_profiles.argtypes = [C.c_void_p, C.POINTER(AlnQProfiles), C.POINTER(AlnSeqs), C.POINTER(AlnSeqs), C.POINTER(AlnGap),
+                                              C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.POINTER(AlnHitAlignment), _ip,
+                                              C.c_int32, C.c_char_p, C.c_char_p, C.c_int32, _ip]
         L.aln_hits_align_last_routes.argtypes = [C.c_void_p, _lp]
         L.aln_hmap2_gap_arrays.argtypes = [_fp, C.c_int64, C.c_float, C.c_float, C.c_float, _fp, _fp]
         L.aln_batch_plane_bytes_per_cell.argtypes = [C.c_void_p]
@@ -339,8 +343,8 @@ def profiles_from_sequences(seqs, alphabet, table):
 
 def profile_planes(profile, template, alphabet):
     """The (L + 2) x (T + 2) float32 similarity plane of one profile (L x n, no sentinel rows) against one template (a string,
-    no sentinels): what Batch.dp_simmatrix takes for the pair.  A hit of a profile search is aligned through a resident batch
-    with it; the batch's query residues are placeholders (any string of L letters)."""
+    no sentinels): what Batch.dp_simmatrix takes for the pair.  hits_align_profiles aligns the hits of a profile search without
+    it; a resident batch over such planes (query residues: any string of L letters) is what that call is defined by."""
     prof = np.asarray(profile, dtype=np.float32).reshape(-1, len(alphabet))
     idx = {ch: k for k, ch in enumerate(alphabet)}
     S = np.zeros((len(prof) + 2, len(template) + 2), dtype=np.float32)
@@ -478,9 +482,59 @@ def hits_align(ctx, queries, templates, hits, n_hits, alphabet, table, gi, ge, q
     return rec, lists, tlines, qlines, lengths, rc
 
 
+def _hit_outputs(rows, K, pair_stride, line_stride, want_pairs, want_lines):
+    rec = np.zeros((rows, K), dtype=HIT_ALIGNMENT_DTYPE)
+    pairs = np.zeros((rows, K, pair_stride, 2), dtype=np.int32) if want_pairs else None
+    tl = C.create_string_buffer(max(rows * K * line_stride, 1)) if want_lines else None
+    ql = C.create_string_buffer(max(rows * K * line_stride, 1)) if want_lines else None
+    lengths = np.zeros((rows, K), dtype=np.int32) if want_lines else None
+    return rec, pairs, tl, ql, lengths
+
+
+def hits_align_profiles(ctx, profiles, templates, hits, n_hits, gi, ge, consensus=None, q_begin=0, align_type=LOCAL, want_pairs=True,
+                        want_lines=True, pair_stride=None, line_stride=None):
+    """aln_hits_align_profiles: hits_align for the hits of a profile search (profiles: a QueryProfiles; hits / n_hits in
+    search_topk_profiles' layout, row r is profile q_begin + r).  consensus: the query letters the lines and the identity are made
+    of — one string per profile of the POOL, without sentinels and of the profile's length (or a SeqPool of such) — or None for
+    the placeholder alphabet[0].  -> the 6-tuple of hits_align."""
+    tpool = templates if isinstance(templates, SeqPool) else SeqPool(templates)
+    cpool = None
+    if consensus is not None:
+        cpool = consensus if isinstance(consensus, SeqPool) else SeqPool(consensus)
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    n_hits = np.ascontiguousarray(n_hits, dtype=np.int32)
+    rows, K = hits.shape
+    assert n_hits.shape == (rows,)
+    g = _const_gap(align_type, gi, ge)
+    maxq = max([len(p) + 2 for p in profiles.profiles[q_begin:q_begin + rows]] + [2])
+    maxt = max([len(s) for s in tpool.seqs] + [2])
+    if pair_stride is None:
+        pair_stride = min(maxq, maxt) + 3
+    if line_stride is None:
+        line_stride = maxq + maxt + 2
+    rec, pairs, tl, ql, lengths = _hit_outputs(rows, K, pair_stride, line_stride, want_pairs, want_lines)
+    rc = lib().aln_hits_align_profiles(ctx.h, C.byref(profiles.c), C.byref(cpool.c) if cpool is not None else None, C.byref(tpool.c),
+                                       C.byref(g), q_begin, q_begin + rows, int(K), hits.ctypes.data_as(C.POINTER(AlnHit)), _i(n_hits),
+                                       rec.ctypes.data_as(C.POINTER(AlnHitAlignment)), _i(pairs) if want_pairs else None,
+                                       int(pair_stride) if want_pairs else 0, tl, ql, int(line_stride) if want_lines else 0,
+                                       _i(lengths) if want_lines else None)
+    if rc != 0 and not (rec["status"] == rc).any():
+        _check(rc, ctx.h)
+    lists = tlines = qlines = None
+    if want_pairs:
+        lists = [[pairs[r, k, :min(int(rec["n_pairs"][r, k]), pair_stride)].copy() for k in range(K)] for r in range(rows)]
+    if want_lines:
+        def cut(buf):
+            raw = buf.raw
+            return [[raw[(r * K + k) * line_stride:(r * K + k) * line_stride + int(lengths[r, k])].decode() for k in range(K)]
+                    for r in range(rows)]
+        tlines, qlines = cut(tl), cut(ql)
+    return rec, lists, tlines, qlines, lengths, rc
+
+
 def hits_align_routes(ctx):
-    """aln_hits_align_last_routes: the used slots the context's last hits_align call sent through a fused kernel and through
-    resident batches -> (fused, batched); (0, 0) before any call."""
+    """aln_hits_align_last_routes: the used slots the context's last hits_align / hits_align_profiles call sent through a fused
+    kernel and through resident batches -> (fused, batched); (0, 0) before any call."""
     out = np.zeros(2, dtype=np.int64)
     _check(lib().aln_hits_align_last_routes(ctx.h, out.ctypes.data_as(_lp)), ctx.h)
     return int(out[0]), int(out[1])

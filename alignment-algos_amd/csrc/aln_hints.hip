@@ -44,6 +44,7 @@ const HintDef kDefs[] = {
     {"zscore_chunk_rows", "ALN_ZSCORE_CHUNK_ROWS", false, &aln_hints::zscore_chunk_rows},
     {"align_chunk_hits", "ALN_ALIGN_CHUNK_HITS", false, &aln_hints::align_chunk_hits},
     {"align_fused_nonlocal", "ALN_ALIGN_FUSED_NONLOCAL", false, &aln_hints::align_fused_nonlocal},
+    {"align_rows_per_chunk", "ALN_ALIGN_ROWS_PER_CHUNK", false, &aln_hints::align_rows_per_chunk},
     {"enum_heavy_first", "ALN_ENUM_HEAVY_FIRST", false, &aln_hints::enum_heavy_first},
     {"enum_pool_retries", "ALN_ENUM_POOL_RETRIES", false, &aln_hints::enum_pool_retries},
     {"enum_waves", "ALN_ENUM_WAVES", false, &aln_hints::enum_waves},

@@ -104,6 +104,7 @@ struct aln_hints {
   int zscore_chunk_rows = 0; // aln_hits_zscores: query rows whose shuffled strings are resident at a time; 0 = by the 1 GiB budget
   int align_chunk_hits = 0;  // aln_hits_align: hit slots whose strips are resident at a time; 0 = by the 1 GiB budget (never lifts it)
   int align_fused_nonlocal = 1;   // 0: aln_hits_align sends hits of the four non-local align types through resident batches
+  int align_rows_per_chunk = 0;   // aln_hits_align_profiles: 1 = every chunk uploads the profile rows of its own hits; 0 = by the 1 GiB budget
   int plane_row_align = 8;   // cells a plane row is padded to when a batch is created (8, 16, 32 or 64)
   int64_t enum_node_cap = 0; // trie nodes of aln_batch_enumerate (0 = default)
   int enum_keep_pools = 1;   // 1: aln_batch_enumerate_all keeps its device pools with the batch (freed with it); 0: frees them when it returns

@@ -91,6 +91,8 @@ struct ScoreRun {
   const aln_submatrix* sub = nullptr; const aln_gap* gap = nullptr;
   const aln_qprofiles* prof = nullptr;          // the query side is profiles
   std::string ph_res; aln_seqs ph = {};         // ... and their placeholder pool
+  const aln_seqs* consensus = nullptr;          // profiles, set before prepare(): a pool of query letters that must share the
+                                                // profiles' offsets (aln_hits_align_profiles); checked, never encoded or scored
   int32_t q_begin = 0, q_end = 0;
   int rows = 0, n_t = 0;
   bool local = false, packed = false;
@@ -113,7 +115,8 @@ struct ScoreRun {
   std::deque<std::vector<int32_t>> qorders;     // the packed kernel's length orders: alive until the caller has synchronised
 
   // the argument checks of aln_score_all_vs_all, in its order; ALN_OK with route == kNothing: no pair to score
-  // (profiles: queries and sub NULL; the checks of aln_score_profiles_vs_all, in its order)
+  // (profiles: queries and sub NULL; the checks of aln_score_profiles_vs_all, in its order, the consensus pool's directly
+  // after the descriptor's)
   int prepare(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub, const aln_gap* gap,
               int32_t q_begin, int32_t q_end, const aln_qprofiles* prof = nullptr);
   int upload_offsets();                         // qoff / toff only (all a caller of the kAllFull route needs on the device)

@@ -314,6 +314,11 @@ int ScoreRun::prepare(aln_ctx* ctx_, const aln_seqs* queries_, const aln_seqs* t
     if (prof->n < 1 || prof->n > 30 || !prof->alphabet || !prof->rows || !prof->offsets || prof->n_seqs < 0) return ALN_E_ARG;
     for (int s = 0; s < prof->n_seqs; ++s)
       if (prof->offsets[s + 1] - prof->offsets[s] < 2) return ALN_E_ARG;
+    if (consensus) {
+      if (consensus->n_seqs != prof->n_seqs || !consensus->offsets || !consensus->residues) return ALN_E_ARG;
+      for (int s = 0; s <= prof->n_seqs; ++s)
+        if (consensus->offsets[s] != prof->offsets[s]) return ALN_E_ARG;
+    }
     ph_res.assign((size_t)prof->offsets[prof->n_seqs], prof->alphabet[0]);
     for (int s = 0; s < prof->n_seqs; ++s) { ph_res[(size_t)prof->offsets[s]] = '^'; ph_res[(size_t)prof->offsets[s + 1] - 1] = '$'; }
     ph.n_seqs = prof->n_seqs; ph.offsets = prof->offsets; ph.residues = ph_res.data();

@@ -28,58 +28,18 @@
 //                               the row observer kept of column T-2; the walk always runs to a cell of row 1 or column 1, then (0,0).
 // Everything the kernels do not take — templates beyond 2048 columns, scoring systems ScoreRun sends through full builds, pairs
 // without an interior, a length class an instantiation was not kept for — goes through resident batches inside the call.
+// aln_hits_align_profiles is the same call for the hits of a profile search: the same host driver (align_block), the kernels of
+// search_align_profile.hip, and batches built from the profiles' planes for what those do not take.
 #include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#include "score_common.h"
+#include "search_align.h"
 
 namespace aln {
 
 constexpr size_t kAlignBudget = (size_t)1 << 30;   // bytes of strips (and of lists, and of lines) resident at a time
-
-struct HitDesc {            // one used slot a fused kernel takes, 32 bytes
-  int32_t q, t;             // sequence indices in the pools
-  int32_t q_end, t_end;     // local: the trusted end cell (non-local: unused, 0)
-  float score;              // local: the slot's score, D[q_end][t_end] must equal it (non-local: unused, 0)
-  int32_t cls;              // template length class 1 .. 8
-  int64_t strip_off;        // first byte of the hit's strip: (q_end - 1) rows of 256 cls bytes (non-local: Q - 3 rows)
-};
-
-// hit of the chunk -> its length class (class_list_kernel, score_common.h)
-struct DescClass {
-  const HitDesc* desc;
-  __device__ int operator()(int h) const { return desc[h].cls; }
-};
-
-struct AlignArgs {
-  const int32_t* list;      // blockIdx.x -> hit of the chunk
-  const HitDesc* desc;
-  uint8_t* strip;
-  int32_t* trav;            // hit h's list in TRAVERSAL order (end -> start) at trav + h * trav_stride * 2
-  int trav_stride;
-  PairResult* res;          // best = score, n_path, status (what gapped_strings_kernel reads)
-  int32_t* same;            // identical aligned residues of the list (calcIdentity's count before its "- 2")
-};
-
-// The sweeps' observer: the strip byte of every cell (see the head of the file), one 32-bit store per lane and group.
-// SCORE_BIT: bit 4, which only the local walk reads.
-template <bool SCORE_BIT>
-struct StripObserver : NoObserver {
-  uint8_t* strip; int pitch;                    // row i (2 .. last) at strip + (i - 2) * pitch
-  uint32_t w = 0;
-  __device__ __forceinline__ void cell(int, int x, int m, int e, int f, int pv, int A, int gmx, int key) {
-    uint32_t b = (m >= max(e, f)) ? 0u : (e >= f ? 1u : 2u);
-    b |= (pv >= A) ? 4u : 0u;
-    b |= (gmx >= key) ? 8u : 0u;
-    if (SCORE_BIT) b |= (m > 0) ? 16u : 0u;
-    w = (x == 0 ? 0u : w) | (b << (8 * x));
-  }
-  __device__ __forceinline__ void group(int i, int r) {       // the lane's four columns: 256 contiguous bytes per wave
-    (reinterpret_cast<uint32_t*>(strip + (size_t)(i - 2) * pitch) + threadIdx.x)[64 * r] = w;
-  }
-};
 
 template <int R>
 __global__ __launch_bounds__(64) void align_local_hit_kernel(ScoreArgs a, AlignArgs g) {
@@ -179,49 +139,6 @@ __global__ __launch_bounds__(64) void align_local_hit_kernel(ScoreArgs a, AlignA
     g.same[hit] = same;
   }
 }
-
-// sweep_global's observer: the strip bytes, and what the final cell's pointer (dpmatrix.h:505-534) needs.
-//   row():  of column T-2 the first row k <= Q-3 holding the maximal insertion key D[k][T-2] + gek k (gek = ge, or 0 under a free
-//           tail insertion).  Row Q-2 costs nothing and equals the match candidate, which comes first: it never wins and is left out.
-//   last(): of row Q-2 the match candidate D[Q-2][T-2] and the best deletion with the smallest column holding it (column T-2
-//           costs nothing and ties the match).
-template <int R>
-struct GlobalObserver : StripObserver<false> {
-  const GlobalCols<R>& k;
-  int free_del, gek, lastk;                     // lastk = Q - 3
-  int ikey = kNegS, irow = 0;                   // irow == 0: no candidate (owning lane only)
-  int match = kNegS, dlv = kNegS, dlc = 0;      // after last(): wave-uniform
-  __device__ __forceinline__ GlobalObserver(const GlobalCols<R>& k_, int free_del_, int gek_, int lastk_)
-      : k(k_), free_del(free_del_), gek(gek_), lastk(lastk_) {}
-  __device__ __forceinline__ void row(int i, const int (&d)[R][4], int) {
-    const int key = sweep_pick<R>(d, k.rs, k.xs, kNegS) + gek * i;
-    const bool up = (int)threadIdx.x == k.ls && i <= lastk && key > ikey;   // strictly greater: the smallest row wins ties
-    ikey = up ? key : ikey;
-    irow = up ? i : irow;
-  }
-  __device__ __forceinline__ void last(const int (&d)[R][4]) {
-    match = __shfl(sweep_pick<R>(d, k.rs, k.xs, kNegS), k.ls);
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        const int c = 4 * (int)threadIdx.x + 256 * r + x;
-        const int len = k.T - 2 - c;
-        const int cost = (len < 1 || free_del) ? 0 : k.gi + k.ge * (len - 1);
-        const int v = k.in[r][x] ? d[r][x] - cost : kNegS;
-        const bool up = v > dlv;                // the lane's columns ascend
-        dlv = up ? v : dlv;
-        dlc = up ? c : dlc;
-      }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {   // value max, column min
-      const int ov = __shfl_xor(dlv, off), oc = __shfl_xor(dlc, off);
-      const bool take = ov > dlv || (ov == dlv && oc < dlc);
-      dlv = take ? ov : dlv;
-      dlc = take ? oc : dlc;
-    }
-  }
-};
 
 template <int R>
 __global__ __launch_bounds__(64) void align_global_hit_kernel(ScoreArgs a, AlignArgs g, int free_del, int free_ins) {
@@ -358,14 +275,13 @@ struct AlignOut {
 };
 
 // The batch route over the listed slots: aln_batch_create + aln_batch_dp + aln_batch_optimal / _strings, grouped under the
-// plane budget exactly as end_cells_through_batches (search_topk.hip) groups them.
+// plane budget exactly as end_cells_through_batches (search_topk.hip) groups them.  prof != nullptr: `queries` holds the query
+// letters (the consensus pool or the placeholder), `sub` is not read and every batch is built from the planes of its own pairs
+// (BatchSim), which its budget counts.
 static int align_through_batches(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
-                                 const aln_gap* gap, const std::vector<int32_t>& qi_all, const std::vector<int32_t>& ti_all,
-                                 const std::vector<size_t>& slot_all, AlignOut& ao) {
+                                 const aln_qprofiles* prof, const aln_gap* gap, const std::vector<int32_t>& qi_all,
+                                 const std::vector<int32_t>& ti_all, const std::vector<size_t>& slot_all, AlignOut& ao) {
   const size_t budget = (size_t)12 << 30, max_pairs = 65536;
-  aln_sim sim = aln_sim();
-  sim.kind = ALN_SIM_SUBMATRIX;
-  sim.sub = *sub;
   std::vector<int32_t> n, st, pairs, len;
   std::vector<float> sc, ident;
   std::vector<char> tl, ql;
@@ -376,16 +292,18 @@ static int align_through_batches(aln_ctx* ctx, const aln_seqs* queries, const al
     while (g1 < qi_all.size() && g1 - g0 < max_pairs) {
       const int64_t Q = queries->offsets[qi_all[g1] + 1] - queries->offsets[qi_all[g1]];
       const int64_t T = templates->offsets[ti_all[g1] + 1] - templates->offsets[ti_all[g1]];
-      const size_t need = (size_t)Q * (size_t)(T + 16) * 8;
+      const size_t need = batch_pair_bytes((size_t)Q, (size_t)T, prof != nullptr);
       if (g1 > g0 && bytes + need > budget) break;
       bytes += need; mq = std::max(mq, Q); mt = std::max(mt, T); msum = std::max(msum, Q + T); ++g1;
     }
     const int32_t np = (int32_t)(g1 - g0), stride = (int32_t)std::max<int64_t>(std::min(mq, mt) + 3, 4), ls = (int32_t)(msum + 2);
     n.assign((size_t)np, 0); st.assign((size_t)np, 0); pairs.assign((size_t)np * stride * 2, 0);
     sc.assign((size_t)np, 0.f); ident.assign((size_t)np, 0.f); len.assign((size_t)np, 0);
+    BatchSim bs;
+    bs.set(sub, prof, templates, (size_t)np, qi_all.data() + g0, ti_all.data() + g0);
     aln_batch* bb = nullptr;
     int rc = aln_batch_create(ctx, queries, templates, np, qi_all.data() + g0, ti_all.data() + g0, 0, &bb);
-    if (rc == ALN_OK) rc = aln_batch_dp(bb, &sim, gap, ALN_FWD, ALN_DP_AUTO, 0);
+    if (rc == ALN_OK) rc = aln_batch_dp(bb, &bs.sim, gap, ALN_FWD, ALN_DP_AUTO, 0);
     if (rc == ALN_OK) rc = aln_batch_optimal(bb, sc.data(), n.data(), pairs.data(), stride, st.data());
     if (rc == ALN_OK) {
       tl.assign((size_t)np * ls, 0); ql.assign((size_t)np * ls, 0);
@@ -402,26 +320,32 @@ static int align_through_batches(aln_ctx* ctx, const aln_seqs* queries, const al
   return ALN_OK;
 }
 
-}  // namespace aln
-
-using namespace aln;
-
-extern "C" int aln_hits_align(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
-                              const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K, const aln_hit* hits,
-                              const int32_t* n_hits, aln_hit_alignment* out, int32_t* pairs, int32_t pair_stride, char* tlines,
-                              char* qlines, int32_t line_stride, int32_t* lengths) {
-  if (ctx) ctx->align_routes[0] = ctx->align_routes[1] = 0;
-  if (!hits || !n_hits || !out || K < 1 || K > 1024) return ALN_E_ARG;
-  if (pairs ? pair_stride < 2 : false) return ALN_E_ARG;
+// the checks both entries make before ScoreRun's: the hit list, the record array, K, and the two optional output groups
+static bool align_outputs_ok(int32_t K, const aln_hit* hits, const int32_t* n_hits, const aln_hit_alignment* out, const int32_t* pairs,
+                             int32_t pair_stride, const char* tlines, const char* qlines, int32_t line_stride, const int32_t* lengths) {
+  if (!hits || !n_hits || !out || K < 1 || K > 1024) return false;
+  if (pairs ? pair_stride < 2 : false) return false;
   const bool want_lines = tlines || qlines;
-  if (want_lines ? (!tlines || !qlines || line_stride < 1) : lengths != nullptr) return ALN_E_ARG;
-  ScoreRun run;
-  int rc = run.prepare(ctx, queries, templates, sub, gap, q_begin, q_end);
-  if (rc != ALN_OK) return rc;
+  if (want_lines ? (!tlines || !qlines || line_stride < 1) : lengths != nullptr) return false;
+  return true;
+}
+
+// The shared body of aln_hits_align and aln_hits_align_profiles (run: prepared; `queries`: the pool the query letters and
+// lengths are read from — run.queries, or the consensus pool of a profile run): the slot checks, the routes, the chunks of
+// fused hits, the batches.
+static int align_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const aln_hit* hits, const int32_t* n_hits,
+                       aln_hit_alignment* out, int32_t* pairs, int32_t pair_stride, char* tlines, char* qlines, int32_t line_stride,
+                       int32_t* lengths) {
+  aln_ctx* ctx = run.ctx;
+  const aln_seqs* templates = run.templates;
+  const aln_qprofiles* prof = run.prof;
+  const int32_t q_begin = run.q_begin;
+  const bool want_lines = tlines || qlines;
+  int rc;
   const int rows = run.rows, n_t = run.n_t;
   if (rows == 0) return ALN_OK;
   const bool fused_ok = run.route == ScoreRun::kFast && (run.local || ctx->hints.align_fused_nonlocal);
-  const unsigned fused_classes = run.local ? kFusedClasses : kFusedGlobalClasses;
+  const unsigned fused_classes = prof ? align_prof_classes(run.local) : (run.local ? kFusedClasses : kFusedGlobalClasses);
   // a fused hit's strip rows and the most entries its list can have
   auto strip_rows = [&](const HitDesc& d) {
     return run.local ? d.q_end - 1 : (int)(queries->offsets[d.q + 1] - queries->offsets[d.q]) - 3;
@@ -504,6 +428,11 @@ extern "C" int aln_hits_align(aln_ctx* ctx, const aln_seqs* queries, const aln_s
     };
 #define STRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(e_); hipStreamSynchronize(ctx->stream); cleanup(); return ALN_E_HIP; } } while (0)
 #define RTRY(expr) do { int r_ = (expr); if (r_ != ALN_OK) { hipStreamSynchronize(ctx->stream); cleanup(); return r_; } } while (0)
+    // profiles: the device rows of [q_begin, q_end) are uploaded once when they fit the budget, else (or under the hint) every
+    // chunk uploads the rows of its own profiles — hits are row-major, so a chunk's rows are one contiguous range
+    if (prof)
+      run.rows_per_slab = ctx->hints.align_rows_per_chunk != 0 ||
+                          ((size_t)(prof->offsets[run.q_end] - prof->offsets[q_begin]) + kProfilePadRows) * 128 > kAlignBudget;
     RTRY(run.upload());
     STRY(hipMalloc((void**)&dstrip, max_strip));
     STRY(hipMalloc((void**)&ddesc, max_n * sizeof(HitDesc)));
@@ -517,21 +446,24 @@ extern "C" int aln_hits_align(aln_ctx* ctx, const aln_seqs* queries, const aln_s
     std::vector<PairDesc> hpd;
     std::vector<StrOut> hso;
     std::vector<char> hlines;
-    if (want_lines) {
+    if (want_lines || prof) {              // the profile kernels count the identity over the characters
       const size_t nq = (size_t)queries->offsets[queries->n_seqs], nt = (size_t)templates->offsets[n_t];
-      STRY(hipMalloc((void**)&dpd, max_n * sizeof(PairDesc)));
-      STRY(hipMalloc((void**)&dso, max_n * sizeof(StrOut)));
-      STRY(hipMalloc((void**)&dlines, max_n * 2 * (size_t)line_stride));
       STRY(hipMalloc((void**)&dqch, std::max<size_t>(nq, 1)));
       STRY(hipMalloc((void**)&dtch, std::max<size_t>(nt, 1)));
       STRY(hipMemcpyAsync(dqch, queries->residues, nq, hipMemcpyHostToDevice, ctx->stream));
       STRY(hipMemcpyAsync(dtch, templates->residues, nt, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (want_lines) {
+      STRY(hipMalloc((void**)&dpd, max_n * sizeof(PairDesc)));
+      STRY(hipMalloc((void**)&dso, max_n * sizeof(StrOut)));
+      STRY(hipMalloc((void**)&dlines, max_n * 2 * (size_t)line_stride));
       hpd.resize(max_n); hso.resize(max_n); hlines.resize(max_n * 2 * (size_t)line_stride);
     }
     for (const Chunk& c : chunks) {
       const int n = (int)c.n;
       ClassOff co = {};
       for (int k = 1; k < 9; ++k) co.off[k] = co.off[k - 1] + c.cls_cnt[k - 1];
+      if (prof && run.rows_per_slab) RTRY(run.upload_profile_rows(fast[c.h0].q, fast[c.h0 + c.n - 1].q + 1));
       STRY(hipMemcpyAsync(ddesc, fast.data() + c.h0, (size_t)n * sizeof(HitDesc), hipMemcpyHostToDevice, ctx->stream));
       STRY(hipMemsetAsync(dfill, 0, 9 * 4, ctx->stream));
       const DescClass dc = {ddesc};
@@ -542,7 +474,9 @@ extern "C" int aln_hits_align(aln_ctx* ctx, const aln_seqs* queries, const aln_s
       for (int k = 1; k <= 8; ++k) {
         if (c.cls_cnt[k] == 0) continue;
         g.list = dlist + co.off[k];
-        if (run.local)
+        if (prof)
+          launch_align_hit_prof(k, run.local, c.cls_cnt[k], ctx->stream, run.a, g, dqch, dtch, run.free_del, run.free_ins);
+        else if (run.local)
           dispatch_r<7>(k, [&](auto rc) {                       // (class 8 never gets here: kFusedClasses)
             hipLaunchKernelGGL(align_local_hit_kernel<decltype(rc)::value>, dim3(c.cls_cnt[k]), dim3(64), 0, ctx->stream, run.a, g);
           });
@@ -591,10 +525,43 @@ extern "C" int aln_hits_align(aln_ctx* ctx, const aln_seqs* queries, const aln_s
     cleanup();
   }
   if (!bq.empty()) {
-    rc = align_through_batches(ctx, queries, templates, sub, gap, bq, bt, bslot, ao);
+    rc = align_through_batches(ctx, queries, templates, run.sub, prof, run.gap, bq, bt, bslot, ao);
     if (rc != ALN_OK) return rc;
   }
   return ao.worst;
+}
+
+}  // namespace aln
+
+using namespace aln;
+
+extern "C" int aln_hits_align(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
+                              const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K, const aln_hit* hits,
+                              const int32_t* n_hits, aln_hit_alignment* out, int32_t* pairs, int32_t pair_stride, char* tlines,
+                              char* qlines, int32_t line_stride, int32_t* lengths) {
+  if (ctx) ctx->align_routes[0] = ctx->align_routes[1] = 0;
+  if (!align_outputs_ok(K, hits, n_hits, out, pairs, pair_stride, tlines, qlines, line_stride, lengths)) return ALN_E_ARG;
+  ScoreRun run;
+  int rc = run.prepare(ctx, queries, templates, sub, gap, q_begin, q_end);
+  if (rc != ALN_OK) return rc;
+  return align_block(run, run.queries, K, hits, n_hits, out, pairs, pair_stride, tlines, qlines, line_stride, lengths);
+}
+
+// The same for the hits of a profile search.  The query letters — the lines and the identity need them, the scores never do —
+// are the caller's consensus pool or, without one, the placeholder pool the run builds for profiles.
+extern "C" int aln_hits_align_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_seqs* consensus,
+                                       const aln_seqs* templates, const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K,
+                                       const aln_hit* hits, const int32_t* n_hits, aln_hit_alignment* out, int32_t* pairs,
+                                       int32_t pair_stride, char* tlines, char* qlines, int32_t line_stride, int32_t* lengths) {
+  if (ctx) ctx->align_routes[0] = ctx->align_routes[1] = 0;
+  if (!profiles || !templates || !gap) return ALN_E_ARG;
+  if (!align_outputs_ok(K, hits, n_hits, out, pairs, pair_stride, tlines, qlines, line_stride, lengths)) return ALN_E_ARG;
+  ScoreRun run;
+  run.consensus = consensus;
+  int rc = run.prepare(ctx, nullptr, templates, nullptr, gap, q_begin, q_end, profiles);
+  if (rc != ALN_OK) return rc;
+  return align_block(run, consensus ? consensus : run.queries, K, hits, n_hits, out, pairs, pair_stride, tlines, qlines,
+                     line_stride, lengths);
 }
 
 extern "C" int aln_hits_align_last_routes(const aln_ctx* ctx, int64_t out[2]) {

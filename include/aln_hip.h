@@ -217,6 +217,9 @@ int aln_has_gfx950(void);
  *   "align_fused_nonlocal"          aln_hits_align: 1 (default) = hits of the four non-local align types are aligned by the fused
  *                                   kernel where it applies; 0 = they all go through resident batches (environment default
  *                                   ALN_ALIGN_FUSED_NONLOCAL).  Same results.
+ *   "align_rows_per_chunk"          aln_hits_align_profiles: 0 (default) = the device rows of the profiles [q_begin, q_end) are
+ *                                   uploaded once when they fit 1 GiB, else chunk by chunk; 1 = every chunk of hits uploads the
+ *                                   rows of its own profiles (environment default ALN_ALIGN_ROWS_PER_CHUNK).  Same results.
  * Unknown key -> ALN_E_ARG.  No hint changes any result. */
 int aln_ctx_set_hint(aln_ctx* ctx, const char* key, int64_t value);
 int aln_ctx_get_hint(const aln_ctx* ctx, const char* key, int64_t* value);
@@ -402,8 +405,8 @@ typedef struct {
  * else — a fractional entry or gap, the bound exceeded, longer templates — goes through resident batches inside the call and so
  * accepts what aln_batch_dp accepts; the Q x T planes of a batch are expanded ON THE HOST for this fallback (it is the 4 B/cell
  * path the entries exist to avoid), and the ~12 GB budget of a batch counts them.
- * The hits of a profile search are aligned today through a resident batch over the hits with the same planes
- * (aln_amd.profile_planes); aln_hits_zscores and aln_hits_align take residue queries only. */
+ * The hits of a profile search are aligned by aln_hits_align_profiles (below, after aln_hits_align), from the same device rows
+ * and again with nothing per cell but the 1 B/cell strip; aln_hits_zscores still takes residue queries only. */
 int aln_score_profiles_vs_all(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_seqs* templates, const aln_gap* gap,
                               int32_t q_begin, int32_t q_end, float* scores);
 int aln_search_topk_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_seqs* templates, const aln_gap* gap,
@@ -484,8 +487,37 @@ int aln_hits_align(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templa
                    aln_hit_alignment* out /* (q_end-q_begin) x K */,
                    int32_t* pairs, int32_t pair_stride /* NULL, or rows x K x pair_stride x 2 int32 */,
                    char* tlines, char* qlines, int32_t line_stride, int32_t* lengths /* all NULL, or as aln_batch_optimal_strings */);
-/* out[0]: the used slots the last aln_hits_align call on this context sent through a fused kernel, out[1]: through resident
- * batches; { 0, 0 } before any call and after a call that failed its checks.  NULL argument: ALN_E_ARG. */
+/* aln_hits_align for the hits of a profile search (aln_search_topk_profiles).  The hit layout and which slots are used, out,
+ * pairs, the line group and lengths, the per-slot statuses and the return value, the local rule (the slot's end cell is trusted;
+ * a sweep score that differs from .score gives the slot ALN_E_ARG, n_pairs 0, and the call goes on), non-local slots ignoring
+ * q_end / t_end / score, q_begin == q_end (ALN_OK, nothing written), the hints "align_chunk_hits" and "align_fused_nonlocal" and
+ * aln_hits_align_last_routes are those of aln_hits_align.
+ * Every value is what aln_batch_create over (the query letters of the row, the template) + aln_batch_dp(ALN_SIM_MATRIX with the
+ * pair's plane as aln_score_profiles_vs_all defines it, gap, ALN_FWD, ALN_DP_AUTO) + aln_batch_optimal /
+ * aln_batch_optimal_strings give, bit for bit.
+ * Query letters: a profile has none, the query line and the identity need them.  `consensus` is an ordinary pool, sentinels
+ * included, with n_seqs == profiles->n_seqs and offsets[s] == profiles->offsets[s] for every s; its letters are never scored
+ * and are not checked against the alphabet.  NULL: the placeholder pool — the profiles' offsets, '^', alphabet[0] for every
+ * interior position, '$'.  The identity counts equal CHARACTERS of the two pools over the list's entries (then - 2), as
+ * aln_batch_optimal_strings does.
+ * Routes: integer rows (of the interior rows of the whole pool) and gaps inside aln_score_all_vs_all's 2^23 bound, Q >= 3 and
+ * T >= 3, a template of up to 2048 columns — one wave per hit, the rows staged from HBM into LDS 8 at a time, 1 byte per cell
+ * into a transient strip (csrc/search_align_profile.hip), for all five align types.  Everything else — fractional rows or gaps,
+ * longer templates, pairs without an interior — goes through resident batches inside the call, whose planes are expanded on
+ * the host and counted in the ~12 GB budget.  The device rows of [q_begin, q_end) are uploaded once when they fit 1 GiB, else
+ * with every chunk of hits (hint "align_rows_per_chunk").
+ * Checks, in this order, nothing written when one fails: NULL profiles / templates / gap / hits / n_hits / out; K outside
+ * 1..1024; pairs with pair_stride < 2; the line group given in part or line_stride < 1 (ALN_E_ARG);
+ * aln_score_profiles_vs_all's, in its order, with the consensus pool — a wrong n_seqs, a NULL member, any differing offset:
+ * ALN_E_ARG — directly after the profile descriptor and before the templates' letters; every n_hits[r] in 0..K; every used
+ * slot's t in [0, n_templates); local, its end cell in range (ALN_E_ARG). */
+int aln_hits_align_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_seqs* consensus /* may be NULL */,
+                            const aln_seqs* templates, const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K,
+                            const aln_hit* hits, const int32_t* n_hits, aln_hit_alignment* out,
+                            int32_t* pairs, int32_t pair_stride,
+                            char* tlines, char* qlines, int32_t line_stride, int32_t* lengths);
+/* out[0]: the used slots the last aln_hits_align / aln_hits_align_profiles call on this context sent through a fused kernel,
+ * out[1]: through resident batches; { 0, 0 } before any call and after a call that failed its checks.  NULL argument: ALN_E_ARG. */
 int aln_hits_align_last_routes(const aln_ctx* ctx, int64_t out[2]);
 
 /* ---- multi-GPU: a length-sorted deal of independent units + ONE collective (RCCL all-gather of scores) ----------- */
