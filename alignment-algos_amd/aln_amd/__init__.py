@@ -95,7 +95,7 @@ EXPORTS = [
     "aln_deal_units", "aln_comm_unique_id", "aln_comm_create", "aln_ctx_create_multi", "aln_comm_destroy", "aln_comm_n_ranks",
     "aln_comm_last_error", "aln_gather_scores", "aln_gather_resident_enqueue", "aln_gather_resident_collect", "aln_search_topk",
     "aln_hits_zscores", "aln_hits_align", "aln_hits_align_last_routes", "aln_score_profiles_vs_all", "aln_search_topk_profiles",
-    "aln_hits_align_profiles",
+    "aln_hits_align_profiles", "aln_hits_zscores_profiles",
 ]
 COMM_ID_BYTES = 128
 
@@ -168,6 +168,9 @@ def lib():
         L.aln_hits_zscores.argtypes = [C.c_void_p, C.POINTER(AlnSeqs), C.POINTER(AlnSeqs), C.POINTER(AlnSubmatrix), C.POINTER(AlnGap),
                                        C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.c_int32, C.c_uint32,
                                        C.POINTER(AlnHitStats)]
+        L.aln_hits_zscores_profiles.argtypes = [C.c_void_p, C.POINTER(AlnQProfiles), C.POINTER(AlnSeqs), C.POINTER(AlnGap), C.c_int32,
+                                                C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.c_int32, C.c_uint32,
+                                                C.POINTER(AlnHitStats)]
         L.aln_hits_align.argtypes = [C.c_void_p, C.POINTER(AlnSeqs), C.POINTER(AlnSeqs), C.POINTER(AlnSubmatrix), C.POINTER(AlnGap),
                                      C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.POINTER(AlnHitAlignment), _ip, C.c_int32,
                                      C.c_char_p, C.c_char_p, C.c_int32, _ip]
@@ -396,6 +399,18 @@ def _fmix32(x):
     return x ^ (x >> 16)
 
 
+def shuffle_order(seed, q_index, s, n):
+    """The order shuffle s of query q_index (its index in the pool) under `seed` puts n interior positions in (include/aln_hip.h:
+    the rule applied to the list 0 .. n-1): position i of the shuffle holds the original position a[i].  aln_hits_zscores
+    permutes residues by it, aln_hits_zscores_profiles the interior rows of a profile.  Pure Python.  -> the list a"""
+    key = _fmix32((_fmix32((_fmix32((seed ^ 0x9E3779B9) & 0xFFFFFFFF) + q_index) & 0xFFFFFFFF) + s) & 0xFFFFFFFF)
+    a = list(range(n))
+    for i in range(n - 1, 0, -1):
+        j = (_fmix32((key + i * 0x9E3779B9) & 0xFFFFFFFF) * (i + 1)) >> 32
+        a[i], a[j] = a[j], a[i]
+    return a
+
+
 def shuffle_query(seed, q_index, s, residues):
     """Shuffle s of query q_index (its index in the pool) under `seed`, as aln_hits_zscores permutes it (include/aln_hip.h):
     pure Python over the interior residues — `residues` comes WITHOUT sentinels.  Reproduces a background sample."""
@@ -430,6 +445,24 @@ def hits_zscores(ctx, queries, templates, hits, n_hits, alphabet, table, gi, ge,
     _check(lib().aln_hits_zscores(ctx.h, C.byref(qpool.c), C.byref(tpool.c), C.byref(sub), C.byref(g), q_begin, q_begin + rows, int(K),
                                   hits.ctypes.data_as(C.POINTER(AlnHit)), _i(n_hits), int(n_shuffles), int(seed) & 0xFFFFFFFF,
                                   stats.ctypes.data_as(C.POINTER(AlnHitStats))), ctx.h)
+    return stats
+
+
+def hits_zscores_profiles(ctx, profiles, templates, hits, n_hits, gi, ge, n_shuffles, seed=0, q_begin=0, align_type=LOCAL):
+    """aln_hits_zscores_profiles: hits_zscores for the hits of a profile search (profiles: a QueryProfiles; hits / n_hits in
+    search_topk_profiles' layout, row r is profile q_begin + r).  Shuffle s of a profile is the profile with its interior rows in
+    the order shuffle_order gives; the device reads one resident copy of the rows in that order.  Integer scoring only.
+    -> stats[rows, K] (fields sum, sumsq, n, z; unused slots 0)."""
+    tpool = templates if isinstance(templates, SeqPool) else SeqPool(templates)
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    n_hits = np.ascontiguousarray(n_hits, dtype=np.int32)
+    rows, K = hits.shape
+    assert n_hits.shape == (rows,)
+    g = _const_gap(align_type, gi, ge)
+    stats = np.zeros((rows, K), dtype=HIT_STATS_DTYPE)
+    _check(lib().aln_hits_zscores_profiles(ctx.h, C.byref(profiles.c), C.byref(tpool.c), C.byref(g), q_begin, q_begin + rows, int(K),
+                                           hits.ctypes.data_as(C.POINTER(AlnHit)), _i(n_hits), int(n_shuffles),
+                                           int(seed) & 0xFFFFFFFF, stats.ctypes.data_as(C.POINTER(AlnHitStats))), ctx.h)
     return stats
 
 

@@ -42,6 +42,7 @@ const HintDef kDefs[] = {
     {"search_slab_rows", "ALN_SEARCH_SLAB_ROWS", false, &aln_hints::search_slab_rows},
     {"search_debug", "ALN_SEARCH_DEBUG", false, &aln_hints::search_debug},
     {"zscore_chunk_rows", "ALN_ZSCORE_CHUNK_ROWS", false, &aln_hints::zscore_chunk_rows},
+    {"zscore_rows_per_chunk", "ALN_ZSCORE_ROWS_PER_CHUNK", false, &aln_hints::zscore_rows_per_chunk},
     {"align_chunk_hits", "ALN_ALIGN_CHUNK_HITS", false, &aln_hints::align_chunk_hits},
     {"align_fused_nonlocal", "ALN_ALIGN_FUSED_NONLOCAL", false, &aln_hints::align_fused_nonlocal},
     {"align_rows_per_chunk", "ALN_ALIGN_ROWS_PER_CHUNK", false, &aln_hints::align_rows_per_chunk},

@@ -102,6 +102,7 @@ struct aln_hints {
   int search_slab_rows = 0;  // aln_search_topk: query rows whose scores are resident at a time; 0 = by the 1 GiB slab budget
   int search_debug = 0;      // 1: aln_search_topk reports its slabs and the device time of scoring / selection / end cells on stderr
   int zscore_chunk_rows = 0; // aln_hits_zscores: query rows whose shuffled strings are resident at a time; 0 = by the 1 GiB budget
+  int zscore_rows_per_chunk = 0;  // aln_hits_zscores_profiles: 1 = every chunk uploads the profile rows of its own query rows; 0 = by the 1 GiB budget
   int align_chunk_hits = 0;  // aln_hits_align: hit slots whose strips are resident at a time; 0 = by the 1 GiB budget (never lifts it)
   int align_fused_nonlocal = 1;   // 0: aln_hits_align sends hits of the four non-local align types through resident batches
   int align_rows_per_chunk = 0;   // aln_hits_align_profiles: 1 = every chunk uploads the profile rows of its own hits; 0 = by the 1 GiB budget

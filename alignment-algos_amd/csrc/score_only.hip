@@ -420,7 +420,9 @@ int ScoreRun::upload_offsets() {
 // Profiles: rows [offsets[qa], offsets[qb]) of the pool, widened to 32 int32 (letters n .. 31 and both sentinel rows 0), 128-byte
 // aligned (hipMalloc's alignment, 128 bytes per row).  INVARIANT: the allocation ends kProfilePadRows rows (zeros) behind the last
 // row — a sweep requests the 8-row chunks its rows 1 .. Q-2 lie in plus the one after (ProfileRows, score_sweep.h), i.e. at most
-// rows .. Q + 13 of its profile, of which the last profile's reach past the pool's end.
+// rows .. Q + 13 of its profile, of which the last profile's reach past the pool's end.  A sweep that reads the rows through an
+// order (PermutedProfileRows, search_zscore_profile.hip) requests ENTRIES 0 .. Q + 13 of that order instead, every one of them a
+// row index below Q: the order is padded (order_stride, same file), and no copy of such a sweep leaves its profile.
 int ScoreRun::upload_profile_rows(int32_t qa, int32_t qb) {
   const int64_t r0 = prof->offsets[qa], r1 = prof->offsets[qb];
   const size_t n_rows = (size_t)(r1 - r0) + kProfilePadRows;

@@ -8,7 +8,8 @@
 //   GlobalCols<R> + sweep_global  the four non-local align types: no clip, "minus infinity" outside the interior,
 //                                 end gaps priced per align type, the final cell included                      (dpmatrix.h:375-534)
 // Users: score_only.hip (scores), search_topk.hip (end cells), search_zscore.hip (one sweep per shuffle), search_align.hip
-// (four or five bits per cell into a strip), score_profile.hip (queries given as position-specific rows).  What a user sees of
+// (four or five bits per cell into a strip), score_profile.hip (queries given as position-specific rows),
+// search_zscore_profile.hip (those rows in a permuted order, through a source of its own).  What a user sees of
 // a sweep beyond its result goes through an observer, where a row's similarities come from through a row source; the packed
 // 16-bit kernel of score_only.hip has its own types and its own sweep.
 #pragma once

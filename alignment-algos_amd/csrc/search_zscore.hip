@@ -13,23 +13,13 @@
 // Query rows are handled a chunk at a time so that the shuffled strings and the accumulators stay below 1 GiB each.  Hits on
 // templates beyond 2048 columns go the way they go in aln_score_all_vs_all: the host materialises the same permutations (its
 // own statement of the rule) and score_through_batches scores them through full builds.
-#include <algorithm>
-#include <cmath>
 #include <cstdio>
 #include <string>
 #include <vector>
 
-#include "score_common.h"
+#include "search_zscore.h"
 
 namespace aln {
-
-constexpr int kShufGroup = 32;                    // most shuffles one wave scores (template state is set up once per wave)
-constexpr size_t kZBudget = (size_t)1 << 30;      // bytes of shuffled strings, and of accumulators, resident at a time
-
-__device__ __forceinline__ uint32_t fmix32(uint32_t x) {
-  x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
-  return x;
-}
 
 struct ShuffleArgs {
   const uint8_t* qcodes; const int64_t* qoff;   // query pool
@@ -60,18 +50,6 @@ __global__ __launch_bounds__(256) void shuffle_queries_kernel(ShuffleArgs a) {
     const uint8_t x = v[i]; v[i] = v[j]; v[j] = x;
   }
 }
-
-// slot (row * K + k) -> the length class of its template, 0: beyond 2048 columns (scored on the host side), -1: unused slot
-// (class_list_kernel, score_common.h)
-struct SlotClass {
-  const int32_t* slot_t; const int64_t* toff;
-  __device__ int operator()(int h) const {
-    const int t = slot_t[h];
-    if (t < 0) return -1;
-    const int T = (int)(toff[t + 1] - toff[t]);
-    return T > 2048 ? 0 : (T + 255) / 256;
-  }
-};
 
 struct ZScoreArgs {
   ScoreArgs a;                                  // a.q_begin: query index of the chunk's row 0; a.qcodes is not read
@@ -125,32 +103,6 @@ __global__ __launch_bounds__(64) void score_shuffled_kernel(ZScoreArgs z) {
     atomicAdd(&z.acc[2 * (size_t)slot], (unsigned long long)sum);
     atomicAdd(&z.acc[2 * (size_t)slot + 1], (unsigned long long)sumsq);
   }
-}
-
-// ---- host side -----------------------------------------------------------------------------------------------------------
-// The permutation once more, on residue characters: the full-build route's strings do not come from the device kernel.
-static uint32_t host_fmix(uint32_t h) {
-  h = (h ^ (h >> 16)) * 0x85EBCA6Bu;
-  h = (h ^ (h >> 13)) * 0xC2B2AE35u;
-  return h ^ (h >> 16);
-}
-static void host_shuffle(uint32_t seed, uint32_t q, uint32_t s, char* seq, int64_t Q) {
-  const uint32_t golden = 0x9E3779B9u;
-  const uint32_t key = host_fmix(host_fmix(host_fmix(seed ^ golden) + q) + s);
-  char* interior = seq + 1;                       // '^' and '$' stay
-  for (int64_t hi = Q - 3; hi > 0; --hi) {
-    const uint64_t draw = host_fmix(key + (uint32_t)hi * golden);
-    const int64_t lo = (int64_t)((draw * (uint64_t)(hi + 1)) >> 32);
-    std::swap(interior[hi], interior[lo]);
-  }
-}
-
-static float z_of(int64_t n, float score, int64_t sum, int64_t sumsq) {
-  if (n < 2) return 0.0f;
-  const __int128 D = (__int128)n * sumsq - (__int128)sum * sum;
-  if (D == 0) return 0.0f;
-  const int64_t N = n * (int64_t)score - sum;
-  return (float)((double)N * sqrt((double)(n - 1) / ((double)n * (double)D)));
 }
 
 }  // namespace aln

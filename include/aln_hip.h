@@ -209,9 +209,13 @@ int aln_has_gfx950(void);
  *   "search_slab_rows"              aln_search_topk, aln_search_topk_profiles: query rows whose scores are resident on the device at a time; 0 (default) = as many as
  *                                   keep the slab's scores (4 B x n_templates per row) and hits (16 B x K per row) below 1 GiB each
  *   "search_debug"                  1: aln_search_topk / aln_search_topk_profiles report their slabs and the device time of scoring / selection / end cells on stderr
- *   "zscore_chunk_rows"             aln_hits_zscores: query rows whose shuffled strings and accumulators are resident on the device at a
- *                                   time; 0 (default) = as many as keep the shuffled pool (n_shuffles x |q| bytes per row with a hit) and the
- *                                   accumulators (16 B x K per row) below 1 GiB each; a larger value is cut to that
+ *   "zscore_chunk_rows"             aln_hits_zscores, aln_hits_zscores_profiles: query rows whose shuffled strings (profiles: shuffle
+ *                                   orders) and accumulators are resident on the device at a time; 0 (default) = as many as keep the
+ *                                   shuffled pool (n_shuffles x |q| bytes per row with a hit; profiles: n_shuffles x 2 B per profile
+ *                                   row, padded) and the accumulators (16 B x K per row) below 1 GiB each; a larger value is cut to that
+ *   "zscore_rows_per_chunk"         aln_hits_zscores_profiles: 0 (default) = the device rows of the profiles [q_begin, q_end) are
+ *                                   uploaded once when they fit 1 GiB, else chunk by chunk; 1 = every chunk of query rows uploads
+ *                                   the rows of its own profiles (environment default ALN_ZSCORE_ROWS_PER_CHUNK).  Same results.
  *   "align_chunk_hits"              aln_hits_align: hit slots whose 1 B/cell strips are resident on the device at a time; 0 (default) = as
  *                                   many as keep the strips, the lists and the lines below 1 GiB each; a value never lifts that budget
  *   "align_fused_nonlocal"          aln_hits_align: 1 (default) = hits of the four non-local align types are aligned by the fused
@@ -406,7 +410,8 @@ typedef struct {
  * accepts what aln_batch_dp accepts; the Q x T planes of a batch are expanded ON THE HOST for this fallback (it is the 4 B/cell
  * path the entries exist to avoid), and the ~12 GB budget of a batch counts them.
  * The hits of a profile search are aligned by aln_hits_align_profiles (below, after aln_hits_align), from the same device rows
- * and again with nothing per cell but the 1 B/cell strip; aln_hits_zscores still takes residue queries only. */
+ * and again with nothing per cell but the 1 B/cell strip; aln_hits_zscores still takes residue queries only: the hits of a
+ * profile search go to aln_hits_zscores_profiles (below, after aln_hits_zscores), which permutes the rows of a profile. */
 int aln_score_profiles_vs_all(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_seqs* templates, const aln_gap* gap,
                               int32_t q_begin, int32_t q_end, float* scores);
 int aln_search_topk_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_seqs* templates, const aln_gap* gap,
@@ -447,6 +452,28 @@ int aln_hits_zscores(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* temp
                      const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K,
                      const aln_hit* hits /* (q_end-q_begin) x K */, const int32_t* n_hits /* q_end-q_begin */,
                      int32_t n_shuffles, uint32_t seed, aln_hit_stats* stats /* (q_end-q_begin) x K */);
+
+/* aln_hits_zscores for the hits of a profile search (aln_search_topk_profiles, or any list in its layout).  The hit layout and
+ * the slots read, the aln_hit_stats record and its padding, the z formula with its exact 128-bit D, n_shuffles in 1..4096, K in
+ * 1..1024, q_begin == q_end (ALN_OK, nothing written) and "returns when stats is complete" are aln_hits_zscores', word for word.
+ * The shuffle permutes ROWS: with L = rows - 2 the interior rows of profile q (its index in the POOL, not the row block) and a =
+ * the rule above applied to the list 0, 1, .., L-1 (same fmix, same key from seed, q, s, same descending swaps), shuffle s of
+ * the profile keeps its two sentinel rows and has as interior row 1 + i the ORIGINAL row 1 + a[i].  sum / sumsq run over the
+ * scores aln_score_profiles_vs_all reports for (shuffle s of profile q, template t), all five align types.  Consequence: for
+ * profiles derived from residue queries under an integral table (row i = the table row of residue i) the result is
+ * byte-identical to aln_hits_zscores on those residues with the same seed.
+ * The permuted profiles are not materialised: the device keeps one copy of a profile's rows and reads it in permuted order
+ * (csrc/search_zscore_profile.hip), 2 B per row and shuffle; the chunking is aln_hits_zscores' (hints "zscore_chunk_rows",
+ * "zscore_rows_per_chunk").  Templates beyond 2048 columns are scored through full builds inside the call.
+ * INTEGER SCORING ONLY: a pool aln_score_profiles_vs_all would send through full builds as a whole (a fractional entry or gap,
+ * its 2^23 bound exceeded) is refused with ALN_E_NOT_INTEGRAL.
+ * Order of the checks, nothing written when one fails: NULL hits / n_hits / stats, K and n_shuffles (ALN_E_ARG);
+ * aln_score_profiles_vs_all's, in its order; every n_hits[r] in 0..K and every used slot's t in [0, n_templates) (ALN_E_ARG);
+ * ALN_E_NOT_INTEGRAL last. */
+int aln_hits_zscores_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_seqs* templates, const aln_gap* gap,
+                              int32_t q_begin, int32_t q_end, int32_t K,
+                              const aln_hit* hits /* (q_end-q_begin) x K */, const int32_t* n_hits /* q_end-q_begin */,
+                              int32_t n_shuffles, uint32_t seed, aln_hit_stats* stats /* (q_end-q_begin) x K */);
 
 /* ---- the alignments of search hits, traced on the device from the end cells the search reported -------------------- */
 /* One record per hit slot.  Unused slots hold { 0, 0, 0.0f, 0.0f }. */
