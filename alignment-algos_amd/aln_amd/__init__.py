@@ -95,7 +95,7 @@ EXPORTS = [
     "aln_deal_units", "aln_comm_unique_id", "aln_comm_create", "aln_ctx_create_multi", "aln_comm_destroy", "aln_comm_n_ranks",
     "aln_comm_last_error", "aln_gather_scores", "aln_gather_resident_enqueue", "aln_gather_resident_collect", "aln_search_topk",
     "aln_hits_zscores", "aln_hits_align", "aln_hits_align_last_routes", "aln_score_profiles_vs_all", "aln_search_topk_profiles",
-    "aln_hits_align_profiles", "aln_hits_zscores_profiles",
+    "aln_hits_align_profiles", "aln_hits_zscores_profiles", "aln_hits_align_multi",
 ]
 COMM_ID_BYTES = 128
 
@@ -177,6 +177,9 @@ def lib():
         L.aln_hits_align_profiles.argtypes = [C.c_void_p, C.POINTER(AlnQProfiles), C.POINTER(AlnSeqs), C.POINTER(AlnSeqs), C.POINTER(AlnGap),
                                               C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.POINTER(AlnHitAlignment), _ip,
                                               C.c_int32, C.c_char_p, C.c_char_p, C.c_int32, _ip]
+        L.aln_hits_align_multi.argtypes = [C.c_void_p, C.POINTER(AlnSeqs), C.POINTER(AlnSeqs), C.POINTER(AlnSubmatrix), C.POINTER(AlnGap),
+                                           C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.c_int32, C.c_float, _ip,
+                                           C.POINTER(AlnHitAlignment), _ip, C.c_int32, C.c_char_p, C.c_char_p, C.c_int32, _ip]
         L.aln_hits_align_last_routes.argtypes = [C.c_void_p, _lp]
         L.aln_hmap2_gap_arrays.argtypes = [_fp, C.c_int64, C.c_float, C.c_float, C.c_float, _fp, _fp]
         L.aln_batch_plane_bytes_per_cell.argtypes = [C.c_void_p]
@@ -563,6 +566,116 @@ def hits_align_profiles(ctx, profiles, templates, hits, n_hits, gi, ge, consensu
                     for r in range(rows)]
         tlines, qlines = cut(tl), cut(ql)
     return rec, lists, tlines, qlines, lengths, rc
+
+
+def hits_align_multi(ctx, queries, templates, hits, n_hits, alphabet, table, gi, ge, max_alignments, min_score=-np.inf, q_begin=0,
+                     align_type=LOCAL, want_pairs=True, want_lines=True, pair_stride=None, line_stride=None):
+    """aln_hits_align_multi: up to N = max_alignments non-intersecting local alignments of every used slot of hits[rows, K]
+    (only the slots' t is read): round 0 is Optimal's alignment, round a >= 1 Optimal's alignment with every aligned pair of
+    the earlier rounds forbidden.  -> rec[rows, K, N] (unreported rounds 0), lists (rows x K x N pair arrays in list order, or
+    None), tlines, qlines (rows x K x N str, or None), lengths[rows, K, N] (or None), n_found[rows, K], rc (0, or the lowest
+    per-alignment status).  Raises only when the call wrote nothing."""
+    qpool = queries if isinstance(queries, SeqPool) else SeqPool(queries)
+    tpool = templates if isinstance(templates, SeqPool) else SeqPool(templates)
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    n_hits = np.ascontiguousarray(n_hits, dtype=np.int32)
+    rows, K = hits.shape
+    N = int(max_alignments)
+    assert n_hits.shape == (rows,)
+    tab = np.ascontiguousarray(table, dtype=np.float32)
+    ab = alphabet.encode()
+    sub = AlnSubmatrix(len(alphabet), ab, _f(tab))
+    g = _const_gap(align_type, gi, ge)
+    maxq = max([len(s) for s in qpool.seqs[q_begin:q_begin + rows]] + [2])
+    maxt = max([len(s) for s in tpool.seqs] + [2])
+    if pair_stride is None:
+        pair_stride = min(maxq, maxt) + 3
+    if line_stride is None:
+        line_stride = maxq + maxt + 2
+    M = max(N, 1)
+    rec, pairs, tl, ql, lengths = _hit_outputs(rows, K * M, pair_stride, line_stride, want_pairs, want_lines)
+    n_found = np.zeros((rows, K), dtype=np.int32)
+    rc = lib().aln_hits_align_multi(ctx.h, C.byref(qpool.c), C.byref(tpool.c), C.byref(sub), C.byref(g), q_begin, q_begin + rows, int(K),
+                                    hits.ctypes.data_as(C.POINTER(AlnHit)), _i(n_hits), N, float(min_score), _i(n_found),
+                                    rec.ctypes.data_as(C.POINTER(AlnHitAlignment)), _i(pairs) if want_pairs else None,
+                                    int(pair_stride) if want_pairs else 0, tl, ql, int(line_stride) if want_lines else 0,
+                                    _i(lengths) if want_lines else None)
+    if rc != 0 and not (rec["status"] == rc).any():
+        _check(rc, ctx.h)
+    rec = rec.reshape(rows, K, M)
+    lists = tlines = qlines = None
+    if want_pairs:
+        pairs = pairs.reshape(rows, K, M, pair_stride, 2)
+        lists = [[[pairs[r, k, a, :min(int(rec["n_pairs"][r, k, a]), pair_stride)].copy() for a in range(M)] for k in range(K)]
+                 for r in range(rows)]
+    if want_lines:
+        lengths = lengths.reshape(rows, K, M)
+
+        def cut(buf):
+            raw = buf.raw
+            return [[[raw[((r * K + k) * M + a) * line_stride:((r * K + k) * M + a) * line_stride + int(lengths[r, k, a])].decode()
+                      for a in range(M)] for k in range(K)] for r in range(rows)]
+        tlines, qlines = cut(tl), cut(ql)
+    return rec, lists, tlines, qlines, lengths, n_found, rc
+
+
+def masked_plane(q, t, alphabet, table, forbidden, value):
+    """The Q x T float32 similarity plane of '^'+q+'$' against '^'+t+'$' (sentinel rows and columns 0) with `value` at every
+    cell of `forbidden` (pairs (i, j)): what a round of hits_align_multi is defined on."""
+    tab = np.asarray(table, dtype=np.float32)
+    idx = {ch: k for k, ch in enumerate(alphabet)}
+    S = np.zeros((len(q) + 2, len(t) + 2), dtype=np.float32)
+    if len(q) and len(t):
+        qi = np.array([idx[c] for c in q], dtype=np.int64)
+        tj = np.array([idx[c] for c in t], dtype=np.int64)
+        S[1:-1, 1:-1] = tab[qi[:, None], tj[None, :]]
+    for i, j in forbidden:
+        S[i, j] = value
+    return S
+
+
+def hits_align_multi_detour(ctx, queries, templates, pairs_qt, alphabet, table, gi, ge, max_alignments, min_score=-np.inf,
+                            group=512):
+    """What hits_align_multi replaces, spelled out with resident batches (host glue only; the comparator of the tests and of
+    tools/bench_align_multi.py): per round one Batch over the (query index, template index) pairs still alive, built by
+    dp_simmatrix from planes expanded and masked on the host, then optimal + optimal_strings (`group` pairs per Batch, so that the
+    host planes stay small).
+    -> per pair the list of its reported rounds, each (score, pair list, identity, tline, qline, status)."""
+    queries = queries if isinstance(queries, SeqPool) else SeqPool(queries)
+    templates = templates if isinstance(templates, SeqPool) else SeqPool(templates)
+    qs, ts = queries.seqs, templates.seqs
+    out = [[] for _ in pairs_qt]
+    forb = [[] for _ in pairs_qt]
+    neg = [0.0] * len(pairs_qt)
+    alive = list(range(len(pairs_qt)))
+    for a in range(int(max_alignments)):
+        if not alive:
+            break
+        nxt = []
+        for g0 in range(0, len(alive), group):
+            part = alive[g0:g0 + group]
+            planes = [masked_plane(qs[pairs_qt[p][0]][1:-1], ts[pairs_qt[p][1]][1:-1], alphabet, table, forb[p], neg[p]) for p in part]
+            b = Batch(ctx, queries, templates, [pairs_qt[p][0] for p in part], [pairs_qt[p][1] for p in part])
+            try:
+                b.dp_simmatrix(planes, LOCAL, gi, ge)
+                scores, lists, status = b.optimal()
+                s2, ident, st2, tl, ql = b.optimal_strings()
+            finally:
+                b.close()
+            for k, p in enumerate(part):
+                sc = scores[k]
+                if not (sc >= min_score and (a == 0 or sc > 0)):
+                    continue
+                out[p].append((sc, lists[k], ident[k], tl[k], ql[k], int(status[k])))
+                if status[k] != 0:
+                    continue
+                Q, T = planes[k].shape
+                if a == 0:
+                    neg[p] = -(float(sc) + 1.0)
+                forb[p] += [(int(i), int(j)) for i, j in lists[k] if 1 <= i <= Q - 2 and 1 <= j <= T - 2]
+                nxt.append(p)
+        alive = nxt
+    return out
 
 
 def hits_align_routes(ctx):

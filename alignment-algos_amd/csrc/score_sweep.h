@@ -9,7 +9,8 @@
 //                                 end gaps priced per align type, the final cell included                      (dpmatrix.h:375-534)
 // Users: score_only.hip (scores), search_topk.hip (end cells), search_zscore.hip (one sweep per shuffle), search_align.hip
 // (four or five bits per cell into a strip), score_profile.hip (queries given as position-specific rows),
-// search_zscore_profile.hip (those rows in a permuted order, through a source of its own).  What a user sees of
+// search_zscore_profile.hip (those rows in a permuted order, through a source of its own), search_align_multi.hip
+// (sweep_local_masked: the local sweep over a plane of forbidden cells).  What a user sees of
 // a sweep beyond its result goes through an observer, where a row's similarities come from through a row source; the packed
 // 16-bit kernel of score_only.hip has its own types and its own sweep.
 #pragma once
@@ -219,6 +220,116 @@ __device__ __forceinline__ int sweep_local(const int* tab, const LocalCols<R>& k
         int h = max(((x == 0) ? uk : bk[r][x - 1]) + s, 0);
         if (r == 0 && x == 1) h = (c == 1) ? max(s, 0) : h;  // column 1 (lane 0 only): free insertion from the origin (:593-599)
         if (masked) h &= k.inm[r][x];                        // columns 0 and >= T-1 stay 0
+        d[r][x] = h;
+      }
+    }
+    finish_row();
+    obs.row(i, d, lmax);
+  }
+  return lmax;
+}
+
+// sweep_local over the table rows with a set of FORBIDDEN cells (search_align_multi.hip): one bit per cell, row i of the pair at
+// mask + i * 8 R words, column c in bit c & 31 of word c / 32 — a lane's four columns of group r are nibble (lane & 7) of word
+// 8 r + lane / 8, one 32-byte-per-8-lanes load per group and row.  D is forced to 0 where the bit is set, directly after the
+// cell is formed and before anything reads it: row 1, column 1 with its free insertion from the origin and the edge groups
+// included; as a gap source or a diagonal predecessor such a cell is then an ordinary zero cell.  MASKED == false reads no
+// mask and is sweep_local's recurrence.  A sibling, not a policy of sweep_local: every existing user of that function compiles
+// from unchanged text (DESIGN 4.8h has the metadata comparison).  The mask is written by earlier rounds of the same wave, so it
+// is read through plain loads, never as __restrict__ / invariant data.
+template <int R, bool MASKED, class Obs>
+__device__ __forceinline__ int sweep_local_masked(const int* tab, const LocalCols<R>& k, const uint8_t* qc, int last,
+                                                  const uint32_t* mask, int (&d)[R][4], Obs&& obs) {
+  const int lane = threadIdx.x;
+  const int cb = 4 * lane;
+  const int gi = k.gi, ge = k.ge, T = k.T;
+  const uint32_t* mlane = mask + (lane >> 3);
+  const int msh = 4 * (lane & 7);
+  int gmx[R][4], cv[R], ak[R][4];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    cv[r] = kNegS;
+#pragma unroll
+    for (int x = 0; x < 4; ++x) { d[r][x] = 0; gmx[r][x] = kNegS; }
+  }
+  int lmax = 0;
+  auto finish_row = [&]() {
+    int sk = kNegS;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      int tk = kNegS;
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        int A = d[r][x] + k.gec[r][x];
+        if (r == 0 && x == 0) A = (lane == 0) ? kNegS : A;   // column 0 is never a source
+        ak[r][x] = A;
+        tk = max(tk, A);
+      }
+      lmax = max(max(lmax, d[r][0]), d[r][1]);
+      lmax = max(max(lmax, d[r][2]), d[r][3]);
+      const int ik = wave_incl_max_s(tk);
+      const int ek = sdpp<0x138>(kNegS, ik);
+      cv[r] = max(sk, ek);
+      sk = max(sk, __builtin_amdgcn_readlane(ik, 63));
+    }
+  };
+  if (last >= 1) {
+    const int qrow = (int)qc[1] * 128;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      uint32_t nib = 0;
+      if (MASKED) nib = mlane[8 * R + 8 * r] >> msh;
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        const int h = max(sweep_tab_at(tab, qrow, k.code4[r][x]), 0);
+        d[r][x] = ((nib >> x) & 1u) ? 0 : (h & k.inm[r][x]);
+      }
+    }
+    finish_row();
+    obs.row(1, d, lmax);
+  }
+  int qcode_next = (last >= 2) ? (int)qc[2] : 0;
+  for (int i = 2; i <= last; ++i) {
+    const int qrow = qcode_next * 128;
+    if (i + 1 <= last) qcode_next = (int)qc[i + 1];
+    uint32_t mw[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) mw[r] = MASKED ? mlane[(size_t)i * (8 * R) + 8 * r] : 0u;
+    const int roff = gi + ge * (i - 2);
+    const int rowB = ge * (i - 1);
+    int bk[R][4];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      int pv = cv[r];
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        const int m = d[r][x];
+        const int A = ak[r][x];
+        const int e = pv - k.ekc[r][x];
+        const int f = gmx[r][x] - roff;
+        bk[r][x] = max(max(m, e), f);
+        obs.cell(r, x, m, e, f, pv, A, gmx[r][x], m + rowB);
+        pv = max(pv, A);
+        gmx[r][x] = max(gmx[r][x], m + rowB);
+      }
+      obs.group(i, r);
+    }
+    int prev_k = 0;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      int uk = sdpp<0x138>(0, bk[r][3]);
+      if (r > 0) uk = (lane == 0) ? prev_k : uk;
+      prev_k = __builtin_amdgcn_readlane(bk[r][3], 63);
+      const bool masked = (r == 0) || (256 * (r + 1) > T - 1);
+      const uint32_t nib = mw[r] >> msh;
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        const int c = cb + 256 * r + x;
+        const int s = sweep_tab_at(tab, qrow, k.code4[r][x]);
+        int h = max(((x == 0) ? uk : bk[r][x - 1]) + s, 0);
+        if (r == 0 && x == 1) h = (c == 1) ? max(s, 0) : h;  // column 1 (lane 0 only): free insertion from the origin
+        if (masked) h &= k.inm[r][x];                        // columns 0 and >= T-1 stay 0
+        if (MASKED) h = ((nib >> x) & 1u) ? 0 : h;           // a forbidden cell
         d[r][x] = h;
       }
     }

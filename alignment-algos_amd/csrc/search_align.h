@@ -1,9 +1,13 @@
 // search_align.h — what the fused hit-alignment kernels of search_align.hip (residue queries, the table in LDS) and
 // search_align_profile.hip (position-specific queries, rows staged into LDS) share: how a hit is described to a kernel, where its
-// results go, and the two observers that turn a row sweep into the strip bytes and the final cell's pointer.  The strip byte is
+// results go and how a slot's record, list and lines are written for the caller (AlignOut, shared with search_align_multi.hip),
+// and the two observers that turn a row sweep into the strip bytes and the final cell's pointer.  The strip byte is
 // defined at the head of search_align.hip.  The two walks are restated in each file, not shared (a helper that takes
 // the kernel's state by reference costs registers).
 #pragma once
+#include <algorithm>
+#include <cstring>
+
 #include "score_common.h"
 
 namespace aln {
@@ -92,6 +96,47 @@ struct GlobalObserver : StripObserver<false> {
     }
   }
 };
+
+// Where the results of one slot go, and how they are written (the same for both routes)
+struct AlignOut {
+  aln_hit_alignment* out; int32_t* pairs; int32_t pair_stride; char* tlines; char* qlines; int32_t line_stride; int32_t* lengths;
+  int worst = ALN_OK;
+  void note(int st) { if (st < worst) worst = st; }
+  // list: n entries, reversed when flip; line: the slot's two lines of `len` chars (nullptr: none)
+  void put(size_t slot, int status, float score, float identity, int n, const int32_t* list, bool flip, int len, const char* tl,
+           const char* ql) {
+    aln_hit_alignment o = {n, status, score, identity};
+    if (pairs && status == ALN_OK) {
+      const int m = std::min(n, pair_stride);
+      int32_t* dst = pairs + slot * (size_t)pair_stride * 2;
+      for (int k = 0; k < m; ++k) {
+        const int sk = flip ? n - 1 - k : k;
+        dst[2 * k] = list[2 * sk]; dst[2 * k + 1] = list[2 * sk + 1];
+      }
+      if (n > pair_stride) o.status = ALN_E_OVERFLOW;
+    }
+    if (tlines) {
+      char* t = tlines + slot * (size_t)line_stride; char* q = qlines + slot * (size_t)line_stride;
+      int wrote = 0;
+      if (status == ALN_OK && len >= line_stride) o.status = ALN_E_OVERFLOW;
+      else if (status == ALN_OK && len > 0 && tl) { memcpy(t, tl, (size_t)len); memcpy(q, ql, (size_t)len); wrote = len; }
+      t[wrote] = 0; q[wrote] = 0;
+      if (lengths) lengths[slot] = wrote;
+    }
+    out[slot] = o;
+    note(o.status);
+  }
+};
+
+// the checks both entries make before ScoreRun's: the hit list, the record array, K, and the two optional output groups
+inline bool align_outputs_ok(int32_t K, const aln_hit* hits, const int32_t* n_hits, const aln_hit_alignment* out, const int32_t* pairs,
+                             int32_t pair_stride, const char* tlines, const char* qlines, int32_t line_stride, const int32_t* lengths) {
+  if (!hits || !n_hits || !out || K < 1 || K > 1024) return false;
+  if (pairs ? pair_stride < 2 : false) return false;
+  const bool want_lines = tlines || qlines;
+  if (want_lines ? (!tlines || !qlines || line_stride < 1) : lengths != nullptr) return false;
+  return true;
+}
 
 // search_align_profile.hip: the profile twins of align_local_hit_kernel / align_global_hit_kernel for the n hits of g.list, all of
 // length class r (s: ScoreArgs of a profile run, score_profile.hip; qch / tch: the character pools of the query letters and the

@@ -243,37 +243,6 @@ __global__ __launch_bounds__(64) void align_global_hit_kernel(ScoreArgs a, Align
 constexpr unsigned kFusedClasses = 0x0FEu;                   // bit R set: class R runs in align_local_hit_kernel<R>
 constexpr unsigned kFusedGlobalClasses = 0x1FEu;             // bit R set: class R runs in align_global_hit_kernel<R>
 
-// Where the results of one slot go, and how they are written (the same for both routes)
-struct AlignOut {
-  aln_hit_alignment* out; int32_t* pairs; int32_t pair_stride; char* tlines; char* qlines; int32_t line_stride; int32_t* lengths;
-  int worst = ALN_OK;
-  void note(int st) { if (st < worst) worst = st; }
-  // list: n entries, reversed when flip; line: the slot's two lines of `len` chars (nullptr: none)
-  void put(size_t slot, int status, float score, float identity, int n, const int32_t* list, bool flip, int len, const char* tl,
-           const char* ql) {
-    aln_hit_alignment o = {n, status, score, identity};
-    if (pairs && status == ALN_OK) {
-      const int m = std::min(n, pair_stride);
-      int32_t* dst = pairs + slot * (size_t)pair_stride * 2;
-      for (int k = 0; k < m; ++k) {
-        const int sk = flip ? n - 1 - k : k;
-        dst[2 * k] = list[2 * sk]; dst[2 * k + 1] = list[2 * sk + 1];
-      }
-      if (n > pair_stride) o.status = ALN_E_OVERFLOW;
-    }
-    if (tlines) {
-      char* t = tlines + slot * (size_t)line_stride; char* q = qlines + slot * (size_t)line_stride;
-      int wrote = 0;
-      if (status == ALN_OK && len >= line_stride) o.status = ALN_E_OVERFLOW;
-      else if (status == ALN_OK && len > 0 && tl) { memcpy(t, tl, (size_t)len); memcpy(q, ql, (size_t)len); wrote = len; }
-      t[wrote] = 0; q[wrote] = 0;
-      if (lengths) lengths[slot] = wrote;
-    }
-    out[slot] = o;
-    note(o.status);
-  }
-};
-
 // The batch route over the listed slots: aln_batch_create + aln_batch_dp + aln_batch_optimal / _strings, grouped under the
 // plane budget exactly as end_cells_through_batches (search_topk.hip) groups them.  prof != nullptr: `queries` holds the query
 // letters (the consensus pool or the placeholder), `sub` is not read and every batch is built from the planes of its own pairs
@@ -318,16 +287,6 @@ static int align_through_batches(aln_ctx* ctx, const aln_seqs* queries, const al
     g0 = g1;
   }
   return ALN_OK;
-}
-
-// the checks both entries make before ScoreRun's: the hit list, the record array, K, and the two optional output groups
-static bool align_outputs_ok(int32_t K, const aln_hit* hits, const int32_t* n_hits, const aln_hit_alignment* out, const int32_t* pairs,
-                             int32_t pair_stride, const char* tlines, const char* qlines, int32_t line_stride, const int32_t* lengths) {
-  if (!hits || !n_hits || !out || K < 1 || K > 1024) return false;
-  if (pairs ? pair_stride < 2 : false) return false;
-  const bool want_lines = tlines || qlines;
-  if (want_lines ? (!tlines || !qlines || line_stride < 1) : lengths != nullptr) return false;
-  return true;
 }
 
 // The shared body of aln_hits_align and aln_hits_align_profiles (run: prepared; `queries`: the pool the query letters and

@@ -1,0 +1,467 @@
+// search_align_multi.hip — several non-intersecting local alignments per search hit, on the device: aln_hits_align_multi (gfx950).
+//
+// Round 0 of a hit is Optimal's alignment (what aln_hits_align returns); round a >= 1 is Optimal's alignment of the matrix in
+// which every aligned pair of the rounds before is forbidden: D = 0 there, everything else the reference's recurrence
+// (include/aln_hip.h has the rule).  One wave per hit runs all rounds inside one launch:
+//   align_local_multi_kernel<R>   per round: sweep_local_masked (score_sweep.h) over ALL rows 1 .. Q-2 — the end cell is not
+//                                 known in advance — observed for the strip byte of every cell (search_align.hip defines it) and
+//                                 for find_max's end cell (score_local_end_kernel's rule) in the SAME sweep; the walk back of
+//                                 align_local_hit_kernel through the strip; the list, the identity count, and one bit per
+//                                 aligned pair into the hit's forbidden-cell plane (1/8 B per cell) for the rounds that follow.
+// The walk needs no change: a forbidden cell holds 0 when the next row's strip byte takes its score bit, so a walk that reaches
+// one — diagonally or as a gap source — stops before it, as Optimal's does (optimal.h:100).  The walk is restated here, not
+// shared with align_local_hit_kernel (a helper that takes the kernel's state by reference costs registers, and that
+// kernel's metadata must not move).
+//   class_list_kernel, gapped_strings_kernel   unchanged: the lines of every (hit, round) list in one launch.
+// Templates beyond the kept classes, scoring systems ScoreRun sends through full builds and pairs without an interior go
+// through resident batches inside the call, round by round, on ALN_SIM_MATRIX planes expanded and masked on the host.
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "search_align_multi.h"
+
+namespace aln {
+
+constexpr size_t kMultiBudget = (size_t)1 << 30;   // bytes of strips (of masks, of lists, of lines) resident at a time
+
+template <int R>
+__global__ __launch_bounds__(64) void align_local_multi_kernel(ScoreArgs a, MultiArgs g) {
+  __shared__ int tab[32 * 32];
+  const int lane = threadIdx.x;
+  for (int k = lane; k < 32 * 32; k += 64) tab[k] = a.table32[k];
+  __syncthreads();
+  const int hit = g.list[blockIdx.x];
+  const MultiDesc hd = g.desc[hit];
+  const int ti = hd.t, qi = hd.q;
+  const uint8_t* __restrict__ qc = a.qcodes + a.qoff[qi];
+  const uint8_t* __restrict__ tc = a.tcodes + a.toff[ti];
+  const int Q = (int)(a.qoff[qi + 1] - a.qoff[qi]), T = (int)(a.toff[ti + 1] - a.toff[ti]);   // Q >= 3, T >= 3: the host's routing
+  constexpr int kPitch = 256 * R;
+  uint8_t* strip = g.strip + hd.strip_off;      // row i (2 .. Q-2) at strip + (i - 2) * kPitch
+  uint32_t* mask = g.mask + hd.mask_off;        // row i (0 .. Q-1) at mask + i * 8 R
+  const int cap = g.trav_stride;
+
+  LocalCols<R> cols;
+  cols.load(tc, T, a.gi, a.ge);
+  int found = 0;
+  for (int round = 0; round < g.n_rounds; ++round) {
+    // ---- the sweep: strip bytes + find_max (optimal.h:108-124; the reduction and the seed rule of score_local_end_kernel) ------
+    int d[R][4];
+    StripFirstMaxObserver ob;
+    ob.strip = strip; ob.pitch = kPitch;
+    int lmax;
+    if (round == 0) lmax = sweep_local_masked<R, false>(tab, cols, qc, Q - 2, mask, d, ob);   // nothing is forbidden yet: no mask loads
+    else lmax = sweep_local_masked<R, true>(tab, cols, qc, Q - 2, mask, d, ob);
+    int m = lmax;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) m = max(m, __shfl_xor(m, o));
+    int br = (lmax == m) ? ob.lrow : 0x7FFFFFFF;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) br = min(br, __shfl_xor(br, o));
+    int bc = (lmax == m && ob.lrow == br) ? ob.lcol : 0x7FFFFFFF;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) bc = min(bc, __shfl_xor(bc, o));
+    int seed = 0;
+    if (m > 0) {
+      const int cl = T - 2;
+      seed = __shfl(sweep_pick<R>(d, cl / 256, cl & 3, 0), (cl & 255) >> 2);
+    }
+    const bool seed_wins = (m == 0) || (seed == m);
+    const int q_end = seed_wins ? Q - 2 : br, t_end = seed_wins ? T - 2 : bc;
+    // reported: score >= min_score and, after round 0, > 0; the first round that is not ends the hit (all wave-uniform)
+    if ((round > 0 && m <= 0) || !((float)m >= g.min_score)) break;
+    __threadfence();                                           // the walk's lanes read bytes other lanes stored
+    __syncthreads();
+
+    // ---- the walk back (optimal.h:79-105), emitted in traversal order; every aligned pair is forbidden from now on ------------
+    const bool more = round + 1 < g.n_rounds;
+    int32_t* o = g.trav + ((size_t)hit * g.n_rounds + round) * cap * 2;
+    int n = 0, same = 0;
+    auto forbid = [&](int q, int t) {                          // an alignment has one cell per row: no two lanes share a word
+      if (more) atomicOr(mask + (size_t)q * (8 * R) + (t >> 5), 1u << (t & 31));
+    };
+    auto emit1 = [&](int q, int t) {
+      if (lane == 0 && n < cap) { o[2 * n] = q; o[2 * n + 1] = t; same += (qc[q] == tc[t]) ? 1 : 0; }
+      ++n;
+    };
+    auto at = [&](int i, int c) -> uint32_t { return strip[(size_t)(i - 2) * kPitch + c]; };
+    emit1(Q - 1, T - 1);
+    emit1(q_end, t_end);
+    if (lane == 0) forbid(q_end, t_end);
+    int i = q_end, j = t_end;
+    bool origin = false;                                       // the walk stopped at a cell with both indices > 0: (0,0) is prepended
+    while (i >= 2 && j >= 2) {                                 // a cell of row 1 or column 1 points at (0,0), whose score is 0
+      // lane l looks at cell (i - l, j - l): its byte holds the move into it and the score bit of its diagonal predecessor
+      const int ci = i - lane, cj = j - lane;
+      const bool valid = ci >= 2 && cj >= 2;
+      const uint32_t b = valid ? at(ci, cj - 1) : 0u;
+      const bool go = valid && (b & 3u) == 0u && (b & 16u) != 0u;
+      const unsigned long long mm = __ballot(go);
+      const int L = (~mm == 0ull) ? 64 : __builtin_ctzll(~mm); // lanes 0 .. L-1 step diagonally onto a cell that is kept
+      if (lane < L) {
+        const int k = n + lane;
+        if (k < cap) { o[2 * k] = ci - 1; o[2 * k + 1] = cj - 1; same += (qc[ci - 1] == tc[cj - 1]) ? 1 : 0; }
+        forbid(ci - 1, cj - 1);                                // a list the caller's stride truncates still forbids all its cells
+      }
+      n += L; i -= L; j -= L;
+      if (L == 64) continue;
+      if (i < 2 || j < 2) break;
+      const uint32_t bL = (uint32_t)__shfl((int)b, L);
+      const uint32_t mv = bL & 3u;
+      if (mv == 0u) { origin = true; break; }                  // a match whose predecessor's score is <= 0 (a forbidden cell among them)
+      int pi, pj; uint32_t bp = 0;
+      if (mv == 1u) {                                          // deletion: the smallest column of row i-1 holding the maximal key
+        pi = i - 1; pj = 0;
+        for (int k0 = j - 2; k0 >= 1; k0 -= 64) {
+          const int kk = k0 - lane;
+          const uint32_t bb = kk >= 1 ? at(i, kk) : 0u;
+          const unsigned long long clr = __ballot((bb & 4u) == 0u);
+          if (clr) { const int l0 = __builtin_ctzll(clr); pj = k0 - l0; bp = (uint32_t)__shfl((int)bb, l0); break; }
+        }
+      } else {                                                 // insertion: the smallest row of column j-1 holding the maximal key
+        pj = j - 1; pi = 0;
+        for (int k0 = i - 2; k0 >= 1; k0 -= 64) {
+          const int kk = k0 - lane;
+          const uint32_t bb = kk >= 1 ? at(kk + 1, pj) : 0u;
+          const unsigned long long clr = __ballot((bb & 8u) == 0u);
+          if (clr) { const int l0 = __builtin_ctzll(clr); pi = k0 - l0; bp = (uint32_t)__shfl((int)bb, l0); break; }
+        }
+      }
+      if (pi < 1 || pj < 1) break;                             // (cannot happen: row 1 and column 1 always clear their bits)
+      if ((bp & 16u) == 0u) { origin = true; break; }          // the source's score is <= 0
+      emit1(pi, pj);
+      if (lane == 0) forbid(pi, pj);
+      i = pi; j = pj;
+    }
+    if (origin) emit1(0, 0);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) same += __shfl_xor(same, off);
+    if (lane == 0) {
+      PairResult res = {};
+      res.best = (float)m; res.corner = 0.f; res.best_q = q_end; res.best_t = t_end;
+      res.n_path = n;
+      res.status = n <= cap ? 0 : ALN_E_OVERFLOW;
+      g.res[(size_t)hit * g.n_rounds + round] = res;
+      g.same[(size_t)hit * g.n_rounds + round] = same;
+    }
+    ++found;
+    __threadfence();                                           // the next sweep's lanes read mask words other lanes changed, and
+    __syncthreads();                                           // overwrite strip bytes this walk read
+  }
+  if (lane == 0) g.n_found[hit] = found;
+}
+
+// The instantiations kept: every one compiles without scratch memory and without VGPR spills (DESIGN 4.8h has the table).
+constexpr unsigned kMultiClasses = 0x0FEu;                   // bit R set: class R runs in align_local_multi_kernel<R>
+
+// Is round `a` with this score reported?
+static bool reported(int a, float score, float min_score) { return score >= min_score && (a == 0 || score > 0.f); }
+
+// The batch route, round by round over the slots still alive: aln_batch_create + aln_batch_dp + aln_batch_optimal / _strings,
+// grouped under the plane budget as align_through_batches (search_align.hip) groups them.  Round 0 is built from the table
+// itself, exactly as aln_hits_align builds it; later rounds from the pairs' Q x T planes, expanded on the host with every
+// forbidden cell at -(round 0's score + 1).
+static int multi_through_batches(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
+                                 const aln_gap* gap, const std::vector<int32_t>& qi_all, const std::vector<int32_t>& ti_all,
+                                 const std::vector<size_t>& slot_all, int N, float min_score, int32_t* n_found, AlignOut& ao) {
+  const size_t budget = (size_t)12 << 30, max_pairs = 65536;
+  int idx[256];
+  for (int i = 0; i < 256; ++i) idx[i] = -1;
+  for (int i = 0; i < sub->n; ++i) idx[(unsigned char)sub->alphabet[i]] = i;
+  const size_t np_all = qi_all.size();
+  std::vector<std::vector<int32_t>> forbidden(np_all);       // per pair: (i, j) of every aligned pair so far
+  std::vector<float> neg(np_all, 0.f);
+  std::vector<size_t> alive(np_all);
+  for (size_t p = 0; p < np_all; ++p) alive[p] = p;
+  std::vector<int32_t> n, st, pairs, len, gq, gt;
+  std::vector<float> sc, ident, planes;
+  std::vector<int64_t> plane_off;
+  std::vector<char> tl, ql;
+  for (int a = 0; a < N && !alive.empty(); ++a) {
+    std::vector<size_t> next;
+    size_t g0 = 0;
+    while (g0 < alive.size()) {
+      size_t g1 = g0, bytes = 0;
+      int64_t mq = 0, mt = 0, msum = 0;
+      while (g1 < alive.size() && g1 - g0 < max_pairs) {
+        const size_t p = alive[g1];
+        const int64_t Q = queries->offsets[qi_all[p] + 1] - queries->offsets[qi_all[p]];
+        const int64_t T = templates->offsets[ti_all[p] + 1] - templates->offsets[ti_all[p]];
+        const size_t need = batch_pair_bytes((size_t)Q, (size_t)T, a > 0);
+        if (g1 > g0 && bytes + need > budget) break;
+        bytes += need; mq = std::max(mq, Q); mt = std::max(mt, T); msum = std::max(msum, Q + T); ++g1;
+      }
+      const int32_t np = (int32_t)(g1 - g0), stride = (int32_t)std::max<int64_t>(std::min(mq, mt) + 3, 4), ls = (int32_t)(msum + 2);
+      n.assign((size_t)np, 0); st.assign((size_t)np, 0); pairs.assign((size_t)np * stride * 2, 0);
+      sc.assign((size_t)np, 0.f); ident.assign((size_t)np, 0.f); len.assign((size_t)np, 0);
+      gq.resize((size_t)np); gt.resize((size_t)np);
+      for (int32_t k = 0; k < np; ++k) { gq[k] = qi_all[alive[g0 + k]]; gt[k] = ti_all[alive[g0 + k]]; }
+      aln_sim sim = aln_sim();
+      if (a == 0) { sim.kind = ALN_SIM_SUBMATRIX; sim.sub = *sub; }
+      else {
+        plane_off.assign((size_t)np + 1, 0);
+        for (int32_t k = 0; k < np; ++k) {
+          const int64_t Q = queries->offsets[gq[k] + 1] - queries->offsets[gq[k]], T = templates->offsets[gt[k] + 1] - templates->offsets[gt[k]];
+          plane_off[k + 1] = plane_off[k] + Q * T;
+        }
+        planes.assign((size_t)plane_off[np], 0.f);
+        for (int32_t k = 0; k < np; ++k) {
+          const int64_t q0 = queries->offsets[gq[k]], Q = queries->offsets[gq[k] + 1] - q0;
+          const int64_t t0 = templates->offsets[gt[k]], T = templates->offsets[gt[k] + 1] - t0;
+          float* S = planes.data() + plane_off[k];
+          for (int64_t i = 1; i <= Q - 2; ++i) {
+            const float* row = sub->table + (size_t)idx[(unsigned char)queries->residues[q0 + i]] * sub->n;   // letters: checked by prepare()
+            for (int64_t j = 1; j <= T - 2; ++j) S[i * T + j] = row[idx[(unsigned char)templates->residues[t0 + j]]];
+          }
+          const size_t p = alive[g0 + k];
+          for (size_t e = 0; e < forbidden[p].size(); e += 2) S[(int64_t)forbidden[p][e] * T + forbidden[p][e + 1]] = neg[p];
+        }
+        sim.kind = ALN_SIM_MATRIX; sim.planes = planes.data(); sim.plane_off = plane_off.data();
+      }
+      aln_batch* bb = nullptr;
+      int rc = aln_batch_create(ctx, queries, templates, np, gq.data(), gt.data(), 0, &bb);
+      if (rc == ALN_OK) rc = aln_batch_dp(bb, &sim, gap, ALN_FWD, ALN_DP_AUTO, 0);
+      if (rc == ALN_OK) rc = aln_batch_optimal(bb, sc.data(), n.data(), pairs.data(), stride, st.data());
+      if (rc == ALN_OK) {
+        tl.assign((size_t)np * ls, 0); ql.assign((size_t)np * ls, 0);
+        rc = aln_batch_optimal_strings(bb, nullptr, ident.data(), nullptr, tl.data(), ql.data(), ls, len.data());
+        if (rc == ALN_E_STARTPAIR) rc = ALN_OK;                 // reported per alignment
+      }
+      if (bb) aln_batch_destroy(bb);
+      if (rc != ALN_OK) return rc;
+      for (int32_t k = 0; k < np; ++k) {
+        const size_t p = alive[g0 + k];
+        if (!reported(a, sc[k], min_score)) continue;           // the hit ends here
+        const int cnt = st[k] == 0 ? n[k] : 0;
+        const int32_t* list = pairs.data() + (size_t)k * stride * 2;
+        ao.put(slot_all[p] * (size_t)N + a, st[k], sc[k], ident[k], cnt, list, false, len[k], tl.data() + (size_t)k * ls,
+               ql.data() + (size_t)k * ls);
+        n_found[slot_all[p]] = a + 1;
+        if (st[k] != 0 || a + 1 >= N) continue;                 // no list to forbid: the hit ends with this record
+        const int64_t Q = queries->offsets[gq[k] + 1] - queries->offsets[gq[k]], T = templates->offsets[gt[k] + 1] - templates->offsets[gt[k]];
+        if (a == 0) neg[p] = -(sc[k] + 1.f);
+        for (int e = 0; e < cnt; ++e)
+          if (list[2 * e] >= 1 && list[2 * e] <= Q - 2 && list[2 * e + 1] >= 1 && list[2 * e + 1] <= T - 2) {
+            forbidden[p].push_back(list[2 * e]); forbidden[p].push_back(list[2 * e + 1]);
+          }
+        next.push_back(p);
+      }
+      g0 = g1;
+    }
+    alive.swap(next);
+  }
+  return ALN_OK;
+}
+
+static int multi_block(ScoreRun& run, int32_t K, const aln_hit* hits, const int32_t* n_hits, int N, float min_score,
+                       int32_t* n_found, aln_hit_alignment* out, int32_t* pairs, int32_t pair_stride, char* tlines, char* qlines,
+                       int32_t line_stride, int32_t* lengths) {
+  aln_ctx* ctx = run.ctx;
+  const aln_seqs* queries = run.queries;
+  const aln_seqs* templates = run.templates;
+  const int32_t q_begin = run.q_begin;
+  const bool want_lines = tlines || qlines;
+  const int rows = run.rows, n_t = run.n_t;
+  if (rows == 0) return ALN_OK;
+  const bool fused_ok = run.route == ScoreRun::kFast;
+  auto q_len = [&](int q) { return (int64_t)(queries->offsets[q + 1] - queries->offsets[q]); };
+  auto t_len = [&](int t) { return (int64_t)(templates->offsets[t + 1] - templates->offsets[t]); };
+
+  // one walk: validate every used slot and describe it for its route (nothing is written before it ends)
+  std::vector<MultiDesc> fast;
+  std::vector<size_t> fast_slot;
+  std::vector<int32_t> bq, bt;
+  std::vector<size_t> bslot;
+  for (int r = 0; r < rows; ++r) {
+    if (n_hits[r] < 0 || n_hits[r] > K) return ALN_E_ARG;
+    const int q = q_begin + r;
+    const int64_t Q = q_len(q);
+    for (int k = 0; k < n_hits[r]; ++k) {
+      const size_t slot = (size_t)r * K + k;
+      const aln_hit& h = hits[slot];
+      if (h.t < 0 || h.t >= n_t) return ALN_E_ARG;
+      const int64_t T = t_len(h.t);
+      const int cls = (int)((T + 255) / 256);
+      if (fused_ok && Q >= 3 && T >= 3 && T <= 2048 && ((kMultiClasses >> cls) & 1u)) {
+        MultiDesc d = {q, h.t, cls, 0, 0, 0};
+        fast.push_back(d); fast_slot.push_back(slot);
+      } else { bq.push_back(q); bt.push_back(h.t); bslot.push_back(slot); }
+    }
+  }
+  ctx->align_routes[0] = (int64_t)fast.size(); ctx->align_routes[1] = (int64_t)bq.size();
+  AlignOut ao = {out, pairs, pair_stride, tlines, qlines, line_stride, lengths};
+  for (size_t s = 0; s < (size_t)rows * K; ++s) {              // every record starts as "not reported"
+    n_found[s] = 0;
+    for (int a = 0; a < N; ++a) {
+      const size_t e = s * N + a;
+      const aln_hit_alignment zero = {0, 0, 0.0f, 0.0f};
+      out[e] = zero;
+      if (tlines) { tlines[e * (size_t)line_stride] = 0; qlines[e * (size_t)line_stride] = 0; }
+      if (lengths) lengths[e] = 0;
+    }
+  }
+
+  // chunks of fused hits: strips, masks, lists x N and lines x N each stay below the budget; the hint only asks for fewer
+  struct Chunk { size_t h0, n; size_t strip, mask; int trav_stride; int cls_cnt[9]; };
+  std::vector<Chunk> chunks;
+  {
+    const size_t forced = ctx->hints.align_chunk_hits > 0 ? (size_t)ctx->hints.align_chunk_hits : (size_t)-1;
+    Chunk c = {0, 0, 0, 0, 4, {0, 0, 0, 0, 0, 0, 0, 0, 0}};
+    for (size_t h = 0; h < fast.size(); ++h) {
+      MultiDesc& d = fast[h];
+      const int64_t Q = q_len(d.q), T = t_len(d.t);
+      const size_t need = (size_t)std::max<int64_t>(Q - 3, 1) * 256 * (size_t)d.cls;
+      const size_t mneed = (size_t)Q * 8 * (size_t)d.cls;       // words
+      const int lc = (int)std::min(Q, T) + 1;
+      const int ts = std::max(c.trav_stride, lc);
+      const bool full = c.n >= forced || c.strip + need > kMultiBudget || (c.mask + mneed) * 4 > kMultiBudget ||
+                        (c.n + 1) * (size_t)N * ts * 8 > kMultiBudget ||
+                        (want_lines && (c.n + 1) * (size_t)N * 2 * (size_t)line_stride > kMultiBudget);
+      if (c.n > 0 && full) {
+        chunks.push_back(c);
+        c = {h, 0, 0, 0, 4, {0, 0, 0, 0, 0, 0, 0, 0, 0}};
+      }
+      d.strip_off = (int64_t)c.strip; d.mask_off = (int64_t)c.mask;
+      c.strip += need; c.mask += mneed; c.n++; c.cls_cnt[d.cls]++;
+      c.trav_stride = std::max(c.trav_stride, lc);
+    }
+    if (c.n > 0) chunks.push_back(c);
+  }
+
+  if (!chunks.empty()) {
+    size_t max_n = 1, max_strip = 1, max_mask = 1, max_trav = 1;
+    for (const Chunk& c : chunks) {
+      max_n = std::max(max_n, c.n); max_strip = std::max(max_strip, c.strip); max_mask = std::max(max_mask, c.mask);
+      max_trav = std::max(max_trav, c.n * (size_t)N * c.trav_stride * 2);
+    }
+    const size_t max_e = max_n * (size_t)N;
+    uint8_t* dstrip = nullptr; uint32_t* dmask = nullptr; MultiDesc* ddesc = nullptr;
+    int32_t *dlist = nullptr, *dfill = nullptr, *dtrav = nullptr, *dsame = nullptr, *dfound = nullptr;
+    PairResult* dres = nullptr; PairDesc* dpd = nullptr; StrOut* dso = nullptr; char *dlines = nullptr, *dqch = nullptr, *dtch = nullptr;
+    auto cleanup = [&]() {
+      hipFree(dstrip); hipFree(dmask); hipFree(ddesc); hipFree(dlist); hipFree(dfill); hipFree(dtrav); hipFree(dsame); hipFree(dfound);
+      hipFree(dres); hipFree(dpd); hipFree(dso); hipFree(dlines); hipFree(dqch); hipFree(dtch);
+      run.release();
+    };
+#define STRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(e_); hipStreamSynchronize(ctx->stream); cleanup(); return ALN_E_HIP; } } while (0)
+#define RTRY(expr) do { int r_ = (expr); if (r_ != ALN_OK) { hipStreamSynchronize(ctx->stream); cleanup(); return r_; } } while (0)
+    RTRY(run.upload());
+    STRY(hipMalloc((void**)&dstrip, max_strip));
+    STRY(hipMalloc((void**)&dmask, max_mask * 4));
+    STRY(hipMalloc((void**)&ddesc, max_n * sizeof(MultiDesc)));
+    STRY(hipMalloc((void**)&dlist, max_n * 4));
+    STRY(hipMalloc((void**)&dfill, 9 * 4));
+    STRY(hipMalloc((void**)&dtrav, max_trav * 4));
+    STRY(hipMalloc((void**)&dsame, max_e * 4));
+    STRY(hipMalloc((void**)&dfound, max_n * 4));
+    STRY(hipMalloc((void**)&dres, max_e * sizeof(PairResult)));
+    std::vector<PairResult> hres(max_e);
+    std::vector<int32_t> hsame(max_e), hfound(max_n), htrav(max_trav);
+    std::vector<PairDesc> hpd;
+    std::vector<StrOut> hso;
+    std::vector<char> hlines;
+    if (want_lines) {
+      const size_t nq = (size_t)queries->offsets[queries->n_seqs], nt = (size_t)templates->offsets[n_t];
+      STRY(hipMalloc((void**)&dqch, std::max<size_t>(nq, 1)));
+      STRY(hipMalloc((void**)&dtch, std::max<size_t>(nt, 1)));
+      STRY(hipMemcpyAsync(dqch, queries->residues, nq, hipMemcpyHostToDevice, ctx->stream));
+      STRY(hipMemcpyAsync(dtch, templates->residues, nt, hipMemcpyHostToDevice, ctx->stream));
+      STRY(hipMalloc((void**)&dpd, max_e * sizeof(PairDesc)));
+      STRY(hipMalloc((void**)&dso, max_e * sizeof(StrOut)));
+      STRY(hipMalloc((void**)&dlines, max_e * 2 * (size_t)line_stride));
+      hpd.resize(max_e); hso.resize(max_e); hlines.resize(max_e * 2 * (size_t)line_stride);
+    }
+    for (const Chunk& c : chunks) {
+      const int n = (int)c.n;
+      const size_t ne = (size_t)n * N;
+      ClassOff co = {};
+      for (int k = 1; k < 9; ++k) co.off[k] = co.off[k - 1] + c.cls_cnt[k - 1];
+      STRY(hipMemcpyAsync(ddesc, fast.data() + c.h0, (size_t)n * sizeof(MultiDesc), hipMemcpyHostToDevice, ctx->stream));
+      STRY(hipMemsetAsync(dfill, 0, 9 * 4, ctx->stream));
+      STRY(hipMemsetAsync(dmask, 0, c.mask * 4, ctx->stream));
+      STRY(hipMemsetAsync(dres, 0, ne * sizeof(PairResult), ctx->stream));   // rounds that are not reported: n_path 0, empty lines
+      STRY(hipMemsetAsync(dsame, 0, ne * 4, ctx->stream));
+      const MultiClass mc = {ddesc};
+      hipLaunchKernelGGL(class_list_kernel<MultiClass>, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, mc, n, co, dfill, dlist);
+      STRY(hipGetLastError());
+      MultiArgs g = {};
+      g.desc = ddesc; g.strip = dstrip; g.mask = dmask; g.trav = dtrav; g.trav_stride = c.trav_stride; g.n_rounds = N;
+      g.min_score = min_score; g.res = dres; g.same = dsame; g.n_found = dfound;
+      for (int k = 1; k <= 8; ++k) {
+        if (c.cls_cnt[k] == 0) continue;
+        g.list = dlist + co.off[k];
+        dispatch_r<7>(k, [&](auto rc) {                         // (class 8 never gets here: kMultiClasses)
+          hipLaunchKernelGGL(align_local_multi_kernel<decltype(rc)::value>, dim3(c.cls_cnt[k]), dim3(64), 0, ctx->stream, run.a, g);
+        });
+        STRY(hipGetLastError());
+      }
+      if (want_lines) {
+        for (int h = 0; h < n; ++h) {
+          const MultiDesc& d = fast[c.h0 + h];
+          PairDesc pd = {};
+          pd.Q = (int32_t)q_len(d.q); pd.T = (int32_t)t_len(d.t);
+          pd.q_seq = d.q; pd.t_seq = d.t; pd.q_off = queries->offsets[d.q]; pd.t_off = templates->offsets[d.t];
+          for (int a = 0; a < N; ++a) hpd[(size_t)h * N + a] = pd;
+        }
+        STRY(hipMemcpyAsync(dpd, hpd.data(), ne * sizeof(PairDesc), hipMemcpyHostToDevice, ctx->stream));
+        StrParams prm = {c.trav_stride, 1, 0, line_stride};
+        RTRY(launch_gapped_strings(ctx, (int)ne, dpd, dres, dtrav, dqch, dtch, dlines, dso, prm));
+        STRY(hipMemcpyAsync(hso.data(), dso, ne * sizeof(StrOut), hipMemcpyDeviceToHost, ctx->stream));
+        STRY(hipMemcpyAsync(hlines.data(), dlines, ne * 2 * (size_t)line_stride, hipMemcpyDeviceToHost, ctx->stream));
+      }
+      STRY(hipMemcpyAsync(hres.data(), dres, ne * sizeof(PairResult), hipMemcpyDeviceToHost, ctx->stream));
+      STRY(hipMemcpyAsync(hsame.data(), dsame, ne * 4, hipMemcpyDeviceToHost, ctx->stream));
+      STRY(hipMemcpyAsync(hfound.data(), dfound, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+      if (pairs) STRY(hipMemcpyAsync(htrav.data(), dtrav, ne * c.trav_stride * 8, hipMemcpyDeviceToHost, ctx->stream));
+      STRY(hipStreamSynchronize(ctx->stream));                 // the host vectors above are read by the copies until here
+      for (int h = 0; h < n; ++h) {
+        const MultiDesc& d = fast[c.h0 + h];
+        const int64_t Q = q_len(d.q), T = t_len(d.t);
+        const size_t slot = fast_slot[c.h0 + h];
+        n_found[slot] = hfound[h];
+        for (int a = 0; a < hfound[h]; ++a) {
+          const size_t e = (size_t)h * N + a;
+          const PairResult& r = hres[e];
+          const float ident = r.status == 0 ? float(hsame[e] - 2) / float(std::min(Q, T) - 2) * 100.f : 0.f;   // alignment.h:864
+          int len = 0; const char* tl = nullptr; const char* ql = nullptr; int st = r.status;
+          if (want_lines && st == 0) {
+            if (hso[e].err == ALN_E_OVERFLOW) len = line_stride;             // put() turns it into the alignment's status
+            else if (hso[e].err != ALN_OK) st = hso[e].err;
+            else { len = hso[e].length; tl = hlines.data() + e * 2 * line_stride; ql = tl + line_stride; }
+          }
+          ao.put(slot * (size_t)N + a, st, r.best, ident, r.n_path, htrav.data() + e * c.trav_stride * 2, true, len, tl, ql);
+        }
+      }
+    }
+#undef STRY
+#undef RTRY
+    cleanup();
+  }
+  if (!bq.empty()) {
+    const int rc = multi_through_batches(ctx, queries, templates, run.sub, run.gap, bq, bt, bslot, N, min_score, n_found, ao);
+    if (rc != ALN_OK) return rc;
+  }
+  return ao.worst;
+}
+
+}  // namespace aln
+
+using namespace aln;
+
+extern "C" int aln_hits_align_multi(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
+                                    const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K, const aln_hit* hits,
+                                    const int32_t* n_hits, int32_t max_alignments, float min_score, int32_t* n_found,
+                                    aln_hit_alignment* out, int32_t* pairs, int32_t pair_stride, char* tlines, char* qlines,
+                                    int32_t line_stride, int32_t* lengths) {
+  if (ctx) ctx->align_routes[0] = ctx->align_routes[1] = 0;
+  if (!n_found || max_alignments < 1 || max_alignments > 16) return ALN_E_ARG;
+  if (!align_outputs_ok(K, hits, n_hits, out, pairs, pair_stride, tlines, qlines, line_stride, lengths)) return ALN_E_ARG;
+  ScoreRun run;
+  int rc = run.prepare(ctx, queries, templates, sub, gap, q_begin, q_end);
+  if (rc != ALN_OK) return rc;
+  if (!run.local) return ALN_E_ARG;
+  return multi_block(run, K, hits, n_hits, max_alignments, min_score, n_found, out, pairs, pair_stride, tlines, qlines, line_stride,
+                     lengths);
+}

@@ -543,7 +543,48 @@ int aln_hits_align_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, const a
                             const aln_hit* hits, const int32_t* n_hits, aln_hit_alignment* out,
                             int32_t* pairs, int32_t pair_stride,
                             char* tlines, char* qlines, int32_t line_stride, int32_t* lengths);
-/* out[0]: the used slots the last aln_hits_align / aln_hits_align_profiles call on this context sent through a fused kernel,
+/* Several NON-INTERSECTING local alignments per hit (the second, third .. HSP of a hit; Waterman-Eggert's declumping restated on
+ * the reference's recurrence).  ALN_LOCAL only.  For one pair — query of Q residues, template of T, sentinels counted — under a
+ * table and constant affine gaps:
+ *   round 0      is Optimal's alignment of the pair: exactly what aln_hits_align returns for the hit aln_search_topk reports.
+ *   round a >= 1 is Optimal's alignment (find_max + the local walk, optimal.h:79-124) of the DPMatrix built from a CHANGED
+ *                similarity plane: every aligned pair (i, j) of the rounds 0 .. a-1 holds a value so negative that the cell
+ *                clips to 0.  An aligned pair is a list entry with 1 <= i <= Q-2 and 1 <= j <= T-2; the closing (Q-1, T-1) and the
+ *                origin (0, 0) are none.  Any value <= -(score of round 0) does — masking only lowers cells, so no later cell
+ *                exceeds that score — and the result does not depend on which is used.  Equivalently: D = 0 at those cells and
+ *                everything else follows the reference's recurrence and candidate order.  A gap may jump over a forbidden
+ *                cell; as a gap source a forbidden cell is an ordinary zero cell.
+ *   reporting    a round is reported when its score is >= min_score (-INFINITY: no bound) and, for a >= 1, also > 0.  Round 0
+ *                is reported even with score 0 (the seed-cell list), as aln_hits_align does.  The first round that is not
+ *                reported ends the hit; at most max_alignments (N, 1..16) rounds are reported.
+ * Consequences: the reported alignments of a hit share no aligned pair; their scores never increase from one round to the next;
+ * every reported value is, bit for bit, what aln_batch_create over the pair + aln_batch_dp(ALN_SIM_MATRIX with the round's plane,
+ * gap, ALN_FWD, ALN_DP_AUTO) + aln_batch_optimal / aln_batch_optimal_strings give.
+ * The hit layout and which slots are used are aln_hits_align's, but only a slot's .t is read: end cell and score are recomputed,
+ * so any (row, template) list will do.  Slot s = r * K + k, round a: the record is out[s * N + a], the pair list at
+ * pairs + (s * N + a) * pair_stride * 2, the lines at tlines / qlines + (s * N + a) * line_stride, their length lengths[s * N + a];
+ * "not wanted" (NULL pairs, the line group) as in aln_hits_align.  n_found[s] is the number of reported rounds (0 for an unused
+ * slot); records >= n_found[s] hold { 0, 0, 0.0f, 0.0f }, empty lines and length 0.  A list longer than pair_stride or a line
+ * that does not fit line_stride gives THAT alignment ALN_E_OVERFLOW as in aln_hits_align; an overflowing list still forbids all
+ * of its cells — it is truncated for the caller only.
+ * Routes: integer table and gaps inside aln_score_all_vs_all's 2^23 bound, Q >= 3, T >= 3 and a template of up to 1792 columns —
+ * one wave per hit runs all rounds in one launch (csrc/search_align_multi.hip): per round one register-resident sweep of rows
+ * 1 .. Q-2 that honours a 1-bit-per-cell plane of forbidden cells and yields both the end cell and the 1 B/cell strip, then the
+ * walk back, which also sets the bits.  Everything else — longer templates, fractional tables or gaps, values beyond the bound,
+ * pairs without an interior — goes through resident batches inside the call, round by round, on planes expanded and masked on
+ * the host (~12 GB of planes at a time), so the call accepts what aln_search_topk accepts.  aln_hits_align_last_routes reports
+ * this call's slots too.  No hint of its own: chunks obey "align_chunk_hits" and 1 GiB each of strips, masks, lists and lines.
+ * Checks, in this order, nothing written when one fails: NULL n_found, max_alignments outside 1..16 and aln_hits_align's first
+ * group (ALN_E_ARG); aln_score_all_vs_all's, in its order; an align type other than ALN_LOCAL (ALN_E_ARG); every n_hits[r] in
+ * 0..K and every used slot's t in [0, n_templates) (ALN_E_ARG).  q_begin == q_end: ALN_OK, nothing written.  Returns when every
+ * output is complete: the lowest per-alignment status, ALN_OK when all are 0. */
+int aln_hits_align_multi(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
+                         const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K,
+                         const aln_hit* hits, const int32_t* n_hits,
+                         int32_t max_alignments /* N, 1..16 */, float min_score /* -INFINITY: none */,
+                         int32_t* n_found /* rows x K */, aln_hit_alignment* out /* rows x K x N */,
+                         int32_t* pairs, int32_t pair_stride, char* tlines, char* qlines, int32_t line_stride, int32_t* lengths);
+/* out[0]: the used slots the last aln_hits_align / aln_hits_align_profiles / aln_hits_align_multi call on this context sent through a fused kernel,
  * out[1]: through resident batches; { 0, 0 } before any call and after a call that failed its checks.  NULL argument: ALN_E_ARG. */
 int aln_hits_align_last_routes(const aln_ctx* ctx, int64_t out[2]);
 
