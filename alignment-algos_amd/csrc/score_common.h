@@ -3,6 +3,7 @@
 // work is listed and launched by template length class, and ScoreRun, the host side of one all-vs-all scoring call cut into
 // steps so that a caller can leave the scores of a slab of query rows in a device buffer of its own.
 #pragma once
+#include <algorithm>
 #include <deque>
 #include <string>
 #include <type_traits>
@@ -146,5 +147,28 @@ struct BatchSim {
 };
 // bytes of planes a Q x T pair of such a batch holds on the device (score + pointer planes, padded rows; + the similarity plane)
 inline size_t batch_pair_bytes(size_t Q, size_t T, bool with_sim_plane) { return Q * (T + 16) * (with_sim_plane ? 12 : 8); }
+
+constexpr size_t kBatchPlaneBudget = (size_t)12 << 30;   // bytes of planes one resident batch of the full-build route may hold
+constexpr size_t kBatchMaxPairs = 65536;                 // ... and the most pairs of a batch cut from a pair list
+
+// Cuts the pair list (qi[k], ti[k]), k < n, into successive resident batches [g0, g1): the first pair is always taken, then the
+// group stops before the pair that would exceed the plane budget, or at kBatchMaxPairs.  Start from BatchGroup(); next() is false
+// when the list is used up.  max_q, max_t, max_sum: the largest Q, T and Q + T of the group (list and line strides).
+struct BatchGroup {
+  size_t g0 = 0, g1 = 0;
+  int64_t max_q = 0, max_t = 0, max_sum = 0;
+  bool next(const aln_seqs* queries, const aln_seqs* templates, const int32_t* qi, const int32_t* ti, size_t n, bool with_sim_plane) {
+    g0 = g1; max_q = max_t = max_sum = 0;
+    size_t bytes = 0;
+    while (g1 < n && g1 - g0 < kBatchMaxPairs) {
+      const int64_t Q = queries->offsets[qi[g1] + 1] - queries->offsets[qi[g1]];
+      const int64_t T = templates->offsets[ti[g1] + 1] - templates->offsets[ti[g1]];
+      const size_t need = batch_pair_bytes((size_t)Q, (size_t)T, with_sim_plane);
+      if (g1 > g0 && bytes + need > kBatchPlaneBudget) break;
+      bytes += need; max_q = std::max(max_q, Q); max_t = std::max(max_t, T); max_sum = std::max(max_sum, Q + T); ++g1;
+    }
+    return g1 > g0;
+  }
+};
 
 }  // namespace aln

@@ -239,7 +239,7 @@ int score_through_batches(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs*
                           const aln_gap* gap, int32_t q_begin, int32_t q_end, const std::vector<int32_t>& tlist, float* scores,
                           const int32_t* col, size_t ld, const aln_qprofiles* prof) {
   if (ld == 0) ld = (size_t)templates->n_seqs;
-  const size_t budget = (size_t)12 << 30;
+  const size_t budget = kBatchPlaneBudget;      // (no BatchGroup: the pairs are made as they are grouped, and there is no pair limit)
   std::vector<int32_t> qi, tix;
   std::vector<float> sc;
   std::vector<int32_t> st;

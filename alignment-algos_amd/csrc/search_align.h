@@ -1,9 +1,10 @@
-// search_align.h — what the fused hit-alignment kernels of search_align.hip (residue queries, the table in LDS) and
-// search_align_profile.hip (position-specific queries, rows staged into LDS) share: how a hit is described to a kernel, where its
-// results go and how a slot's record, list and lines are written for the caller (AlignOut, shared with search_align_multi.hip),
-// and the two observers that turn a row sweep into the strip bytes and the final cell's pointer.  The strip byte is
-// defined at the head of search_align.hip.  The two walks are restated in each file, not shared (a helper that takes
-// the kernel's state by reference costs registers).
+// search_align.h — what the fused hit-alignment kernels of search_align.hip (residue queries, the table in LDS),
+// search_align_profile.hip (position-specific queries, rows staged into LDS) and search_align_multi.hip (several rounds per
+// hit) share: how a hit is described to a kernel, where its results go and how a slot's record, list and lines are written for
+// the caller (AlignOut, put_fused, pair_desc), the two observers that turn a row sweep into the strip bytes and the final
+// cell's pointer, and strip_walk, the walk back through the strip that all five kernels call.  The strip byte is defined at
+// the head of search_align.hip.  DESIGN 4.8 found that a helper which takes a kernel's ROW ARRAYS by reference costs
+// registers; the walk runs after the sweep on scalar state only (strip, i, j, n), and sharing it costs none.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -95,7 +96,67 @@ struct GlobalObserver : StripObserver<false> {
       dlc = take ? oc : dlc;
     }
   }
+  // The final cell's pointer (dpmatrix.h:505-534), after the sweep: match, deletions from (Q-2, k) k ascending, insertions from
+  // (k, T-2) k ascending; a later candidate wins only when strictly greater.  (i, j): the cell the walk starts from.
+  __device__ __forceinline__ void final_cell(int free_ins, int& i, int& j) const {
+    const int ir = __shfl(irow, k.ls), ik = __shfl(ikey, k.ls);
+    const int ilv = ir == 0 ? kNegS : (free_ins ? ik : ik - (k.gi + k.ge * lastk));
+    i = lastk + 1; j = k.T - 2;
+    if (dlv > match) j = dlc;
+    if (ilv > max(match, dlv)) { i = ir; j = k.T - 2; }
+  }
 };
+
+// The walk back through a hit's strip (row i, 2 .. last, at strip + (i - 2) * PITCH; the byte: head of search_align.hip) from
+// the cell (i, j) the caller has already emitted — optimal.h:79-105 under LOCAL, optimal.h:56-74 otherwise.  Entry k of the
+// list, in traversal order (end -> start), is handed to sink(k, q, t) by exactly one lane; n counts the entries.  A cell of
+// row 1 or column 1 points at (0,0), whose score is 0 (dpmatrix.h:579-599): the walk ends there and the caller emits (0,0)
+// itself where its list has it.  Returns true when a LOCAL walk stopped at a cell with both indices > 0 — Optimal's local
+// walk stops BEFORE a cell whose score is <= 0 (optimal.h:100), bit 4 — and (0,0) is prepended.  Every branch is wave-uniform.
+template <int PITCH, bool LOCAL, class Sink>
+__device__ __forceinline__ bool strip_walk(const uint8_t* strip, int i, int j, int& n, Sink&& sink) {
+  const int lane = threadIdx.x;
+  auto at = [&](int ii, int c) -> uint32_t { return strip[(size_t)(ii - 2) * PITCH + c]; };
+  while (i >= 2 && j >= 2) {
+    // lane l looks at cell (i - l, j - l): its byte holds the move into it and (LOCAL) the score bit of its diagonal predecessor
+    const int ci = i - lane, cj = j - lane;
+    const bool valid = ci >= 2 && cj >= 2;
+    const uint32_t b = valid ? at(ci, cj - 1) : 0u;
+    const bool go = valid && (b & 3u) == 0u && (!LOCAL || (b & 16u) != 0u);
+    const unsigned long long m = __ballot(go);
+    const int L = (~m == 0ull) ? 64 : __builtin_ctzll(~m);   // lanes 0 .. L-1 step diagonally (LOCAL: onto a cell that is kept)
+    if (lane < L) sink(n + lane, ci - 1, cj - 1);
+    n += L; i -= L; j -= L;
+    if (L == 64) continue;
+    if (i < 2 || j < 2) break;
+    const uint32_t mv = (uint32_t)__shfl((int)b, L) & 3u;    // not LOCAL: 1 or 2, lane L is valid and did not go
+    if (LOCAL && mv == 0u) return true;                      // a match whose predecessor's score is <= 0 (a forbidden cell among them)
+    int pi, pj; uint32_t bp = 0;
+    if (mv == 1u) {                                          // deletion: the smallest column of row i-1 holding the maximal key
+      pi = i - 1; pj = 0;                                    // (the smallest k wins ties: leftwards from column j-2 while bit 2 is set)
+      for (int k0 = j - 2; k0 >= 1; k0 -= 64) {
+        const int kk = k0 - lane;
+        const uint32_t bb = kk >= 1 ? at(i, kk) : 0u;
+        const unsigned long long clr = __ballot((bb & 4u) == 0u);
+        if (clr) { const int l0 = __builtin_ctzll(clr); pj = k0 - l0; if (LOCAL) bp = (uint32_t)__shfl((int)bb, l0); break; }
+      }
+    } else {                                                 // insertion: the smallest row of column j-1 holding the maximal key
+      pj = j - 1; pi = 0;                                    // (upwards from row i-2 while bit 3 is set)
+      for (int k0 = i - 2; k0 >= 1; k0 -= 64) {
+        const int kk = k0 - lane;
+        const uint32_t bb = kk >= 1 ? at(kk + 1, pj) : 0u;
+        const unsigned long long clr = __ballot((bb & 8u) == 0u);
+        if (clr) { const int l0 = __builtin_ctzll(clr); pi = k0 - l0; if (LOCAL) bp = (uint32_t)__shfl((int)bb, l0); break; }
+      }
+    }
+    if (pi < 1 || pj < 1) break;                             // (cannot happen: row 1 and column 1 always clear their bits)
+    if (LOCAL && (bp & 16u) == 0u) return true;              // the source's score is <= 0
+    if (lane == 0) sink(n, pi, pj);
+    ++n;
+    i = pi; j = pj;
+  }
+  return false;
+}
 
 // Where the results of one slot go, and how they are written (the same for both routes)
 struct AlignOut {
@@ -127,6 +188,29 @@ struct AlignOut {
     note(o.status);
   }
 };
+
+// One record of a fused kernel -> AlignOut::put.  r, same: what the kernel left; Q, T: the pair's lengths; trav: its list in
+// traversal order; so, lines: what gapped_strings_kernel left for it and its two lines of line_stride chars (nullptr: no lines)
+inline void put_fused(AlignOut& ao, size_t slot, const PairResult& r, int same, int64_t Q, int64_t T, const int32_t* trav,
+                      const StrOut* so, const char* lines, int line_stride) {
+  const float ident = r.status == 0 ? float(same - 2) / float(std::min(Q, T) - 2) * 100.f : 0.f;   // alignment.h:864
+  int len = 0; const char* tl = nullptr; const char* ql = nullptr; int st = r.status;
+  if (so && st == 0) {
+    if (so->err == ALN_E_OVERFLOW) len = line_stride;          // put() turns it into the record's status
+    else if (so->err != ALN_OK) st = so->err;
+    else { len = so->length; tl = lines; ql = tl + line_stride; }
+  }
+  ao.put(slot, st, r.best, ident, r.n_path, trav, true, len, tl, ql);
+}
+
+// what gapped_strings_kernel reads of a pair (q, t) whose list a fused kernel wrote
+inline PairDesc pair_desc(const aln_seqs* queries, const aln_seqs* templates, int q, int t) {
+  PairDesc pd = {};
+  pd.Q = (int32_t)(queries->offsets[q + 1] - queries->offsets[q]);
+  pd.T = (int32_t)(templates->offsets[t + 1] - templates->offsets[t]);
+  pd.q_seq = q; pd.t_seq = t; pd.q_off = queries->offsets[q]; pd.t_off = templates->offsets[t];
+  return pd;
+}
 
 // the checks both entries make before ScoreRun's: the hit list, the record array, K, and the two optional output groups
 inline bool align_outputs_ok(int32_t K, const aln_hit* hits, const int32_t* n_hits, const aln_hit_alignment* out, const int32_t* pairs,

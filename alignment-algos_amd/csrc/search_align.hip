@@ -79,57 +79,13 @@ __global__ __launch_bounds__(64) void align_local_hit_kernel(ScoreArgs a, AlignA
   int32_t* o = g.trav + (size_t)hit * g.trav_stride * 2;
   const int cap = g.trav_stride;
   int n = 0, same = 0;
-  auto emit1 = [&](int q, int t) {
-    if (lane == 0 && n < cap) { o[2 * n] = q; o[2 * n + 1] = t; same += (qc[q] == tc[t]) ? 1 : 0; }
-    ++n;
+  auto sink = [&](int k, int q, int t) {
+    if (k < cap) { o[2 * k] = q; o[2 * k + 1] = t; same += (qc[q] == tc[t]) ? 1 : 0; }
   };
-  auto at = [&](int i, int c) -> uint32_t { return strip[(size_t)(i - 2) * kPitch + c]; };
+  auto emit1 = [&](int q, int t) { if (lane == 0) sink(n, q, t); ++n; };
   emit1(Q - 1, T - 1);
   emit1(q_end, t_end);
-  int i = q_end, j = t_end;
-  bool origin = false;                                       // the walk stopped at a cell with both indices > 0: (0,0) is prepended
-  while (i >= 2 && j >= 2) {                                 // a cell of row 1 or column 1 points at (0,0), whose score is 0
-    // lane l looks at cell (i - l, j - l): its byte holds the move into it and the score bit of its diagonal predecessor
-    const int ci = i - lane, cj = j - lane;
-    const bool valid = ci >= 2 && cj >= 2;
-    const uint32_t b = valid ? at(ci, cj - 1) : 0u;
-    const bool go = valid && (b & 3u) == 0u && (b & 16u) != 0u;
-    const unsigned long long m = __ballot(go);
-    const int L = (~m == 0ull) ? 64 : __builtin_ctzll(~m);   // lanes 0 .. L-1 step diagonally onto a cell that is kept
-    if (lane < L) {
-      const int k = n + lane;
-      if (k < cap) { o[2 * k] = ci - 1; o[2 * k + 1] = cj - 1; same += (qc[ci - 1] == tc[cj - 1]) ? 1 : 0; }
-    }
-    n += L; i -= L; j -= L;
-    if (L == 64) continue;
-    if (i < 2 || j < 2) break;
-    const uint32_t bL = (uint32_t)__shfl((int)b, L);
-    const uint32_t mv = bL & 3u;
-    if (mv == 0u) { origin = true; break; }                  // a match whose predecessor's score is <= 0
-    int pi, pj; uint32_t bp = 0;
-    if (mv == 1u) {                                          // deletion: the smallest column of row i-1 holding the maximal key
-      pi = i - 1; pj = 0;
-      for (int k0 = j - 2; k0 >= 1; k0 -= 64) {
-        const int kk = k0 - lane;
-        const uint32_t bb = kk >= 1 ? at(i, kk) : 0u;
-        const unsigned long long clr = __ballot((bb & 4u) == 0u);
-        if (clr) { const int l0 = __builtin_ctzll(clr); pj = k0 - l0; bp = (uint32_t)__shfl((int)bb, l0); break; }
-      }
-    } else {                                                 // insertion: the smallest row of column j-1 holding the maximal key
-      pj = j - 1; pi = 0;
-      for (int k0 = i - 2; k0 >= 1; k0 -= 64) {
-        const int kk = k0 - lane;
-        const uint32_t bb = kk >= 1 ? at(kk + 1, pj) : 0u;
-        const unsigned long long clr = __ballot((bb & 8u) == 0u);
-        if (clr) { const int l0 = __builtin_ctzll(clr); pi = k0 - l0; bp = (uint32_t)__shfl((int)bb, l0); break; }
-      }
-    }
-    if (pi < 1 || pj < 1) break;                             // (cannot happen: row 1 and column 1 always clear their bits)
-    if ((bp & 16u) == 0u) { origin = true; break; }          // the source's score is <= 0
-    emit1(pi, pj);
-    i = pi; j = pj;
-  }
-  if (origin) emit1(0, 0);
+  if (strip_walk<kPitch, true>(strip, q_end, t_end, n, sink)) emit1(0, 0);
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) same += __shfl_xor(same, off);
   if (lane == 0) {
@@ -164,15 +120,8 @@ __global__ __launch_bounds__(64) void align_global_hit_kernel(ScoreArgs a, Align
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) score = max(score, __shfl_xor(score, off));
 
-  // ---- the final cell's pointer (dpmatrix.h:505-534): match, deletions from (Q-2, k) k ascending, insertions from (k, T-2) k
-  // ascending; a later candidate wins only when strictly greater ---------------------------------------------------------------
-  const int match = ob.match, dlv = ob.dlv;
-  const int irow = __shfl(ob.irow, cols.ls);
-  const int ikey = __shfl(ob.ikey, cols.ls);
-  const int ilv = irow == 0 ? kNegS : (free_ins ? ikey : ikey - (gi + ge * (Q - 3)));
-  int i = Q - 2, j = T - 2;
-  if (dlv > match) j = ob.dlc;
-  if (ilv > max(match, dlv)) { i = irow; j = T - 2; }
+  int i, j;
+  ob.final_cell(free_ins, i, j);
   __threadfence();                                           // the walk's lanes read bytes other lanes stored
   __syncthreads();
 
@@ -180,51 +129,13 @@ __global__ __launch_bounds__(64) void align_global_hit_kernel(ScoreArgs a, Align
   int32_t* o = g.trav + (size_t)hit * g.trav_stride * 2;
   const int cap = g.trav_stride;
   int n = 0, same = 0;
-  auto emit1 = [&](int q, int t) {
-    if (lane == 0 && n < cap) { o[2 * n] = q; o[2 * n + 1] = t; same += (qc[q] == tc[t]) ? 1 : 0; }
-    ++n;
+  auto sink = [&](int k, int q, int t) {
+    if (k < cap) { o[2 * k] = q; o[2 * k + 1] = t; same += (qc[q] == tc[t]) ? 1 : 0; }
   };
-  auto at = [&](int ii, int c) -> uint32_t { return strip[(size_t)(ii - 2) * kPitch + c]; };
+  auto emit1 = [&](int q, int t) { if (lane == 0) sink(n, q, t); ++n; };
   emit1(Q - 1, T - 1);
   emit1(i, j);
-  while (i >= 2 && j >= 2) {
-    // lane l looks at cell (i - l, j - l): its byte holds the move into it
-    const int ci = i - lane, cj = j - lane;
-    const bool valid = ci >= 2 && cj >= 2;
-    const uint32_t b = valid ? at(ci, cj - 1) : 0u;
-    const bool go = valid && (b & 3u) == 0u;
-    const unsigned long long m = __ballot(go);
-    const int L = (~m == 0ull) ? 64 : __builtin_ctzll(~m);   // lanes 0 .. L-1 step diagonally
-    if (lane < L) {
-      const int k = n + lane;
-      if (k < cap) { o[2 * k] = ci - 1; o[2 * k + 1] = cj - 1; same += (qc[ci - 1] == tc[cj - 1]) ? 1 : 0; }
-    }
-    n += L; i -= L; j -= L;
-    if (L == 64) continue;
-    if (i < 2 || j < 2) break;
-    const uint32_t mv = (uint32_t)__shfl((int)b, L) & 3u;    // 1 or 2: lane L is valid and did not go
-    int pi, pj;
-    if (mv == 1u) {                                          // deletion: the smallest column of row i-1 holding the maximal key
-      pi = i - 1; pj = 0;
-      for (int k0 = j - 2; k0 >= 1; k0 -= 64) {
-        const int kk = k0 - lane;
-        const uint32_t bb = kk >= 1 ? at(i, kk) : 0u;
-        const unsigned long long clr = __ballot((bb & 4u) == 0u);
-        if (clr) { pj = k0 - __builtin_ctzll(clr); break; }
-      }
-    } else {                                                 // insertion: the smallest row of column j-1 holding the maximal key
-      pj = j - 1; pi = 0;
-      for (int k0 = i - 2; k0 >= 1; k0 -= 64) {
-        const int kk = k0 - lane;
-        const uint32_t bb = kk >= 1 ? at(kk + 1, pj) : 0u;
-        const unsigned long long clr = __ballot((bb & 8u) == 0u);
-        if (clr) { pi = k0 - __builtin_ctzll(clr); break; }
-      }
-    }
-    if (pi < 1 || pj < 1) break;                             // (cannot happen: row 1 and column 1 always clear their bits)
-    emit1(pi, pj);
-    i = pi; j = pj;
-  }
+  strip_walk<kPitch, false>(strip, i, j, n, sink);
   emit1(0, 0);
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) same += __shfl_xor(same, off);
@@ -243,29 +154,21 @@ __global__ __launch_bounds__(64) void align_global_hit_kernel(ScoreArgs a, Align
 constexpr unsigned kFusedClasses = 0x0FEu;                   // bit R set: class R runs in align_local_hit_kernel<R>
 constexpr unsigned kFusedGlobalClasses = 0x1FEu;             // bit R set: class R runs in align_global_hit_kernel<R>
 
-// The batch route over the listed slots: aln_batch_create + aln_batch_dp + aln_batch_optimal / _strings, grouped under the
-// plane budget exactly as end_cells_through_batches (search_topk.hip) groups them.  prof != nullptr: `queries` holds the query
+// The batch route over the listed slots: aln_batch_create + aln_batch_dp + aln_batch_optimal / _strings, in the groups
+// BatchGroup (score_common.h) cuts under the plane budget.  prof != nullptr: `queries` holds the query
 // letters (the consensus pool or the placeholder), `sub` is not read and every batch is built from the planes of its own pairs
 // (BatchSim), which its budget counts.
 static int align_through_batches(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
                                  const aln_qprofiles* prof, const aln_gap* gap, const std::vector<int32_t>& qi_all,
                                  const std::vector<int32_t>& ti_all, const std::vector<size_t>& slot_all, AlignOut& ao) {
-  const size_t budget = (size_t)12 << 30, max_pairs = 65536;
   std::vector<int32_t> n, st, pairs, len;
   std::vector<float> sc, ident;
   std::vector<char> tl, ql;
-  size_t g0 = 0;
-  while (g0 < qi_all.size()) {
-    size_t g1 = g0, bytes = 0;
-    int64_t mq = 0, mt = 0, msum = 0;
-    while (g1 < qi_all.size() && g1 - g0 < max_pairs) {
-      const int64_t Q = queries->offsets[qi_all[g1] + 1] - queries->offsets[qi_all[g1]];
-      const int64_t T = templates->offsets[ti_all[g1] + 1] - templates->offsets[ti_all[g1]];
-      const size_t need = batch_pair_bytes((size_t)Q, (size_t)T, prof != nullptr);
-      if (g1 > g0 && bytes + need > budget) break;
-      bytes += need; mq = std::max(mq, Q); mt = std::max(mt, T); msum = std::max(msum, Q + T); ++g1;
-    }
-    const int32_t np = (int32_t)(g1 - g0), stride = (int32_t)std::max<int64_t>(std::min(mq, mt) + 3, 4), ls = (int32_t)(msum + 2);
+  BatchGroup grp;
+  while (grp.next(queries, templates, qi_all.data(), ti_all.data(), qi_all.size(), prof != nullptr)) {
+    const size_t g0 = grp.g0;
+    const int32_t np = (int32_t)(grp.g1 - g0), stride = (int32_t)std::max<int64_t>(std::min(grp.max_q, grp.max_t) + 3, 4);
+    const int32_t ls = (int32_t)(grp.max_sum + 2);
     n.assign((size_t)np, 0); st.assign((size_t)np, 0); pairs.assign((size_t)np * stride * 2, 0);
     sc.assign((size_t)np, 0.f); ident.assign((size_t)np, 0.f); len.assign((size_t)np, 0);
     BatchSim bs;
@@ -284,7 +187,6 @@ static int align_through_batches(aln_ctx* ctx, const aln_seqs* queries, const al
     for (int32_t p = 0; p < np; ++p)
       ao.put(slot_all[g0 + p], st[p], sc[p], ident[p], st[p] == 0 ? n[p] : 0, pairs.data() + (size_t)p * stride * 2, false, len[p],
              tl.data() + (size_t)p * ls, ql.data() + (size_t)p * ls);
-    g0 = g1;
   }
   return ALN_OK;
 }
@@ -447,14 +349,7 @@ static int align_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
         STRY(hipGetLastError());
       }
       if (want_lines) {
-        for (int h = 0; h < n; ++h) {
-          const HitDesc& d = fast[c.h0 + h];
-          PairDesc pd = {};
-          pd.Q = (int32_t)(queries->offsets[d.q + 1] - queries->offsets[d.q]);
-          pd.T = (int32_t)(templates->offsets[d.t + 1] - templates->offsets[d.t]);
-          pd.q_seq = d.q; pd.t_seq = d.t; pd.q_off = queries->offsets[d.q]; pd.t_off = templates->offsets[d.t];
-          hpd[h] = pd;
-        }
+        for (int h = 0; h < n; ++h) hpd[h] = pair_desc(queries, templates, fast[c.h0 + h].q, fast[c.h0 + h].t);
         STRY(hipMemcpyAsync(dpd, hpd.data(), (size_t)n * sizeof(PairDesc), hipMemcpyHostToDevice, ctx->stream));
         StrParams prm = {c.trav_stride, 1, 0, line_stride};
         RTRY(launch_gapped_strings(ctx, n, dpd, dres, dtrav, dqch, dtch, dlines, dso, prm));
@@ -467,16 +362,9 @@ static int align_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
       STRY(hipStreamSynchronize(ctx->stream));                 // the host vectors above are read by the copies until here
       for (int h = 0; h < n; ++h) {
         const HitDesc& d = fast[c.h0 + h];
-        const PairResult& r = hres[h];
         const int64_t Q = queries->offsets[d.q + 1] - queries->offsets[d.q], T = templates->offsets[d.t + 1] - templates->offsets[d.t];
-        const float ident = r.status == 0 ? float(hsame[h] - 2) / float(std::min(Q, T) - 2) * 100.f : 0.f;   // alignment.h:864
-        int len = 0; const char* tl = nullptr; const char* ql = nullptr; int st = r.status;
-        if (want_lines && st == 0) {
-          if (hso[h].err == ALN_E_OVERFLOW) len = line_stride;             // put() turns it into the slot's status
-          else if (hso[h].err != ALN_OK) st = hso[h].err;
-          else { len = hso[h].length; tl = hlines.data() + (size_t)h * 2 * line_stride; ql = tl + line_stride; }
-        }
-        ao.put(fast_slot[c.h0 + h], st, r.best, ident, r.n_path, htrav.data() + (size_t)h * c.trav_stride * 2, true, len, tl, ql);
+        put_fused(ao, fast_slot[c.h0 + h], hres[h], hsame[h], Q, T, htrav.data() + (size_t)h * c.trav_stride * 2,
+                  want_lines ? &hso[h] : nullptr, want_lines ? hlines.data() + (size_t)h * 2 * line_stride : nullptr, line_stride);
       }
     }
 #undef STRY

@@ -9,9 +9,9 @@
 //                                 align_local_hit_kernel through the strip; the list, the identity count, and one bit per
 //                                 aligned pair into the hit's forbidden-cell plane (1/8 B per cell) for the rounds that follow.
 // The walk needs no change: a forbidden cell holds 0 when the next row's strip byte takes its score bit, so a walk that reaches
-// one — diagonally or as a gap source — stops before it, as Optimal's does (optimal.h:100).  The walk is restated here, not
-// shared with align_local_hit_kernel (a helper that takes the kernel's state by reference costs registers, and that
-// kernel's metadata must not move).
+// one — diagonally or as a gap source — stops before it, as Optimal's does (optimal.h:100).  It is strip_walk (search_align.h), the
+// one align_local_hit_kernel calls, with a sink that also sets the pair's bit.  (DESIGN 4.8's finding is about helpers that take
+// a kernel's row arrays by reference; the walk's state is scalars after the sweep, and sharing it cost no register: 4.8i.)
 //   class_list_kernel, gapped_strings_kernel   unchanged: the lines of every (hit, round) list in one launch.
 // Templates beyond the kept classes, scoring systems ScoreRun sends through full builds and pairs without an interior go
 // through resident batches inside the call, round by round, on ALN_SIM_MATRIX planes expanded and masked on the host.
@@ -82,60 +82,15 @@ __global__ __launch_bounds__(64) void align_local_multi_kernel(ScoreArgs a, Mult
     auto forbid = [&](int q, int t) {                          // an alignment has one cell per row: no two lanes share a word
       if (more) atomicOr(mask + (size_t)q * (8 * R) + (t >> 5), 1u << (t & 31));
     };
-    auto emit1 = [&](int q, int t) {
-      if (lane == 0 && n < cap) { o[2 * n] = q; o[2 * n + 1] = t; same += (qc[q] == tc[t]) ? 1 : 0; }
-      ++n;
+    auto sink = [&](int k, int q, int t) {
+      if (k < cap) { o[2 * k] = q; o[2 * k + 1] = t; same += (qc[q] == tc[t]) ? 1 : 0; }
     };
-    auto at = [&](int i, int c) -> uint32_t { return strip[(size_t)(i - 2) * kPitch + c]; };
+    auto emit1 = [&](int q, int t) { if (lane == 0) sink(n, q, t); ++n; };
     emit1(Q - 1, T - 1);
     emit1(q_end, t_end);
     if (lane == 0) forbid(q_end, t_end);
-    int i = q_end, j = t_end;
-    bool origin = false;                                       // the walk stopped at a cell with both indices > 0: (0,0) is prepended
-    while (i >= 2 && j >= 2) {                                 // a cell of row 1 or column 1 points at (0,0), whose score is 0
-      // lane l looks at cell (i - l, j - l): its byte holds the move into it and the score bit of its diagonal predecessor
-      const int ci = i - lane, cj = j - lane;
-      const bool valid = ci >= 2 && cj >= 2;
-      const uint32_t b = valid ? at(ci, cj - 1) : 0u;
-      const bool go = valid && (b & 3u) == 0u && (b & 16u) != 0u;
-      const unsigned long long mm = __ballot(go);
-      const int L = (~mm == 0ull) ? 64 : __builtin_ctzll(~mm); // lanes 0 .. L-1 step diagonally onto a cell that is kept
-      if (lane < L) {
-        const int k = n + lane;
-        if (k < cap) { o[2 * k] = ci - 1; o[2 * k + 1] = cj - 1; same += (qc[ci - 1] == tc[cj - 1]) ? 1 : 0; }
-        forbid(ci - 1, cj - 1);                                // a list the caller's stride truncates still forbids all its cells
-      }
-      n += L; i -= L; j -= L;
-      if (L == 64) continue;
-      if (i < 2 || j < 2) break;
-      const uint32_t bL = (uint32_t)__shfl((int)b, L);
-      const uint32_t mv = bL & 3u;
-      if (mv == 0u) { origin = true; break; }                  // a match whose predecessor's score is <= 0 (a forbidden cell among them)
-      int pi, pj; uint32_t bp = 0;
-      if (mv == 1u) {                                          // deletion: the smallest column of row i-1 holding the maximal key
-        pi = i - 1; pj = 0;
-        for (int k0 = j - 2; k0 >= 1; k0 -= 64) {
-          const int kk = k0 - lane;
-          const uint32_t bb = kk >= 1 ? at(i, kk) : 0u;
-          const unsigned long long clr = __ballot((bb & 4u) == 0u);
-          if (clr) { const int l0 = __builtin_ctzll(clr); pj = k0 - l0; bp = (uint32_t)__shfl((int)bb, l0); break; }
-        }
-      } else {                                                 // insertion: the smallest row of column j-1 holding the maximal key
-        pj = j - 1; pi = 0;
-        for (int k0 = i - 2; k0 >= 1; k0 -= 64) {
-          const int kk = k0 - lane;
-          const uint32_t bb = kk >= 1 ? at(kk + 1, pj) : 0u;
-          const unsigned long long clr = __ballot((bb & 8u) == 0u);
-          if (clr) { const int l0 = __builtin_ctzll(clr); pi = k0 - l0; bp = (uint32_t)__shfl((int)bb, l0); break; }
-        }
-      }
-      if (pi < 1 || pj < 1) break;                             // (cannot happen: row 1 and column 1 always clear their bits)
-      if ((bp & 16u) == 0u) { origin = true; break; }          // the source's score is <= 0
-      emit1(pi, pj);
-      if (lane == 0) forbid(pi, pj);
-      i = pi; j = pj;
-    }
-    if (origin) emit1(0, 0);
+    // a list the caller's stride truncates still forbids all its cells
+    if (strip_walk<kPitch, true>(strip, q_end, t_end, n, [&](int k, int q, int t) { sink(k, q, t); forbid(q, t); })) emit1(0, 0);
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) same += __shfl_xor(same, off);
     if (lane == 0) {
@@ -160,13 +115,12 @@ constexpr unsigned kMultiClasses = 0x0FEu;                   // bit R set: class
 static bool reported(int a, float score, float min_score) { return score >= min_score && (a == 0 || score > 0.f); }
 
 // The batch route, round by round over the slots still alive: aln_batch_create + aln_batch_dp + aln_batch_optimal / _strings,
-// grouped under the plane budget as align_through_batches (search_align.hip) groups them.  Round 0 is built from the table
+// in the groups BatchGroup (score_common.h) cuts under the plane budget.  Round 0 is built from the table
 // itself, exactly as aln_hits_align builds it; later rounds from the pairs' Q x T planes, expanded on the host with every
 // forbidden cell at -(round 0's score + 1).
 static int multi_through_batches(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
                                  const aln_gap* gap, const std::vector<int32_t>& qi_all, const std::vector<int32_t>& ti_all,
                                  const std::vector<size_t>& slot_all, int N, float min_score, int32_t* n_found, AlignOut& ao) {
-  const size_t budget = (size_t)12 << 30, max_pairs = 65536;
   int idx[256];
   for (int i = 0; i < 256; ++i) idx[i] = -1;
   for (int i = 0; i < sub->n; ++i) idx[(unsigned char)sub->alphabet[i]] = i;
@@ -175,29 +129,22 @@ static int multi_through_batches(aln_ctx* ctx, const aln_seqs* queries, const al
   std::vector<float> neg(np_all, 0.f);
   std::vector<size_t> alive(np_all);
   for (size_t p = 0; p < np_all; ++p) alive[p] = p;
-  std::vector<int32_t> n, st, pairs, len, gq, gt;
+  std::vector<int32_t> n, st, pairs, len, aq, at;
   std::vector<float> sc, ident, planes;
   std::vector<int64_t> plane_off;
   std::vector<char> tl, ql;
   for (int a = 0; a < N && !alive.empty(); ++a) {
     std::vector<size_t> next;
-    size_t g0 = 0;
-    while (g0 < alive.size()) {
-      size_t g1 = g0, bytes = 0;
-      int64_t mq = 0, mt = 0, msum = 0;
-      while (g1 < alive.size() && g1 - g0 < max_pairs) {
-        const size_t p = alive[g1];
-        const int64_t Q = queries->offsets[qi_all[p] + 1] - queries->offsets[qi_all[p]];
-        const int64_t T = templates->offsets[ti_all[p] + 1] - templates->offsets[ti_all[p]];
-        const size_t need = batch_pair_bytes((size_t)Q, (size_t)T, a > 0);
-        if (g1 > g0 && bytes + need > budget) break;
-        bytes += need; mq = std::max(mq, Q); mt = std::max(mt, T); msum = std::max(msum, Q + T); ++g1;
-      }
-      const int32_t np = (int32_t)(g1 - g0), stride = (int32_t)std::max<int64_t>(std::min(mq, mt) + 3, 4), ls = (int32_t)(msum + 2);
+    aq.resize(alive.size()); at.resize(alive.size());          // the round's pair list: the slots still alive
+    for (size_t k = 0; k < alive.size(); ++k) { aq[k] = qi_all[alive[k]]; at[k] = ti_all[alive[k]]; }
+    BatchGroup grp;
+    while (grp.next(queries, templates, aq.data(), at.data(), alive.size(), a > 0)) {
+      const size_t g0 = grp.g0;
+      const int32_t np = (int32_t)(grp.g1 - g0), stride = (int32_t)std::max<int64_t>(std::min(grp.max_q, grp.max_t) + 3, 4);
+      const int32_t ls = (int32_t)(grp.max_sum + 2);
+      const int32_t *gq = aq.data() + g0, *gt = at.data() + g0;
       n.assign((size_t)np, 0); st.assign((size_t)np, 0); pairs.assign((size_t)np * stride * 2, 0);
       sc.assign((size_t)np, 0.f); ident.assign((size_t)np, 0.f); len.assign((size_t)np, 0);
-      gq.resize((size_t)np); gt.resize((size_t)np);
-      for (int32_t k = 0; k < np; ++k) { gq[k] = qi_all[alive[g0 + k]]; gt[k] = ti_all[alive[g0 + k]]; }
       aln_sim sim = aln_sim();
       if (a == 0) { sim.kind = ALN_SIM_SUBMATRIX; sim.sub = *sub; }
       else {
@@ -221,7 +168,7 @@ static int multi_through_batches(aln_ctx* ctx, const aln_seqs* queries, const al
         sim.kind = ALN_SIM_MATRIX; sim.planes = planes.data(); sim.plane_off = plane_off.data();
       }
       aln_batch* bb = nullptr;
-      int rc = aln_batch_create(ctx, queries, templates, np, gq.data(), gt.data(), 0, &bb);
+      int rc = aln_batch_create(ctx, queries, templates, np, gq, gt, 0, &bb);
       if (rc == ALN_OK) rc = aln_batch_dp(bb, &sim, gap, ALN_FWD, ALN_DP_AUTO, 0);
       if (rc == ALN_OK) rc = aln_batch_optimal(bb, sc.data(), n.data(), pairs.data(), stride, st.data());
       if (rc == ALN_OK) {
@@ -248,7 +195,6 @@ static int multi_through_batches(aln_ctx* ctx, const aln_seqs* queries, const al
           }
         next.push_back(p);
       }
-      g0 = g1;
     }
     alive.swap(next);
   }
@@ -398,13 +344,8 @@ static int multi_block(ScoreRun& run, int32_t K, const aln_hit* hits, const int3
         STRY(hipGetLastError());
       }
       if (want_lines) {
-        for (int h = 0; h < n; ++h) {
-          const MultiDesc& d = fast[c.h0 + h];
-          PairDesc pd = {};
-          pd.Q = (int32_t)q_len(d.q); pd.T = (int32_t)t_len(d.t);
-          pd.q_seq = d.q; pd.t_seq = d.t; pd.q_off = queries->offsets[d.q]; pd.t_off = templates->offsets[d.t];
-          for (int a = 0; a < N; ++a) hpd[(size_t)h * N + a] = pd;
-        }
+        for (int h = 0; h < n; ++h)
+          std::fill_n(hpd.begin() + (size_t)h * N, N, pair_desc(queries, templates, fast[c.h0 + h].q, fast[c.h0 + h].t));
         STRY(hipMemcpyAsync(dpd, hpd.data(), ne * sizeof(PairDesc), hipMemcpyHostToDevice, ctx->stream));
         StrParams prm = {c.trav_stride, 1, 0, line_stride};
         RTRY(launch_gapped_strings(ctx, (int)ne, dpd, dres, dtrav, dqch, dtch, dlines, dso, prm));
@@ -423,15 +364,8 @@ static int multi_block(ScoreRun& run, int32_t K, const aln_hit* hits, const int3
         n_found[slot] = hfound[h];
         for (int a = 0; a < hfound[h]; ++a) {
           const size_t e = (size_t)h * N + a;
-          const PairResult& r = hres[e];
-          const float ident = r.status == 0 ? float(hsame[e] - 2) / float(std::min(Q, T) - 2) * 100.f : 0.f;   // alignment.h:864
-          int len = 0; const char* tl = nullptr; const char* ql = nullptr; int st = r.status;
-          if (want_lines && st == 0) {
-            if (hso[e].err == ALN_E_OVERFLOW) len = line_stride;             // put() turns it into the alignment's status
-            else if (hso[e].err != ALN_OK) st = hso[e].err;
-            else { len = hso[e].length; tl = hlines.data() + e * 2 * line_stride; ql = tl + line_stride; }
-          }
-          ao.put(slot * (size_t)N + a, st, r.best, ident, r.n_path, htrav.data() + e * c.trav_stride * 2, true, len, tl, ql);
+          put_fused(ao, slot * (size_t)N + a, hres[e], hsame[e], Q, T, htrav.data() + e * c.trav_stride * 2,
+                    want_lines ? &hso[e] : nullptr, want_lines ? hlines.data() + e * 2 * line_stride : nullptr, line_stride);
         }
       }
     }

@@ -65,56 +65,13 @@ __global__ __launch_bounds__(64) void align_local_hit_prof_kernel(ScoreArgs a, A
   int32_t* o = g.trav + (size_t)hit * g.trav_stride * 2;
   const int cap = g.trav_stride;
   int n = 0, same = 0;
-  auto emit1 = [&](int q, int t) {
-    if (lane == 0 && n < cap) { o[2 * n] = q; o[2 * n + 1] = t; same += (qs[q] == ts[t]) ? 1 : 0; }
-    ++n;
+  auto sink = [&](int k, int q, int t) {
+    if (k < cap) { o[2 * k] = q; o[2 * k + 1] = t; same += (qs[q] == ts[t]) ? 1 : 0; }
   };
-  auto at = [&](int i, int c) -> uint32_t { return strip[(size_t)(i - 2) * kPitch + c]; };
+  auto emit1 = [&](int q, int t) { if (lane == 0) sink(n, q, t); ++n; };
   emit1(Q - 1, T - 1);
   emit1(q_end, t_end);
-  int i = q_end, j = t_end;
-  bool origin = false;
-  while (i >= 2 && j >= 2) {
-    const int ci = i - lane, cj = j - lane;
-    const bool valid = ci >= 2 && cj >= 2;
-    const uint32_t b = valid ? at(ci, cj - 1) : 0u;
-    const bool go = valid && (b & 3u) == 0u && (b & 16u) != 0u;
-    const unsigned long long m = __ballot(go);
-    const int L = (~m == 0ull) ? 64 : __builtin_ctzll(~m);
-    if (lane < L) {
-      const int k = n + lane;
-      if (k < cap) { o[2 * k] = ci - 1; o[2 * k + 1] = cj - 1; same += (qs[ci - 1] == ts[cj - 1]) ? 1 : 0; }
-    }
-    n += L; i -= L; j -= L;
-    if (L == 64) continue;
-    if (i < 2 || j < 2) break;
-    const uint32_t bL = (uint32_t)__shfl((int)b, L);
-    const uint32_t mv = bL & 3u;
-    if (mv == 0u) { origin = true; break; }
-    int pi, pj; uint32_t bp = 0;
-    if (mv == 1u) {
-      pi = i - 1; pj = 0;
-      for (int k0 = j - 2; k0 >= 1; k0 -= 64) {
-        const int kk = k0 - lane;
-        const uint32_t bb = kk >= 1 ? at(i, kk) : 0u;
-        const unsigned long long clr = __ballot((bb & 4u) == 0u);
-        if (clr) { const int l0 = __builtin_ctzll(clr); pj = k0 - l0; bp = (uint32_t)__shfl((int)bb, l0); break; }
-      }
-    } else {
-      pj = j - 1; pi = 0;
-      for (int k0 = i - 2; k0 >= 1; k0 -= 64) {
-        const int kk = k0 - lane;
-        const uint32_t bb = kk >= 1 ? at(kk + 1, pj) : 0u;
-        const unsigned long long clr = __ballot((bb & 8u) == 0u);
-        if (clr) { const int l0 = __builtin_ctzll(clr); pi = k0 - l0; bp = (uint32_t)__shfl((int)bb, l0); break; }
-      }
-    }
-    if (pi < 1 || pj < 1) break;
-    if ((bp & 16u) == 0u) { origin = true; break; }
-    emit1(pi, pj);
-    i = pi; j = pj;
-  }
-  if (origin) emit1(0, 0);
+  if (strip_walk<kPitch, true>(strip, q_end, t_end, n, sink)) emit1(0, 0);
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) same += __shfl_xor(same, off);
   if (lane == 0) {
@@ -150,14 +107,8 @@ __global__ __launch_bounds__(64) void align_global_hit_prof_kernel(ScoreArgs a, 
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) score = max(score, __shfl_xor(score, off));
 
-  // ---- the final cell's pointer (dpmatrix.h:505-534), as in align_global_hit_kernel -------------------------------------------
-  const int match = ob.match, dlv = ob.dlv;
-  const int irow = __shfl(ob.irow, cols.ls);
-  const int ikey = __shfl(ob.ikey, cols.ls);
-  const int ilv = irow == 0 ? kNegS : (free_ins ? ikey : ikey - (gi + ge * (Q - 3)));
-  int i = Q - 2, j = T - 2;
-  if (dlv > match) j = ob.dlc;
-  if (ilv > max(match, dlv)) { i = irow; j = T - 2; }
+  int i, j;
+  ob.final_cell(free_ins, i, j);
   __threadfence();                                           // the last copy has landed; the walk's lanes read bytes other lanes stored
   __syncthreads();
 
@@ -165,50 +116,13 @@ __global__ __launch_bounds__(64) void align_global_hit_prof_kernel(ScoreArgs a, 
   int32_t* o = g.trav + (size_t)hit * g.trav_stride * 2;
   const int cap = g.trav_stride;
   int n = 0, same = 0;
-  auto emit1 = [&](int q, int t) {
-    if (lane == 0 && n < cap) { o[2 * n] = q; o[2 * n + 1] = t; same += (qs[q] == ts[t]) ? 1 : 0; }
-    ++n;
+  auto sink = [&](int k, int q, int t) {
+    if (k < cap) { o[2 * k] = q; o[2 * k + 1] = t; same += (qs[q] == ts[t]) ? 1 : 0; }
   };
-  auto at = [&](int ii, int c) -> uint32_t { return strip[(size_t)(ii - 2) * kPitch + c]; };
+  auto emit1 = [&](int q, int t) { if (lane == 0) sink(n, q, t); ++n; };
   emit1(Q - 1, T - 1);
   emit1(i, j);
-  while (i >= 2 && j >= 2) {
-    const int ci = i - lane, cj = j - lane;
-    const bool valid = ci >= 2 && cj >= 2;
-    const uint32_t b = valid ? at(ci, cj - 1) : 0u;
-    const bool go = valid && (b & 3u) == 0u;
-    const unsigned long long m = __ballot(go);
-    const int L = (~m == 0ull) ? 64 : __builtin_ctzll(~m);
-    if (lane < L) {
-      const int k = n + lane;
-      if (k < cap) { o[2 * k] = ci - 1; o[2 * k + 1] = cj - 1; same += (qs[ci - 1] == ts[cj - 1]) ? 1 : 0; }
-    }
-    n += L; i -= L; j -= L;
-    if (L == 64) continue;
-    if (i < 2 || j < 2) break;
-    const uint32_t mv = (uint32_t)__shfl((int)b, L) & 3u;    // 1 or 2: lane L is valid and did not go
-    int pi, pj;
-    if (mv == 1u) {
-      pi = i - 1; pj = 0;
-      for (int k0 = j - 2; k0 >= 1; k0 -= 64) {
-        const int kk = k0 - lane;
-        const uint32_t bb = kk >= 1 ? at(i, kk) : 0u;
-        const unsigned long long clr = __ballot((bb & 4u) == 0u);
-        if (clr) { pj = k0 - __builtin_ctzll(clr); break; }
-      }
-    } else {
-      pj = j - 1; pi = 0;
-      for (int k0 = i - 2; k0 >= 1; k0 -= 64) {
-        const int kk = k0 - lane;
-        const uint32_t bb = kk >= 1 ? at(kk + 1, pj) : 0u;
-        const unsigned long long clr = __ballot((bb & 8u) == 0u);
-        if (clr) { pi = k0 - __builtin_ctzll(clr); break; }
-      }
-    }
-    if (pi < 1 || pj < 1) break;                             // (cannot happen: row 1 and column 1 always clear their bits)
-    emit1(pi, pj);
-    i = pi; j = pj;
-  }
+  strip_walk<kPitch, false>(strip, i, j, n, sink);
   emit1(0, 0);
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) same += __shfl_xor(same, off);

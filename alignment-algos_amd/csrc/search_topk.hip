@@ -185,24 +185,15 @@ __global__ __launch_bounds__(64) void score_local_end_kernel(ScoreArgs a, const 
 
 // End cells of local hits whose pair went the full-build route: resident batches over just those hits, Optimal's pair list —
 // enumerate_local (optimal.h:79-105) appends (Q-1, T-1) and prepends find_max's cell, so the entry before the last is that cell.
-// Groups stay below the plane budget of score_through_batches; prof != nullptr: as there, planes expanded on the host.
+// Groups are BatchGroup's (score_common.h); prof != nullptr: as there, planes expanded on the host.
 static int end_cells_through_batches(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
                                      const aln_gap* gap, const std::vector<int32_t>& qi_all, const std::vector<int32_t>& ti_all,
                                      const std::vector<aln_hit*>& where, const aln_qprofiles* prof) {
-  const size_t budget = (size_t)12 << 30, max_pairs = 65536;
   std::vector<int32_t> n, st, pairs;
-  size_t g0 = 0;
-  while (g0 < qi_all.size()) {
-    size_t g1 = g0, bytes = 0;
-    int64_t mq = 0, mt = 0;
-    while (g1 < qi_all.size() && g1 - g0 < max_pairs) {
-      const int64_t Q = queries->offsets[qi_all[g1] + 1] - queries->offsets[qi_all[g1]];
-      const int64_t T = templates->offsets[ti_all[g1] + 1] - templates->offsets[ti_all[g1]];
-      const size_t need = batch_pair_bytes((size_t)Q, (size_t)T, prof != nullptr);
-      if (g1 > g0 && bytes + need > budget) break;
-      bytes += need; mq = std::max(mq, Q); mt = std::max(mt, T); ++g1;
-    }
-    const int32_t np = (int32_t)(g1 - g0), stride = (int32_t)std::max<int64_t>(std::min(mq, mt) + 3, 4);
+  BatchGroup grp;
+  while (grp.next(queries, templates, qi_all.data(), ti_all.data(), qi_all.size(), prof != nullptr)) {
+    const size_t g0 = grp.g0;
+    const int32_t np = (int32_t)(grp.g1 - g0), stride = (int32_t)std::max<int64_t>(std::min(grp.max_q, grp.max_t) + 3, 4);
     n.assign((size_t)np, 0); st.assign((size_t)np, 0); pairs.assign((size_t)np * stride * 2, 0);
     aln_batch* bb = nullptr;
     BatchSim bs;
@@ -218,7 +209,6 @@ static int end_cells_through_batches(aln_ctx* ctx, const aln_seqs* queries, cons
       const int32_t* e = pairs.data() + ((size_t)p * stride + (size_t)(n[p] - 2)) * 2;
       where[g0 + p]->q_end = e[0]; where[g0 + p]->t_end = e[1];
     }
-    g0 = g1;
   }
   return ALN_OK;
 }
