@@ -1,7 +1,8 @@
 // score_common.h — what the all-vs-all score kernels (score_only.hip) and the entries built on them (search_topk.hip,
-// search_zscore.hip, search_align.hip) share beside the row sweep itself (score_sweep.h): the kernels' argument block, how
-// work is listed and launched by template length class, and ScoreRun, the host side of one all-vs-all scoring call cut into
-// steps so that a caller can leave the scores of a slab of query rows in a device buffer of its own.
+// search_zscore.hip, search_align.hip) share beside the row sweep itself (score_sweep.h): the kernels' argument block, the
+// query side a kernel is instantiated for (residues scored through the table, or position-specific rows), how work is listed
+// and launched by template length class, and ScoreRun, the host side of one all-vs-all scoring call cut into steps so that a
+// caller can leave the scores of a slab of query rows in a device buffer of its own.
 #pragma once
 #include <algorithm>
 #include <deque>
@@ -23,6 +24,46 @@ struct ScoreArgs {
   float* scores;                                // rows x n_t
   int q_begin, n_t;
   int gi, ge;
+};
+
+// ---- the query side ------------------------------------------------------------------------------------------------------------
+// A position-specific query (aln_qprofiles) says, for every query position, what each template letter scores there: S[i][j] =
+// rows[i][letter of t[j]].  The sweeps read a row's similarities as 32 ints in LDS indexed by the template's code; for a residue
+// query that vector is the table row of the query's letter, for a profile it is row i of the profile itself.  So every kernel
+// around a sweep is ONE template over the query side, which says where the rows come from and nothing else:
+//   Rows          the sweep's row source (score_sweep.h)
+//   stage()       what the kernel's 4 KiB of LDS (__shared__ __attribute__((aligned(16))) int lds[32 * 32]) holds before the sweep
+//   rows()        the global pointer handed to the sweep for query qi
+//   kStaged       the side copies rows into LDS asynchronously while the sweep runs: a kernel must drain the last copy before
+//                 its wave ends, and such a query has no letters of its own (the identity is counted over characters)
+//   letters()     of a pool's codes and its characters, the one an alignment's identity is counted over (search_align.hip)
+//   kFusedLocal / kFusedGlobal   bit R set: class R runs in align_local_hit_kernel<R> / align_global_hit_kernel<R> (search_align.hip)
+// The row arrays never leave the kernel and the sweeps' text does not change with the side.
+struct ResidueQuery {
+  typedef TableRows Rows;
+  static constexpr bool kStaged = false;
+  // R = 8 of the local kernel is not kept for this side, so that class goes the batch route.  It was dropped for 24 VGPRs
+  // spilled into AGPRs; as the kernel stands today it would compile to 237 VGPRs and none (4.8j has the
+  // figures).  The mask is a route, and changing a route is a change of behaviour of its own.
+  static constexpr unsigned kFusedLocal = 0x0FEu, kFusedGlobal = 0x1FEu;
+  static __device__ __forceinline__ void stage(int* lds, const ScoreArgs& a) {          // the 32 x 32 table
+    for (int k = threadIdx.x; k < 32 * 32; k += 64) lds[k] = a.table32[k];
+    __syncthreads();
+  }
+  static __device__ __forceinline__ const uint8_t* rows(const ScoreArgs& a, int qi) { return a.qcodes + a.qoff[qi]; }
+  static __device__ __forceinline__ const uint8_t* letters(const uint8_t* codes, const char*) { return codes; }
+};
+// ScoreArgs of a profile run: qcodes is the device rows as bytes, biased so that pool row r starts at qcodes + 128 r; qoff counts
+// ROWS; table32 and qsel are unused.  The LDS is ProfileRows' ring of 32 rows, 8 rows (1 KiB) per copy, one copy ahead of the sweep.
+struct ProfileQuery {
+  typedef ProfileRows Rows;
+  static constexpr bool kStaged = true;
+  static constexpr unsigned kFusedLocal = 0x1FEu, kFusedGlobal = 0x1FEu;                // no scratch, no VGPR spill
+  static __device__ __forceinline__ void stage(int*, const ScoreArgs&) {}
+  static __device__ __forceinline__ const int4* rows(const ScoreArgs& a, int qi) {
+    return reinterpret_cast<const int4*>(a.qcodes + a.qoff[qi] * 128);
+  }
+  static __device__ __forceinline__ const char* letters(const uint8_t*, const char* chars) { return chars; }
 };
 
 // A template of T <= 2048 columns is of length class R = ceil(T / 256): the groups of 256 columns a wave sweeps.
@@ -73,11 +114,6 @@ struct FirstMaxObserver : NoObserver {
     }
   }
 };
-
-// score_profile.hip: the profile twins of score_local_kernel / score_global_kernel for the templates of class r (grid: templates
-// of the class x query rows), and of score_local_end_kernel for the n hit slots of `list`
-void launch_score_prof(int r, bool local, dim3 grid, hipStream_t stream, const ScoreArgs& s, int free_del, int free_ins);
-void launch_score_local_end_prof(int r, int n, hipStream_t stream, const ScoreArgs& s, const int32_t* list, aln_hit* hits, int K);
 
 // One all-vs-all scoring call (the arguments of aln_score_all_vs_all): prepare() checks them and decides the route, upload()
 // puts what the register-resident kernels read on the device, launch() enqueues those kernels for a block of query rows

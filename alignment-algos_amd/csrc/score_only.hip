@@ -11,6 +11,10 @@
 // bound by VALU issue (about 6 half-rate + 8 full-rate instructions per cell), not by HBM.
 // Grid: x = template index, y = query index inside the caller's row block; templates are replicated on every GPU,
 // query rows are what ranks shard.
+// Queries given as POSITION-SPECIFIC rows (aln_qprofiles) run the same two kernels, instantiated for the profile side
+// (ProfileQuery, score_common.h): same recurrence, same results as a full build over the Q x T plane of the profile
+// (aln_batch_dp with ALN_SIM_MATRIX) + Optimal; only where a row's 32 similarities in LDS come from differs (ProfileRows,
+// score_sweep.h).  There is no packed kernel for them.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -21,20 +25,20 @@
 
 namespace aln {
 
-template <int R>
+// One kernel per job for both query sides (ResidueQuery, ProfileQuery: score_common.h); one wave per pair.
+template <int R, class Side>
 __global__ __launch_bounds__(64) void score_local_kernel(ScoreArgs a) {
-  __shared__ int tab[32 * 32];
+  __shared__ __attribute__((aligned(16))) int lds[32 * 32];
   const int lane = threadIdx.x;
-  for (int k = lane; k < 32 * 32; k += 64) tab[k] = a.table32[k];
-  __syncthreads();
+  Side::stage(lds, a);
   const int ti = a.tsel[blockIdx.x], qi = a.q_begin + blockIdx.y;
-  const uint8_t* __restrict__ qc = a.qcodes + a.qoff[qi];
+  const typename Side::Rows::Src* __restrict__ qr = Side::rows(a, qi);
   const uint8_t* __restrict__ tc = a.tcodes + a.toff[ti];
   const int Q = (int)(a.qoff[qi + 1] - a.qoff[qi]), T = (int)(a.toff[ti + 1] - a.toff[ti]);
   LocalCols<R> cols;
   cols.load(tc, T, a.gi, a.ge);
   int d[R][4];
-  int m = sweep_local<R>(tab, cols, qc, Q - 2, d, NoObserver());
+  int m = sweep_local<R, typename Side::Rows>(lds, cols, qr, Q - 2, d, NoObserver());
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) m = max(m, __shfl_xor(m, o));
   if (lane == 0) a.scores[(size_t)blockIdx.y * a.n_t + ti] = (float)m;
@@ -42,14 +46,13 @@ __global__ __launch_bounds__(64) void score_local_kernel(ScoreArgs a) {
 
 
 // ---- the four non-local align types: the score Optimal reports is the FINAL cell's (optimal.h:56-74) ---------------------------
-template <int R>
+template <int R, class Side>
 __global__ __launch_bounds__(64) void score_global_kernel(ScoreArgs a, int free_del, int free_ins) {
-  __shared__ int tab[32 * 32];
+  __shared__ __attribute__((aligned(16))) int lds[32 * 32];
   const int lane = threadIdx.x;
-  for (int k = lane; k < 32 * 32; k += 64) tab[k] = a.table32[k];
-  __syncthreads();
+  Side::stage(lds, a);
   const int ti = a.tsel[blockIdx.x], qi = a.q_begin + blockIdx.y;
-  const uint8_t* __restrict__ qc = a.qcodes + a.qoff[qi];
+  const typename Side::Rows::Src* __restrict__ qr = Side::rows(a, qi);
   const uint8_t* __restrict__ tc = a.tcodes + a.toff[ti];
   const int Q = (int)(a.qoff[qi + 1] - a.qoff[qi]), T = (int)(a.toff[ti + 1] - a.toff[ti]);
   const int gi = a.gi, ge = a.ge;
@@ -64,7 +67,7 @@ __global__ __launch_bounds__(64) void score_global_kernel(ScoreArgs a, int free_
   }
   GlobalCols<R> cols;
   cols.load(tc, T, gi, ge);
-  int best = sweep_global<R>(tab, cols, qc, Q, free_del, free_ins, NoObserver());
+  int best = sweep_global<R, typename Side::Rows>(lds, cols, qr, Q, free_del, free_ins, NoObserver());
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) best = max(best, __shfl_xor(best, o));
   if (lane == 0) *out = (float)best;
@@ -421,7 +424,7 @@ int ScoreRun::upload_offsets() {
 // aligned (hipMalloc's alignment, 128 bytes per row).  INVARIANT: the allocation ends kProfilePadRows rows (zeros) behind the last
 // row — a sweep requests the 8-row chunks its rows 1 .. Q-2 lie in plus the one after (ProfileRows, score_sweep.h), i.e. at most
 // rows .. Q + 13 of its profile, of which the last profile's reach past the pool's end.  A sweep that reads the rows through an
-// order (PermutedProfileRows, search_zscore_profile.hip) requests ENTRIES 0 .. Q + 13 of that order instead, every one of them a
+// order (PermutedProfileRows, search_zscore.hip) requests ENTRIES 0 .. Q + 13 of that order instead, every one of them a
 // row index below Q: the order is padded (order_stride, same file), and no copy of such a sweep leaves its profile.
 int ScoreRun::upload_profile_rows(int32_t qa, int32_t qb) {
   const int64_t r0 = prof->offsets[qa], r1 = prof->offsets[qb];
@@ -494,12 +497,16 @@ int ScoreRun::launch(int row0, int nrows, float* dscores) {
       s.tsel = dsel + cls_begin[r];
       s.qsel = dqsel ? dqsel + row0 + r0 : nullptr;
       const dim3 grid(nc, packed ? (nr + 1) / 2 : nr);   // packed: two query rows per wave
-      if (prof) launch_score_prof(r, local, grid, ctx->stream, s, free_del, free_ins);
-      else dispatch_r<8>(r, [&](auto rc) {
+      dispatch_r<8>(r, [&](auto rc) {
         constexpr int R = decltype(rc)::value;
         if (packed) hipLaunchKernelGGL(score_local_pk_kernel<R>, grid, block, 0, ctx->stream, s, nr);
-        else if (!local) hipLaunchKernelGGL(score_global_kernel<R>, grid, block, 0, ctx->stream, s, free_del, free_ins);
-        else hipLaunchKernelGGL(score_local_kernel<R>, grid, block, 0, ctx->stream, s);
+        else if (prof) {
+          if (local) hipLaunchKernelGGL((score_local_kernel<R, ProfileQuery>), grid, block, 0, ctx->stream, s);
+          else hipLaunchKernelGGL((score_global_kernel<R, ProfileQuery>), grid, block, 0, ctx->stream, s, free_del, free_ins);
+        } else {
+          if (local) hipLaunchKernelGGL((score_local_kernel<R, ResidueQuery>), grid, block, 0, ctx->stream, s);
+          else hipLaunchKernelGGL((score_global_kernel<R, ResidueQuery>), grid, block, 0, ctx->stream, s, free_del, free_ins);
+        }
       });
       STRY(hipGetLastError());
     }

@@ -7,10 +7,10 @@
 //   LocalCols<R>  + sweep_local   clipped at 0, end gaps free, columns outside the interior masked to 0        (dpmatrix.h:538-689)
 //   GlobalCols<R> + sweep_global  the four non-local align types: no clip, "minus infinity" outside the interior,
 //                                 end gaps priced per align type, the final cell included                      (dpmatrix.h:375-534)
-// Users: score_only.hip (scores), search_topk.hip (end cells), search_zscore.hip (one sweep per shuffle), search_align.hip
-// (four or five bits per cell into a strip), score_profile.hip (queries given as position-specific rows),
-// search_zscore_profile.hip (those rows in a permuted order, through a source of its own), search_align_multi.hip
-// (sweep_local_masked: the local sweep over a plane of forbidden cells).  What a user sees of
+// Users: score_only.hip (scores), search_topk.hip (end cells), search_zscore.hip (one sweep per shuffle; a profile's rows in a
+// permuted order, through a source of its own), search_align.hip (four or five bits per cell into a strip) — each kernel of
+// these once, instantiated for residue queries and for queries given as position-specific rows (the query side,
+// score_common.h) — and search_align_multi.hip (sweep_local_masked: the local sweep over a plane of forbidden cells).  What a user sees of
 // a sweep beyond its result goes through an observer, where a row's similarities come from through a row source; the packed
 // 16-bit kernel of score_only.hip has its own types and its own sweep.
 #pragma once
@@ -56,7 +56,7 @@ struct TableRows {
   static constexpr bool kInSweep = true;
 };
 
-// A position-specific query (score_profile.hip): the device holds row i of the profile as 32 int32 (128 bytes; letters n .. 31
+// A position-specific query (ProfileQuery, score_common.h): the device holds row i of the profile as 32 int32 (128 bytes; letters n .. 31
 // and the two sentinel rows are 0), rows contiguous, so 8 rows are the 1 KiB that ONE 16-byte-per-lane global -> LDS copy writes
 // lane-linearly.  LDS holds a ring of 32 rows (4 chunks of 8, the 4 KiB of the table it replaces): row i sits in slot i & 31.
 // Chunk c + 1 is requested when the sweep enters chunk c, then the source waits until at most that one copy is outstanding, i.e.

@@ -1,8 +1,8 @@
-// search_align.h — what the fused hit-alignment kernels of search_align.hip (residue queries, the table in LDS),
-// search_align_profile.hip (position-specific queries, rows staged into LDS) and search_align_multi.hip (several rounds per
+// search_align.h — what the fused hit-alignment kernels of search_align.hip (one pair of kernels for residue queries, the
+// table in LDS, and for position-specific queries, rows staged into LDS) and search_align_multi.hip (several rounds per
 // hit) share: how a hit is described to a kernel, where its results go and how a slot's record, list and lines are written for
 // the caller (AlignOut, put_fused, pair_desc), the two observers that turn a row sweep into the strip bytes and the final
-// cell's pointer, and strip_walk, the walk back through the strip that all five kernels call.  The strip byte is defined at
+// cell's pointer, and strip_walk, the walk back through the strip that all three kernels call.  The strip byte is defined at
 // the head of search_align.hip.  DESIGN 4.8 found that a helper which takes a kernel's ROW ARRAYS by reference costs
 // registers; the walk runs after the sweep on scalar state only (strip, i, j, n), and sharing it costs none.
 #pragma once
@@ -221,12 +221,5 @@ inline bool align_outputs_ok(int32_t K, const aln_hit* hits, const int32_t* n_hi
   if (want_lines ? (!tlines || !qlines || line_stride < 1) : lengths != nullptr) return false;
   return true;
 }
-
-// search_align_profile.hip: the profile twins of align_local_hit_kernel / align_global_hit_kernel for the n hits of g.list, all of
-// length class r (s: ScoreArgs of a profile run, score_profile.hip; qch / tch: the character pools of the query letters and the
-// templates on the device, which the identity is counted over), and the classes they are kept for (bit R: class R is fused)
-unsigned align_prof_classes(bool local);
-void launch_align_hit_prof(int r, bool local, int n, hipStream_t stream, const ScoreArgs& s, const AlignArgs& g, const char* qch,
-                           const char* tch, int free_del, int free_ins);
 
 }  // namespace aln

@@ -28,8 +28,8 @@
 //                               the row observer kept of column T-2; the walk always runs to a cell of row 1 or column 1, then (0,0).
 // Everything the kernels do not take — templates beyond 2048 columns, scoring systems ScoreRun sends through full builds, pairs
 // without an interior, a length class an instantiation was not kept for — goes through resident batches inside the call.
-// aln_hits_align_profiles is the same call for the hits of a profile search: the same host driver (align_block), the kernels of
-// search_align_profile.hip, and batches built from the profiles' planes for what those do not take.
+// aln_hits_align_profiles is the same call for the hits of a profile search: the same host driver (align_block), the same two
+// kernels instantiated for the profile side, and batches built from the profiles' planes for what those do not take.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -41,17 +41,33 @@ namespace aln {
 
 constexpr size_t kAlignBudget = (size_t)1 << 30;   // bytes of strips (and of lists, and of lines) resident at a time
 
-template <int R>
-__global__ __launch_bounds__(64) void align_local_hit_kernel(ScoreArgs a, AlignArgs g) {
-  __shared__ int tab[32 * 32];
+// Both kernels are templates over the query side (ResidueQuery, ProfileQuery: score_common.h).  qch / tch: the character pools
+// of the query letters (which share the queries' offsets) and of the templates on the device.  A profile has no letters, so its
+// identity is counted over CHARACTERS — the caller's consensus pool, or the placeholder pool of ScoreRun, against the templates',
+// exactly the comparison gapped_strings_kernel makes for the lines; the residue side counts over codes, never reads the pools
+// and is passed nullptr.
+//
+// The VM counter, staged side.  The row loop holds the strip stores (R per row) beside the staging copy, and gfx950 retires
+// loads, LDS copies and stores through ONE counter in issue order.  ProfileRows::landed() waits until at most one operation is
+// outstanding; it is called right after chunk c + 1 is requested, so chunk c has landed (it is older than everything waited
+// for) — and so has every strip store issued so far: once per 8 rows the stores are drained.  That is correct and is what ships:
+// a counted wait that leaves the stores in flight was built and measured, and did not separate from this one.
+// INVARIANT (ScoreRun::upload_profile_rows): a sweep requests at most rows 0 .. Q + 13 of its profile and the buffer is padded
+// for that; the local kernel stops at q_end <= Q - 2.  The last copy requested is never read: it is drained before the walk (and
+// before the kernel returns early) so that nothing is in flight into LDS when the wave ends.
+template <int R, class Side>
+__global__ __launch_bounds__(64) void align_local_hit_kernel(ScoreArgs a, AlignArgs g, const char* __restrict__ qch,
+                                                            const char* __restrict__ tch) {
+  __shared__ __attribute__((aligned(16))) int lds[32 * 32];
   const int lane = threadIdx.x;
-  for (int k = lane; k < 32 * 32; k += 64) tab[k] = a.table32[k];
-  __syncthreads();
+  Side::stage(lds, a);
   const int hit = g.list[blockIdx.x];
   const HitDesc hd = g.desc[hit];
   const int ti = hd.t, qi = hd.q, q_end = hd.q_end, t_end = hd.t_end;
-  const uint8_t* __restrict__ qc = a.qcodes + a.qoff[qi];
+  const typename Side::Rows::Src* __restrict__ qr = Side::rows(a, qi);
   const uint8_t* __restrict__ tc = a.tcodes + a.toff[ti];
+  const auto* __restrict__ qs = Side::letters(a.qcodes, qch) + a.qoff[qi];      // what the identity is counted over
+  const auto* __restrict__ ts = Side::letters(a.tcodes, tch) + a.toff[ti];
   const int Q = (int)(a.qoff[qi + 1] - a.qoff[qi]), T = (int)(a.toff[ti + 1] - a.toff[ti]);
   constexpr int kPitch = 256 * R;
   uint8_t* strip = g.strip + hd.strip_off;      // row i (2 .. q_end) at strip + (i - 2) * kPitch
@@ -63,7 +79,11 @@ __global__ __launch_bounds__(64) void align_local_hit_kernel(ScoreArgs a, AlignA
   __builtin_assume(q_end >= 1);                 // row 1 always runs, as the host guarantees: no path around it to keep registers for
   StripObserver<true> bytes;
   bytes.strip = strip; bytes.pitch = kPitch;
-  sweep_local<R>(tab, cols, qc, q_end, d, bytes);
+  sweep_local<R, typename Side::Rows>(lds, cols, qr, q_end, d, bytes);
+  if constexpr (Side::kStaged) {
+    __threadfence();                                         // the last copy has landed; the walk's lanes read bytes other lanes stored
+    __syncthreads();
+  }
   // D[q_end][t_end]: row q_end is in d[], column t_end in slot (rs, xs) of lane ls
   const int dend = __shfl(sweep_pick<R>(d, t_end / 256, t_end & 3, 0), (t_end & 255) >> 2);
   PairResult res = {};
@@ -72,15 +92,20 @@ __global__ __launch_bounds__(64) void align_local_hit_kernel(ScoreArgs a, AlignA
     if (lane == 0) { res.best = 0.f; res.status = ALN_E_ARG; res.n_path = 0; g.res[hit] = res; g.same[hit] = 0; }
     return;
   }
-  __threadfence();                                           // the walk's lanes read bytes other lanes stored
-  __syncthreads();
+  if constexpr (!Side::kStaged) {
+    __threadfence();                                         // the walk's lanes read bytes other lanes stored
+    __syncthreads();
+  }
 
   // ---- the walk back (optimal.h:79-105), emitted in traversal order ---------------------------------------------------------
   int32_t* o = g.trav + (size_t)hit * g.trav_stride * 2;
   const int cap = g.trav_stride;
   int n = 0, same = 0;
   auto sink = [&](int k, int q, int t) {
-    if (k < cap) { o[2 * k] = q; o[2 * k + 1] = t; same += (qc[q] == tc[t]) ? 1 : 0; }
+    if (k < cap) {
+      o[2 * k] = q; o[2 * k + 1] = t;
+      same += (qs[q] == ts[t]) ? 1 : 0;
+    }
   };
   auto emit1 = [&](int q, int t) { if (lane == 0) sink(n, q, t); ++n; };
   emit1(Q - 1, T - 1);
@@ -96,17 +121,19 @@ __global__ __launch_bounds__(64) void align_local_hit_kernel(ScoreArgs a, AlignA
   }
 }
 
-template <int R>
-__global__ __launch_bounds__(64) void align_global_hit_kernel(ScoreArgs a, AlignArgs g, int free_del, int free_ins) {
-  __shared__ int tab[32 * 32];
+template <int R, class Side>
+__global__ __launch_bounds__(64) void align_global_hit_kernel(ScoreArgs a, AlignArgs g, const char* __restrict__ qch,
+                                                             const char* __restrict__ tch, int free_del, int free_ins) {
+  __shared__ __attribute__((aligned(16))) int lds[32 * 32];
   const int lane = threadIdx.x;
-  for (int k = lane; k < 32 * 32; k += 64) tab[k] = a.table32[k];
-  __syncthreads();
+  Side::stage(lds, a);
   const int hit = g.list[blockIdx.x];
   const HitDesc hd = g.desc[hit];
   const int ti = hd.t, qi = hd.q;
-  const uint8_t* __restrict__ qc = a.qcodes + a.qoff[qi];
+  const typename Side::Rows::Src* __restrict__ qr = Side::rows(a, qi);
   const uint8_t* __restrict__ tc = a.tcodes + a.toff[ti];
+  const auto* __restrict__ qs = Side::letters(a.qcodes, qch) + a.qoff[qi];      // what the identity is counted over
+  const auto* __restrict__ ts = Side::letters(a.tcodes, tch) + a.toff[ti];
   const int Q = (int)(a.qoff[qi + 1] - a.qoff[qi]), T = (int)(a.toff[ti + 1] - a.toff[ti]);   // Q >= 3, T >= 3: the host's routing
   const int gi = a.gi, ge = a.ge;
   constexpr int kPitch = 256 * R;
@@ -116,13 +143,13 @@ __global__ __launch_bounds__(64) void align_global_hit_kernel(ScoreArgs a, Align
   cols.load(tc, T, gi, ge);
   GlobalObserver<R> ob(cols, free_del, free_ins ? 0 : ge, Q - 3);
   ob.strip = strip; ob.pitch = kPitch;
-  int score = sweep_global<R>(tab, cols, qc, Q, free_del, free_ins, ob);
+  int score = sweep_global<R, typename Side::Rows>(lds, cols, qr, Q, free_del, free_ins, ob);
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) score = max(score, __shfl_xor(score, off));
 
   int i, j;
   ob.final_cell(free_ins, i, j);
-  __threadfence();                                           // the walk's lanes read bytes other lanes stored
+  __threadfence();                                           // (staged side: the last copy has landed;) the walk's lanes read bytes other lanes stored
   __syncthreads();
 
   // ---- the walk back (optimal.h:56-74): it always runs to a cell of row 1 or column 1, which points at (0,0) -------------------
@@ -130,7 +157,10 @@ __global__ __launch_bounds__(64) void align_global_hit_kernel(ScoreArgs a, Align
   const int cap = g.trav_stride;
   int n = 0, same = 0;
   auto sink = [&](int k, int q, int t) {
-    if (k < cap) { o[2 * k] = q; o[2 * k + 1] = t; same += (qc[q] == tc[t]) ? 1 : 0; }
+    if (k < cap) {
+      o[2 * k] = q; o[2 * k + 1] = t;
+      same += (qs[q] == ts[t]) ? 1 : 0;
+    }
   };
   auto emit1 = [&](int q, int t) { if (lane == 0) sink(n, q, t); ++n; };
   emit1(Q - 1, T - 1);
@@ -148,11 +178,6 @@ __global__ __launch_bounds__(64) void align_global_hit_kernel(ScoreArgs a, Align
     g.same[hit] = same;
   }
 }
-
-// The instantiations kept: every one compiles without scratch memory and without VGPR spills (DESIGN 4.8d has the table).
-// R = 8 (templates of 1793 .. 2048 columns) does not — 24 VGPRs spilled into AGPRs — so that class goes the batch route.
-constexpr unsigned kFusedClasses = 0x0FEu;                   // bit R set: class R runs in align_local_hit_kernel<R>
-constexpr unsigned kFusedGlobalClasses = 0x1FEu;             // bit R set: class R runs in align_global_hit_kernel<R>
 
 // The batch route over the listed slots: aln_batch_create + aln_batch_dp + aln_batch_optimal / _strings, in the groups
 // BatchGroup (score_common.h) cuts under the plane budget.  prof != nullptr: `queries` holds the query
@@ -206,7 +231,9 @@ static int align_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
   const int rows = run.rows, n_t = run.n_t;
   if (rows == 0) return ALN_OK;
   const bool fused_ok = run.route == ScoreRun::kFast && (run.local || ctx->hints.align_fused_nonlocal);
-  const unsigned fused_classes = prof ? align_prof_classes(run.local) : (run.local ? kFusedClasses : kFusedGlobalClasses);
+  // the instantiations kept: every one compiles without scratch memory and without VGPR spills (the masks are the side's)
+  const unsigned fused_classes = prof ? (run.local ? ProfileQuery::kFusedLocal : ProfileQuery::kFusedGlobal)
+                                      : (run.local ? ResidueQuery::kFusedLocal : ResidueQuery::kFusedGlobal);
   // a fused hit's strip rows and the most entries its list can have
   auto strip_rows = [&](const HitDesc& d) {
     return run.local ? d.q_end - 1 : (int)(queries->offsets[d.q + 1] - queries->offsets[d.q]) - 3;
@@ -335,17 +362,23 @@ static int align_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
       for (int k = 1; k <= 8; ++k) {
         if (c.cls_cnt[k] == 0) continue;
         g.list = dlist + co.off[k];
-        if (prof)
-          launch_align_hit_prof(k, run.local, c.cls_cnt[k], ctx->stream, run.a, g, dqch, dtch, run.free_del, run.free_ins);
-        else if (run.local)
-          dispatch_r<7>(k, [&](auto rc) {                       // (class 8 never gets here: kFusedClasses)
-            hipLaunchKernelGGL(align_local_hit_kernel<decltype(rc)::value>, dim3(c.cls_cnt[k]), dim3(64), 0, ctx->stream, run.a, g);
-          });
-        else
-          dispatch_r<8>(k, [&](auto rc) {                       // kFusedGlobalClasses
-            hipLaunchKernelGGL(align_global_hit_kernel<decltype(rc)::value>, dim3(c.cls_cnt[k]), dim3(64), 0, ctx->stream, run.a, g,
-                               run.free_del, run.free_ins);
-          });
+        auto launch = [&](auto side) {
+          typedef decltype(side) Side;
+          const dim3 grid(c.cls_cnt[k]), block(64);
+          const char *qch = Side::kStaged ? dqch : nullptr, *tch = Side::kStaged ? dtch : nullptr;
+          constexpr int kLocalMax = ((Side::kFusedLocal >> 8) & 1u) ? 8 : 7;   // a class the mask leaves out never gets here
+          if (run.local)
+            dispatch_r<kLocalMax>(k, [&](auto rc) {
+              hipLaunchKernelGGL((align_local_hit_kernel<decltype(rc)::value, Side>), grid, block, 0, ctx->stream, run.a, g, qch, tch);
+            });
+          else
+            dispatch_r<8>(k, [&](auto rc) {
+              hipLaunchKernelGGL((align_global_hit_kernel<decltype(rc)::value, Side>), grid, block, 0, ctx->stream, run.a, g, qch, tch,
+                                 run.free_del, run.free_ins);
+            });
+        };
+        if (prof) launch(ProfileQuery());
+        else launch(ResidueQuery());
         STRY(hipGetLastError());
       }
       if (want_lines) {

@@ -143,23 +143,22 @@ __global__ __launch_bounds__(256) void scatter_cols_kernel(float* slab, int n_t,
 // row-major order does.  Per lane: the row at which the running maximum last strictly improved and — inside that rare
 // branch — the smallest of the lane's columns holding it; the wave reduces by (value max, row min, column min); then the seed
 // exception: D[Q-2][T-2] is in the registers when the sweep ends.  A maximum of 0 (no positive cell, or no interior) is the seed's.
-// (FirstMaxObserver: score_common.h, shared with the profile twin of this kernel.)
-template <int R>
+// (FirstMaxObserver: score_common.h.  Side: the query side, ResidueQuery or ProfileQuery, same header.)
+template <int R, class Side>
 __global__ __launch_bounds__(64) void score_local_end_kernel(ScoreArgs a, const int32_t* __restrict__ list, aln_hit* hits, int K) {
-  __shared__ int tab[32 * 32];
+  __shared__ __attribute__((aligned(16))) int lds[32 * 32];
   const int lane = threadIdx.x;
-  for (int k = lane; k < 32 * 32; k += 64) tab[k] = a.table32[k];
-  __syncthreads();
+  Side::stage(lds, a);
   const int slot = list[blockIdx.x];
   const int ti = hits[slot].t, qi = a.q_begin + slot / K;
-  const uint8_t* __restrict__ qc = a.qcodes + a.qoff[qi];
+  const typename Side::Rows::Src* __restrict__ qr = Side::rows(a, qi);
   const uint8_t* __restrict__ tc = a.tcodes + a.toff[ti];
   const int Q = (int)(a.qoff[qi + 1] - a.qoff[qi]), T = (int)(a.toff[ti + 1] - a.toff[ti]);
   LocalCols<R> cols;
   cols.load(tc, T, a.gi, a.ge);
   int d[R][4];
   FirstMaxObserver first;
-  const int lmax = sweep_local<R>(tab, cols, qc, Q - 2, d, first);
+  const int lmax = sweep_local<R, typename Side::Rows>(lds, cols, qr, Q - 2, d, first);
   // wave reduction: value max, then row min, then column min among the lanes that hold it
   int m = lmax;
 #pragma unroll
@@ -310,9 +309,10 @@ static int search_block(ScoreRun& run, int32_t K, float min_score, aln_hit* hits
       s.q_begin = q_begin + r0;
       for (int c = 1; c <= 8; ++c) {
         if (cls_cnt[c] == 0) continue;
-        if (prof) launch_score_local_end_prof(c, cls_cnt[c], ctx->stream, s, dlist + co.off[c], dhits, K);
-        else dispatch_r<8>(c, [&](auto rc) {
-          hipLaunchKernelGGL(score_local_end_kernel<decltype(rc)::value>, dim3(cls_cnt[c]), dim3(64), 0, ctx->stream, s, dlist + co.off[c], dhits, K);
+        dispatch_r<8>(c, [&](auto rc) {
+          constexpr int R = decltype(rc)::value;
+          if (prof) hipLaunchKernelGGL((score_local_end_kernel<R, ProfileQuery>), dim3(cls_cnt[c]), dim3(64), 0, ctx->stream, s, dlist + co.off[c], dhits, K);
+          else hipLaunchKernelGGL((score_local_end_kernel<R, ResidueQuery>), dim3(cls_cnt[c]), dim3(64), 0, ctx->stream, s, dlist + co.off[c], dhits, K);
         });
         STRY(hipGetLastError());
         n_end += cls_cnt[c];

@@ -1,5 +1,5 @@
-// search_zscore.h — what aln_hits_zscores (search_zscore.hip) and aln_hits_zscores_profiles (search_zscore_profile.hip) share:
-// the shuffle rule on the device and once more on the host, the class of a hit slot, the z formula and the two budgets.
+// search_zscore.h — the pieces of aln_hits_zscores / aln_hits_zscores_profiles (search_zscore.hip) that are not kernels: the
+// shuffle rule, stated once for the device and the host, the class of a hit slot, the z formula and the two budgets.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -11,9 +11,22 @@ namespace aln {
 constexpr int kShufGroup = 32;                    // most shuffles one wave scores (template state is set up once per wave)
 constexpr size_t kZBudget = (size_t)1 << 30;      // bytes of shuffled strings (or orders), and of accumulators, resident at a time
 
-__device__ __forceinline__ uint32_t fmix32(uint32_t x) {
+__host__ __device__ __forceinline__ uint32_t fmix32(uint32_t x) {
   x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
   return x;
+}
+
+// Shuffle s of query q under `seed` (the rule of include/aln_hip.h): Fisher-Yates from the top over `interior`, what lies between
+// the sentinels — residue codes on the device, residue characters on the host, or the indices 0 .. n-1 of a profile's interior
+// rows — n of them.  Serial per string; the strings are independent.
+template <class V>
+__host__ __device__ __forceinline__ void shuffle_interior(uint32_t seed, uint32_t q, uint32_t s, V* interior, int n) {
+  const uint32_t key = fmix32(fmix32(fmix32(seed ^ 0x9E3779B9u) + q) + s);
+  for (int i = n - 1; i >= 1; --i) {
+    const uint32_t r = fmix32(key + (uint32_t)i * 0x9E3779B9u);
+    const int j = (int)(((uint64_t)r * (uint32_t)(i + 1)) >> 32);
+    const V x = interior[i]; interior[i] = interior[j]; interior[j] = x;
+  }
 }
 
 // slot (row * K + k) -> the length class of its template, 0: beyond 2048 columns (scored on the host side), -1: unused slot
@@ -27,27 +40,6 @@ struct SlotClass {
     return T > 2048 ? 0 : (T + 255) / 256;
   }
 };
-
-// The permutation once more, on the host: the full-build route's queries do not come from the device kernels.  `interior` is
-// what lies between the sentinels (residue characters, or the indices 0 .. n-1 of a profile's interior rows), n of them.
-inline uint32_t host_fmix(uint32_t h) {
-  h = (h ^ (h >> 16)) * 0x85EBCA6Bu;
-  h = (h ^ (h >> 13)) * 0xC2B2AE35u;
-  return h ^ (h >> 16);
-}
-template <class V>
-inline void host_shuffle_interior(uint32_t seed, uint32_t q, uint32_t s, V* interior, int64_t n) {
-  const uint32_t golden = 0x9E3779B9u;
-  const uint32_t key = host_fmix(host_fmix(host_fmix(seed ^ golden) + q) + s);
-  for (int64_t hi = n - 1; hi > 0; --hi) {
-    const uint64_t draw = host_fmix(key + (uint32_t)hi * golden);
-    const int64_t lo = (int64_t)((draw * (uint64_t)(hi + 1)) >> 32);
-    std::swap(interior[hi], interior[lo]);
-  }
-}
-inline void host_shuffle(uint32_t seed, uint32_t q, uint32_t s, char* seq, int64_t Q) {
-  host_shuffle_interior(seed, q, s, seq + 1, Q - 2);   // '^' and '$' stay
-}
 
 inline float z_of(int64_t n, float score, int64_t sum, int64_t sumsq) {
   if (n < 2) return 0.0f;

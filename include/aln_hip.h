@@ -404,7 +404,7 @@ typedef struct {
  * (ALN_GAP_AFFINE_CONST) and align type; n outside 1..30, NULL alphabet / rows / offsets, a profile of fewer than 2 rows
  * (ALN_E_ARG); a template letter outside the alphabet (ALN_E_RESIDUE); more than 65534 rows or residues (ALN_E_TOO_LONG).
  * Routes: integer entries (of the interior rows of the whole pool) and gaps inside aln_score_all_vs_all's 2^23 bound, templates
- * of up to 2048 columns — register-resident kernels (csrc/score_profile.hip): the device holds the rows of [q_begin, q_end) as
+ * of up to 2048 columns — register-resident kernels (csrc/score_only.hip): the device holds the rows of [q_begin, q_end) as
  * 32 x int32 each (the search uploads them slab by slab when they exceed 1 GiB) and nothing per cell touches HBM.  Everything
  * else — a fractional entry or gap, the bound exceeded, longer templates — goes through resident batches inside the call and so
  * accepts what aln_batch_dp accepts; the Q x T planes of a batch are expanded ON THE HOST for this fallback (it is the 4 B/cell
@@ -463,7 +463,7 @@ int aln_hits_zscores(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* temp
  * profiles derived from residue queries under an integral table (row i = the table row of residue i) the result is
  * byte-identical to aln_hits_zscores on those residues with the same seed.
  * The permuted profiles are not materialised: the device keeps one copy of a profile's rows and reads it in permuted order
- * (csrc/search_zscore_profile.hip), 2 B per row and shuffle; the chunking is aln_hits_zscores' (hints "zscore_chunk_rows",
+ * (csrc/search_zscore.hip), 2 B per row and shuffle; the chunking is aln_hits_zscores' (hints "zscore_chunk_rows",
  * "zscore_rows_per_chunk").  Templates beyond 2048 columns are scored through full builds inside the call.
  * INTEGER SCORING ONLY: a pool aln_score_profiles_vs_all would send through full builds as a whole (a fractional entry or gap,
  * its 2^23 bound exceeded) is refused with ALN_E_NOT_INTEGRAL.
@@ -529,7 +529,7 @@ int aln_hits_align(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templa
  * aln_batch_optimal_strings does.
  * Routes: integer rows (of the interior rows of the whole pool) and gaps inside aln_score_all_vs_all's 2^23 bound, Q >= 3 and
  * T >= 3, a template of up to 2048 columns — one wave per hit, the rows staged from HBM into LDS 8 at a time, 1 byte per cell
- * into a transient strip (csrc/search_align_profile.hip), for all five align types.  Everything else — fractional rows or gaps,
+ * into a transient strip (csrc/search_align.hip), for all five align types.  Everything else — fractional rows or gaps,
  * longer templates, pairs without an interior — goes through resident batches inside the call, whose planes are expanded on
  * the host and counted in the ~12 GB budget.  The device rows of [q_begin, q_end) are uploaded once when they fit 1 GiB, else
  * with every chunk of hits (hint "align_rows_per_chunk").

@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 U32 = np.uint32
 MODES = [aln_amd.GLOBAL_LOCAL, aln_amd.GLOBAL, aln_amd.LOCAL_GLOBAL, aln_amd.SEMI_LOCAL]
-FUSED_CLASSES = range(1, 9)          # kFusedGlobalClasses (csrc/search_align.hip): templates of up to 2048 columns
+FUSED_CLASSES = range(1, 9)          # ResidueQuery::kFusedGlobal (csrc/score_common.h): templates of up to 2048 columns
 
 
 def fused_expected(q, t):

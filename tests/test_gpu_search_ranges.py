@@ -31,7 +31,7 @@ U32 = np.uint32
 ALPHA = sc.ALPHA
 SEED = 2024
 K_ALL = sc.N_TEMPLATES
-LOCAL_FUSED_CLASSES = range(1, 8)            # kFusedClasses / kFusedGlobalClasses (csrc/search_align.hip)
+LOCAL_FUSED_CLASSES = range(1, 8)            # ResidueQuery::kFusedLocal / kFusedGlobal (csrc/score_common.h)
 NONLOCAL_FUSED_CLASSES = range(1, 9)
 Z_MODES_BIG = (rc.LOCAL, rc.GLOBAL)
 Z_33 = ("score32_in", "identity5")           # one case per size also runs 33 shuffles

@@ -1,5 +1,5 @@
 """-m gpu: aln_hits_zscores_profiles — shuffle z-scores for the hits of a profile search; the device reads ONE resident copy of
-a profile's rows in permuted order (csrc/search_zscore_profile.hip).
+a profile's rows in permuted order (csrc/search_zscore.hip).
 
   1  profiles derived from residue queries equal aln_hits_zscores byte for byte: every length class, the degenerate shapes, both
      sides of the shuffle-group boundary, all five align types
