@@ -7,7 +7,8 @@
 //   * every operation is followed along the stored pointers to the end of the template's current flag region; the visited
 //     cells (template position -> query position), the sub-path's length, end cell, end region and running score are kept;
 //   * in sorted order an operation is accepted unless an accepted, better one that ends in the same region shares more than
-//     max_overlap * (its own length) cells with it (+1 if both end in the same cell); at most `limit` are accepted;
+//     max_overlap * (its own length) cells with it (+1 if both end in the same cell, but at least one cell must really be
+//     shared: the comparison is made only after counting one); at most `limit` are accepted;
 //   * each accepted operation becomes an alignment (the first continues the node's alignment, the others copy its state before
 //     the node), extended by its whole sub-path; the best keeps the node's limit, the others get max(2, limit/2);
 //   * sub-paths that end within two cells of the origin are finished along the stored pointers at once; the others recurse.
@@ -257,11 +258,14 @@ __global__ __launch_bounds__(64) void enumerate_cr_kernel(const PairDesc* __rest
             // cells of both sub-paths exist only on template positions (p_rt, t_start]; everything else reads -1
             const int hi = (ti < o_t[j] ? ti : o_t[j]), lo = (rti > o_rt[j] ? rti : o_rt[j]);
             const uint16_t* rj = a.cr_ali + (size_t)j * tpad;
+            bool shared = false;
             for (int k = hi - 1; k >= lo; --k) {
               const uint16_t x = ld16(ri + k);
-              if (x != kNoQ && x == ld16(rj + k)) ++overlap;
+              if (x != kNoQ && x == ld16(rj + k)) { ++overlap; shared = true; }
             }
-            rej = overlap > overlap_max;
+            // crcw.h:444-454 compares overlap with its maximum only after counting a shared cell: the +1 of a common end cell
+            // alone never rejects, however small max_overlap * l_sp[j] is
+            rej = shared && overlap > overlap_max;
           }
           if (__ballot(rej)) rejected = true;
         }

@@ -9,6 +9,8 @@ Runs oracle/_ref/ref_harness (christang/alignment-algos compiled in place from
   tests/golden/profile_cases.*        the profile path at its default parameters (oracle/_ref/ref_profile)
   tests/golden/profile_param_cases.*  the profile path off them; `gen_golden.py profile_params` rewrites these two alone,
                                       byte for byte
+  tests/golden/enum_modes.json        CW / UCW sets in the one-sided align types 0 and 2 (cases of tests/enum_mode_cases.py);
+                                      `gen_golden.py enum_modes` rewrites this file alone
 
 Only this container has /root/reference; the fixtures are what travels.  Inputs are
 regenerated from seeds by aln_amd.synth (std::mt19937-compatible), but the sequences are
@@ -245,10 +247,39 @@ def gen_profile_params():
     print("profile parameter cases", len(meta))
 
 
+def gen_enum_modes():
+    """ConstrainedNearOptimal / UnconstrainedNearOptimal of the real reference in the two one-sided align types (0 and 2): the
+    constant-gap small cases of tests/enum_mode_cases.py at 11/1 and 4.73/0.34, with that module's search parameters.  Writes
+    tests/golden/enum_modes.json alone (aa_cases.* are not touched): plane digests, the Optimal set, and the CW and UCW sets
+    with the first 6 pair lists in full."""
+    if not refrun.available():
+        raise SystemExit("oracle/_ref/ref_harness missing: run `make -C oracle` where the reference exists")
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import enum_mode_cases as em
+    cases = []
+    for c, mode, fam in em.golden_runs():
+        gi, ge = em.CONST[fam]
+        cw, ucw = em.params(c, fam, "cw"), em.params(c, fam, "ucw")
+        fl = "".join(str(int(x)) for x in em.flags(c, fam, "cw"))
+        r = refrun.run_aa(c.q, c.t, mode, gi, ge, "fwd", ops=["dump", "opt", "cw", cw["nsub"], cw["delta"], fl, "ucw", ucw["nsub"], ucw["delta"]])
+        assert "throw" not in r and set(r["sets"]) == {"OPT", "CW", "UCW"}, (c.name, mode, fam, r.get("throw"))
+        cases.append({"name": em.golden_name(c, mode, fam), "case": c.name, "q": c.q, "t": c.t, "mode": mode, "gi": gi, "ge": ge, "dir": "fwd",
+                      "flags": fl, "nsub": cw["nsub"], "delta": {"CW": cw["delta"], "UCW": ucw["delta"]},
+                      "sha": {"H": sha(r["H"]), "PQ": sha(r["PQ"]), "PT": sha(r["PT"])},
+                      "sets": {k: set_json(v, 6) for k, v in sorted(r["sets"].items())}})
+    with open(os.path.join(GOLD, "enum_modes.json"), "w") as f:
+        json.dump({"generator": "oracle/gen_golden.py enum_modes via oracle/_ref/ref_harness (real reference, g++ -O2, no -ffast-math)",
+                   "cases": cases}, f, separators=(",", ":"), sort_keys=True)
+    print("enum mode cases", len(cases))
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["profile_params"]:
         gen_profile_params()
+    elif sys.argv[1:] == ["enum_modes"]:
+        gen_enum_modes()
     else:
         main()
         gen_profiles()
         gen_profile_params()
+        gen_enum_modes()

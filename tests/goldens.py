@@ -1,4 +1,5 @@
-"""Loader for tests/golden/aa_cases.{json,npz} (outputs of the real reference, see oracle/gen_golden.py)."""
+"""Loader for tests/golden/aa_cases.{json,npz} and tests/golden/enum_modes.json (outputs of the real reference, see
+oracle/gen_golden.py)."""
 import hashlib
 import json
 import os
@@ -8,6 +9,7 @@ import numpy as np
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 _J = None
 _Z = None
+_E = None
 
 
 def load():
@@ -22,6 +24,16 @@ def load():
 def cases(prefix=None):
     j, _ = load()
     return [c for c in j["cases"] if prefix is None or c["name"].startswith(prefix)]
+
+
+def enum_mode_cases():
+    """name -> case of tests/golden/enum_modes.json: the reference's OPT / CW / UCW sets in the one-sided align types 0 and 2, in
+    the format of aa_cases.json (check_set and the digest branch of check_matrices apply as they are)"""
+    global _E
+    if _E is None:
+        with open(os.path.join(GOLD, "enum_modes.json")) as f:
+            _E = {c["name"]: c for c in json.load(f)["cases"]}
+    return _E
 
 
 def subs():
