@@ -89,7 +89,7 @@ EXPORTS = [
     "aln_ctx_create", "aln_ctx_destroy", "aln_error_string", "aln_last_error", "aln_ctx_synchronize", "aln_has_gfx950",
     "aln_batch_create", "aln_batch_destroy", "aln_batch_n_pairs", "aln_batch_device_bytes", "aln_batch_dp",
     "aln_batch_reevaluate", "aln_batch_dp_kernel_name", "aln_batch_dp_sub", "aln_batch_get_cells", "aln_batch_get_sim",
-    "aln_batch_get_corner_scores", "aln_batch_optimal", "aln_batch_optimal_enqueue", "aln_batch_optimal_collect", "aln_batch_optimal_subali", "aln_batch_enumerate", "aln_batch_enumerate_all", "aln_batch_last_enum_ms", "aln_batch_last_enum_usage", "aln_identity",
+    "aln_batch_get_corner_scores", "aln_batch_optimal", "aln_batch_optimal_enqueue", "aln_batch_optimal_collect", "aln_batch_optimal_subali", "aln_batch_enumerate", "aln_batch_enumerate_all", "aln_batch_last_enum_ms", "aln_batch_last_enum_usage", "aln_batch_last_enum_tasks", "aln_identity",
     "aln_gapped_length", "aln_gapped_strings", "aln_hmap2_gap_arrays", "aln_score_all_vs_all", "aln_batch_last_dp_ms", "aln_batch_dp_ms_history", "aln_batch_dp_algorithmic_bytes", "aln_batch_cells",
     "aln_batch_optimal_strings", "aln_batch_optimal_strings_enqueue", "aln_batch_optimal_strings_collect", "aln_batch_last_exact_stats", "aln_batch_set_gap", "aln_ctx_set_hint", "aln_ctx_get_hint", "aln_batch_dp_contract_bytes", "aln_batch_plane_bytes_per_cell",
     "aln_deal_units", "aln_comm_unique_id", "aln_comm_create", "aln_ctx_create_multi", "aln_comm_destroy", "aln_comm_n_ranks",
@@ -151,6 +151,7 @@ def lib():
                                               C.c_int32, _ip, _fp, _ip, _ip, C.c_int32, _ip]
         L.aln_batch_last_enum_ms.argtypes = [C.c_void_p, _fp, _fp]
         L.aln_batch_last_enum_usage.argtypes = [C.c_void_p, _ip, _ip]
+        L.aln_batch_last_enum_tasks.argtypes = [C.c_void_p, _ip]
         L.aln_identity.argtypes = [C.c_char_p, C.c_int32, C.c_char_p, C.c_int32, _ip, C.c_int32]
         L.aln_gapped_length.argtypes = [C.c_int32, C.POINTER(AlnAlignment), C.c_int32, _ip]
         L.aln_gapped_strings.argtypes = [C.c_char_p, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(AlnAlignment), C.c_int32, _ip,
@@ -897,12 +898,18 @@ class Batch:
         return s
 
     def enumerate(self, p, kind, number_suboptimal, delta_ratio, flags=None, user_limit=0, max_alignments=None, pairs_capacity=None,
-                  k_limit=0, sort_limit=0, max_overlap=0.30):
+                  k_limit=0, sort_limit=0, max_overlap=0.30, existing_scores=None):
         """ConstrainedNearOptimal ("cw") / UnconstrainedNearOptimal ("ucw") / KSConstrainedNearOptimal ("kscw") /
-        CRConstrainedNearOptimal ("crcw") for pair p -> list of dicts in set order."""
+        CRConstrainedNearOptimal ("crcw") for pair p -> list of dicts in set order.  existing_scores: None seeds the set with the
+        pair's Optimal alignment; a sequence (possibly empty) is the scores of the set the caller already holds, and those
+        entries come back as dict(score=..., existing=their old index)."""
         Q, T = self.dims(p)
+        ex, n_ex = None, -1
+        if existing_scores is not None:
+            ex = np.ascontiguousarray(existing_scores, dtype=np.float32)
+            n_ex = len(ex)
         noa = AlnNoa(_ENUM[kind], int(number_suboptimal), float(np.float32(delta_ratio)),
-                     int(user_limit), -1, None, int(k_limit), int(sort_limit), float(np.float32(max_overlap)))
+                     int(user_limit), n_ex, _f(ex) if n_ex > 0 else None, int(k_limit), int(sort_limit), float(np.float32(max_overlap)))
         if max_alignments is None:
             max_alignments = max(int(number_suboptimal), 1) + 2
         if pairs_capacity is None:
@@ -919,6 +926,9 @@ class Batch:
         res = []
         for k in range(n.value):
             a = out[k]
+            if a.n_pairs == -1:
+                res.append({"score": np.float32(a.score), "existing": a.pair_off})
+                continue
             res.append({"score": np.float32(a.score), "identity": np.float32(a.identity), "uid": a.uid,
                         "pairs": pairs[a.pair_off:a.pair_off + a.n_pairs].copy()})
         return res
@@ -956,6 +966,12 @@ class Batch:
         nd = np.zeros(self.n, dtype=np.int32)
         _check(lib().aln_batch_last_enum_usage(self.h, _i(a), _i(nd)), self.ctx.h)
         return a, nd
+
+    def last_enum_tasks(self):
+        """-> tickets the several-wave kernel handed out per pair in the last enumerate_all (0: the one-wave kernel searched it)"""
+        t = np.zeros(self.n, dtype=np.int32)
+        _check(lib().aln_batch_last_enum_tasks(self.h, _i(t)), self.ctx.h)
+        return t
 
     def last_enum_ms(self):
         a, b = C.c_float(0), C.c_float(0)

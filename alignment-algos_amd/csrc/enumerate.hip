@@ -885,7 +885,8 @@ extern "C" int aln_batch_enumerate_all(aln_batch* b, const aln_noa* noa, const u
     std::vector<int64_t> off(gn + 1, 0);                    // the sets' slots, packed: pair g's slot k is record off[g] + k
     for (int g = 0; g < gn; ++g) {
       const int p = ids[g];
-      for (int w = 0; w < 4; ++w) b->enum_usage[(size_t)p * 4 + w] = hout[4 * g + w];
+      for (int w = 0; w < 3; ++w) b->enum_usage[(size_t)p * 4 + w] = hout[4 * g + w];
+      b->enum_usage[(size_t)p * 4 + 3] = pw ? hout[4 * g + 3] : 0;       // tickets of the several-wave kernel's task ring
       status[p] = hout[4 * g + 2] ? hout[4 * g + 2] : res[p].status;
       n_out[p] = 0;
       off[g + 1] = off[g];
@@ -1040,6 +1041,13 @@ extern "C" int aln_batch_last_enum_usage(aln_batch* b, int32_t* alignments, int3
     if (alignments) alignments[p] = b->enum_usage[4 * p];
     if (nodes) nodes[p] = b->enum_usage[4 * p + 1];
   }
+  return ALN_OK;
+}
+
+extern "C" int aln_batch_last_enum_tasks(aln_batch* b, int32_t* tasks) {
+  if (!b || !tasks) return ALN_E_ARG;
+  if ((int)b->enum_usage.size() != 4 * b->n_pairs) return ALN_E_STATE;
+  for (int p = 0; p < b->n_pairs; ++p) tasks[p] = b->enum_usage[4 * p + 3];
   return ALN_OK;
 }
 

@@ -585,6 +585,7 @@ __global__ __launch_bounds__(1024) void enumerate_par_kernel(const PairDesc* __r
   if (threadIdx.x == 0) {
     const int status = s_status;
     a.out[0] = (int32_t)s_slots; a.out[1] = (int32_t)s_nodes; a.out[2] = status;
+    a.out[3] = s_tail;                                 // tickets handed out: beyond ali_cap the task ring has wrapped
   }
 }
 

@@ -147,8 +147,11 @@ typedef struct {
   uint32_t user_limit;          /* 0 = the reference's hard-coded 1000000 (cw.h:76) / 100000 (ucw.h:72) */
   int32_t n_existing;           /* < 0: seed the set with the pair's Optimal alignment like the drivers (aa_ali.cpp:83);
                                    >= 0: the caller's AlignmentSet already holds this many alignments (enumerate() appends) */
-  const float* existing_scores; /* their scores (they take part in sortSet); such entries come back with n_pairs = -1
-                                   and pair_off = their old index */
+  const float* existing_scores; /* their scores (they take part in sortSet); such entries come back with n_pairs = -1,
+                                   pair_off = their old index, uid -1, identity 0 and the caller's score.  NULL with
+                                   n_existing > 0 is ALN_E_ARG.  The entries count for the brake `as.size() > user_limit`
+                                   (cw.h:127) like the reference's own; KSCW / CRCW number what they create by its place
+                                   in the WHOLE set (uid = index, kscw.h:262; the enumerator's seed has uid 1) */
   uint32_t k_limit;             /* KSCW / CRCW: operations a branch node keeps (NOaliParams::k_limit, default 16); their user_limit
                                    is NOaliParams::user_limit (0 = the default 100000, noalib.cpp:20) */
   uint32_t sort_limit;          /* CRCW: operations a branch node sorts and follows (NOaliParams::sort_limit; 0 = the default 100) */
@@ -313,7 +316,10 @@ int aln_batch_optimal_subali(aln_batch* b, float* scores, int32_t* n, int32_t* p
  * of the resident batch.  The set is seeded with the pair's Optimal alignment exactly like the drivers do
  * (aa_ali.cpp:83-89), the enumerator pushes its own uid-0 seed on top (B16), and the result is
  * sortSet(number_suboptimal)'ed.  flags: T bytes (SuboptFlags, sflags.h:23-37), ignored for UCW.
- * Outputs: up to max_alignments records + their pairs; *n_out = set size after sortSet. */
+ * With noa->n_existing >= 0 the set is the caller's instead (see aln_noa): enumerate() appends to it, the seed included.
+ * number_suboptimal 0 keeps everything in the order of creation (sortSet sorts nothing, alignment.h:925-931).
+ * Outputs: up to max_alignments records + their pairs; *n_out = set size after sortSet.  ALN_E_OVERFLOW with max_alignments
+ * smaller than that set *n_out to the size needed and writes no record; an argument or state error writes nothing at all. */
 int aln_batch_enumerate(aln_batch* b, int32_t pair, const aln_noa* noa, const uint8_t* flags,
                         aln_alignment* out, int32_t max_alignments,
                         int32_t* pairs, int64_t pairs_capacity, int32_t* n_out);
@@ -329,6 +335,12 @@ int aln_batch_enumerate(aln_batch* b, int32_t pair, const aln_noa* noa, const ui
  *   the several-wave kernel, whose node pool is moreover shared by the pairs of a launch (n_pairs x node_cap_per_pair nodes in
  *   all: a 2000-residue homolog at DELTA_RATIO 0.01 needs 0.03-0.8 M of them).  Pairs that need more are searched again with 4 x larger pools, in groups sized to a device-memory budget,
  *   "enum_pool_retries" times (context hint, default 2), and only then report ALN_E_OVERFLOW;  K: slots per pair in the outputs (>= min(number_suboptimal, set size)).
+ *   (Rounds continue past that count while the alignment pool is smaller than user_limit bounds, user_limit + 65536 + 16 (Q + T)
+ *   slots, and every such round grows the node pool too.  The several-wave kernel hands its pool out in chunks of 65536 nodes,
+ *   n_pairs x node_cap_per_pair nodes rounded down to chunks, at least one: below one chunk per pair some pairs get none and
+ *   report ALN_E_OVERFLOW, and a few nodes per pair are still that one chunk after both 4 x retries.)
+ *   A pair whose set after sortSet is larger than K reports ALN_E_OVERFLOW with n_out = K and its first K entries; an argument
+ *   or state error (K <= 0, pair_stride < the batch's path stride, a REV or a sub-matrix build) writes no output.
  * Outputs (slot k of pair p at index p*K + k, set order): n_out[p] = set size after sortSet, scores, lengths,
  * pairs (NULL = not wanted) as (q,t) int32 at (p*K + k) * pair_stride * 2, status[p] = 0 / ALN_E_STARTPAIR /
  * ALN_E_OVERFLOW.  Returns the worst per-pair status. */
@@ -340,6 +352,11 @@ int aln_batch_enumerate_all(aln_batch* b, const aln_noa* noa, const uint8_t* fla
  * as.size(), cw.h:91) and trie nodes (the several-wave kernel: runs, reserved 512 at a time by each wave) — also for pairs that reported ALN_E_OVERFLOW (the count at which they stopped), so that a
  * caller can size node_cap_per_pair / ali_cap_per_pair.  Either pointer may be NULL. */
 int aln_batch_last_enum_usage(aln_batch* b, int32_t* alignments, int32_t* nodes);
+/* Tickets the several-wave kernel handed out for every pair in the last aln_batch_enumerate_all (the search of that pair which
+ * was run last: the final retry, or 0 when the one-wave kernel searched it, as it does for crcw, with enum_waves 1 and for a
+ * pair that reached user_limit).  A pair's task ring has as many records as its alignment pool, so a count above the
+ * ali_cap_per_pair of that search means the ring wrapped. */
+int aln_batch_last_enum_tasks(aln_batch* b, int32_t* tasks);
 /* Milliseconds the device spent in the search kernel / the unroll kernel of the last aln_batch_enumerate_all. */
 int aln_batch_last_enum_ms(aln_batch* b, float* search_ms, float* unroll_ms);
 

@@ -11,6 +11,8 @@ Runs oracle/_ref/ref_harness (christang/alignment-algos compiled in place from
                                       byte for byte
   tests/golden/enum_modes.json        CW / UCW sets in the one-sided align types 0 and 2 (cases of tests/enum_mode_cases.py);
                                       `gen_golden.py enum_modes` rewrites this file alone
+  tests/golden/enum_chain.json        two enumerations in a row on one AlignmentSet (chains of tests/enum_pool_cases.py);
+                                      `gen_golden.py enum_chain` rewrites this file alone
 
 Only this container has /root/reference; the fixtures are what travels.  Inputs are
 regenerated from seeds by aln_amd.synth (std::mt19937-compatible), but the sequences are
@@ -273,13 +275,43 @@ def gen_enum_modes():
     print("enum mode cases", len(cases))
 
 
+def gen_enum_chain():
+    """Two enumerations in a row on ONE AlignmentSet of the real reference (the harness's chain / chain0 ops): the chains of
+    tests/enum_pool_cases.py.  The second call appends to what the first left, which is what aln_noa.n_existing > 1 promises.
+    Writes tests/golden/enum_chain.json alone: the set after every step, the first 2 pair lists in full."""
+    if not refrun.available():
+        raise SystemExit("oracle/_ref/ref_harness missing: run `make -C oracle` where the reference exists")
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import enum_pool_cases as ep
+    cases = []
+    for c in ep.chain_runs():
+        ops = ["chain0" if c.empty else "chain", len(c.steps)]
+        steps = []
+        for kind, nsub, delta, regions in c.steps:
+            fl = "".join(str(int(x)) for x in ep.flags(c.pair, regions))
+            ops += [kind, nsub, delta] + ([fl] if kind == "cw" else [])
+            steps.append({"kind": kind, "nsub": nsub, "delta": delta, "flags": fl})
+        r = refrun.run_aa(c.pair.q, c.pair.t, c.mode, c.gap[0], c.gap[1], "fwd", ops=ops)
+        want = {"CHAIN%d" % (k + 1) for k in range(len(c.steps))}
+        assert "throw" not in r and set(r["sets"]) == want, (c.name, r.get("throw"))
+        cases.append({"name": c.name, "q": c.pair.q, "t": c.pair.t, "mode": c.mode, "gi": c.gap[0], "ge": c.gap[1], "dir": "fwd",
+                      "empty": c.empty, "steps": steps, "sets": {k: set_json(v, 2) for k, v in sorted(r["sets"].items())}})
+    with open(os.path.join(GOLD, "enum_chain.json"), "w") as f:
+        json.dump({"generator": "oracle/gen_golden.py enum_chain via oracle/_ref/ref_harness (real reference, g++ -O2, no -ffast-math)",
+                   "cases": cases}, f, separators=(",", ":"), sort_keys=True)
+    print("enum chain cases", len(cases))
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["profile_params"]:
         gen_profile_params()
     elif sys.argv[1:] == ["enum_modes"]:
         gen_enum_modes()
+    elif sys.argv[1:] == ["enum_chain"]:
+        gen_enum_chain()
     else:
         main()
         gen_profiles()
         gen_profile_params()
         gen_enum_modes()
+        gen_enum_chain()

@@ -18,6 +18,9 @@
 //   sub <blosum> <align_t> <gi> <ge> <fwd|rev> <query> <templ> q1 t1 q2 t2   (7-arg ctor + Optimal_Subali)
 //   time <blosum> <align_t> <gi> <ge> <len> <seed> <npairs>    (times the DPMatrix ctor)
 //   block <blosum> <align_t> <gi> <ge> <seqfile> r0 r1 c0 c1   (score Optimal reports for every (row, col) of a sequence set)
+// extra op of `aa`: chain|chain0 <n> followed by n steps `cw N delta flags` or `ucw N delta`: the enumerations run one after the
+//   other on ONE AlignmentSet (each sees what the one before left), dumped as CHAIN1 .. CHAINn.  chain starts from Optimal's
+//   set like the drivers; chain0 clear()s it first (AlignmentSet has no constructor that leaves it empty).
 // extra ops of `aa`: bin <path> (planes as raw little-endian int32: Q T, H bits, PQ, PT — for full-size sha256 goldens)
 
 #include <cstdio>
@@ -262,6 +265,31 @@ int main(int argc, char** argv) {
         for (size_t k = 0; k < as.size(); ++k) pairs_total += as[k].size();
         printf("CWCOUNT %d %zu\n", (int)as.size(), pairs_total);
         a += 2;
+      } else if (op == "chain" || op == "chain0") {
+        int steps = atoi(argv[++a]);
+        Optimal<AASequence, AASequence, AAEval> opt(p.align_type);
+        AASet as(dpm, opt);
+        if (op == "chain0") as.clear();
+        for (int s = 0; s < steps; ++s) {
+          std::string kind = argv[++a];
+          NOaliParams noa;
+          noa.number_suboptimal = atoi(argv[++a]);
+          noa.delta_ratio = (float)atof(argv[++a]);
+          if (kind == "cw") {
+            std::string fl = argv[++a];
+            if (fl.size() != t.size()) { fprintf(stderr, "flags length\n"); return 2; }
+            SuboptFlags sf(true, t.size());
+            for (size_t i = 0; i < fl.size(); ++i) sf.Set(i, fl[i] != '0');
+            ConstrainedNearOptimal<AASequence, AASequence, AAEval> c(noa, sf);
+            c.enumerate(dpm, as);
+          } else if (kind == "ucw") {
+            UnconstrainedNearOptimal<AASequence, AASequence, AAEval> c(noa);
+            c.enumerate(dpm, as);
+          } else { fprintf(stderr, "chain step\n"); return 2; }
+          char tag[16];
+          snprintf(tag, sizeof tag, "CHAIN%d", s + 1);
+          dump_set(tag, as);
+        }
       } else if (op == "cw" || op == "ucw") {
         NOaliParams noa;
         noa.number_suboptimal = atoi(argv[a + 1]);

@@ -25,7 +25,7 @@ def _farr(toks):
 
 
 def parse(out):
-    """-> dict with optional keys dim,H,PQ,PT,S,corner,sets{OPT|CW|UCW: {tstr, alis:[...]}},subali,throw"""
+    """-> dict with optional keys dim,H,PQ,PT,S,corner,sets{OPT|CW|UCW|CHAINk: {tstr, alis:[...]}},subali,throw"""
     res = {"sets": {}}
     cur = None
     for line in out.split("\n"):
@@ -41,7 +41,7 @@ def parse(out):
             res[tag] = np.array(tk, dtype=np.int32).reshape(res["dim"])
         elif tag == "CORNER":
             res["corner"] = (_f(tk[0]), _f(tk[1]))
-        elif tag in ("OPT", "CW", "UCW"):
+        elif tag in ("OPT", "CW", "UCW") or tag.startswith("CHAIN"):
             cur = {"n": int(tk[0]), "alis": []}
             res["sets"][tag] = cur
         elif tag == "TSTR":

@@ -1,4 +1,4 @@
-"""Loader for tests/golden/aa_cases.{json,npz} and tests/golden/enum_modes.json (outputs of the real reference, see
+"""Loader for tests/golden/aa_cases.{json,npz}, tests/golden/enum_modes.json and tests/golden/enum_chain.json (outputs of the real reference, see
 oracle/gen_golden.py)."""
 import hashlib
 import json
@@ -10,6 +10,7 @@ GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 _J = None
 _Z = None
 _E = None
+_C = None
 
 
 def load():
@@ -34,6 +35,16 @@ def enum_mode_cases():
         with open(os.path.join(GOLD, "enum_modes.json")) as f:
             _E = {c["name"]: c for c in json.load(f)["cases"]}
     return _E
+
+
+def enum_chain_cases():
+    """name -> case of tests/golden/enum_chain.json: the reference's set after every step of two enumerations chained on one
+    AlignmentSet (sets CHAIN1, CHAIN2, in the format check_set reads)"""
+    global _C
+    if _C is None:
+        with open(os.path.join(GOLD, "enum_chain.json")) as f:
+            _C = {c["name"]: c for c in json.load(f)["cases"]}
+    return _C
 
 
 def subs():
