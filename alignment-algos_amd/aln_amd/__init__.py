@@ -96,6 +96,7 @@ EXPORTS = [
     "aln_comm_last_error", "aln_gather_scores", "aln_gather_resident_enqueue", "aln_gather_resident_collect", "aln_search_topk",
     "aln_hits_zscores", "aln_hits_align", "aln_hits_align_last_routes", "aln_score_profiles_vs_all", "aln_search_topk_profiles",
     "aln_hits_align_profiles", "aln_hits_zscores_profiles", "aln_hits_align_multi",
+    "aln_hits_align_multi_profiles",
 ]
 COMM_ID_BYTES = 128
 
@@ -181,6 +182,10 @@ def lib():
         L.aln_hits_align_multi.argtypes = [C.c_void_p, C.POINTER(AlnSeqs), C.POINTER(AlnSeqs), C.POINTER(AlnSubmatrix), C.POINTER(AlnGap),
                                            C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.c_int32, C.c_float, _ip,
                                            C.POINTER(AlnHitAlignment), _ip, C.c_int32, C.c_char_p, C.c_char_p, C.c_int32, _ip]
+        L.aln_hits_align_multi_profiles.argtypes = [C.c_void_p, C.POINTER(AlnQProfiles), C.POINTER(AlnSeqs), C.POINTER(AlnSeqs),
+                                                    C.POINTER(AlnGap), C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.c_int32,
+                                                    C.c_float, _ip, C.POINTER(AlnHitAlignment), _ip, C.c_int32, C.c_char_p, C.c_char_p,
+                                                    C.c_int32, _ip]
         L.aln_hits_align_last_routes.argtypes = [C.c_void_p, _lp]
         L.aln_hmap2_gap_arrays.argtypes = [_fp, C.c_int64, C.c_float, C.c_float, C.c_float, _fp, _fp]
         L.aln_batch_plane_bytes_per_cell.argtypes = [C.c_void_p]
@@ -603,6 +608,11 @@ def hits_align_multi(ctx, queries, templates, hits, n_hits, alphabet, table, gi,
                                     _i(lengths) if want_lines else None)
     if rc != 0 and not (rec["status"] == rc).any():
         _check(rc, ctx.h)
+    return _multi_results(rec, pairs, tl, ql, lengths, n_found, rc, rows, K, M, pair_stride, line_stride, want_pairs, want_lines)
+
+
+def _multi_results(rec, pairs, tl, ql, lengths, n_found, rc, rows, K, M, pair_stride, line_stride, want_pairs, want_lines):
+    """the flat outputs of aln_hits_align_multi / aln_hits_align_multi_profiles -> hits_align_multi's 7-tuple"""
     rec = rec.reshape(rows, K, M)
     lists = tlines = qlines = None
     if want_pairs:
@@ -618,6 +628,41 @@ def hits_align_multi(ctx, queries, templates, hits, n_hits, alphabet, table, gi,
                       for a in range(M)] for k in range(K)] for r in range(rows)]
         tlines, qlines = cut(tl), cut(ql)
     return rec, lists, tlines, qlines, lengths, n_found, rc
+
+
+def hits_align_multi_profiles(ctx, profiles, templates, hits, n_hits, gi, ge, max_alignments, min_score=-np.inf, consensus=None,
+                              q_begin=0, align_type=LOCAL, want_pairs=True, want_lines=True, pair_stride=None, line_stride=None):
+    """aln_hits_align_multi_profiles: hits_align_multi for the hits of a profile search (profiles: a QueryProfiles; row r is
+    profile q_begin + r; only the slots' t is read).  consensus: the query letters of the lines and the identity, as in
+    hits_align_profiles, or None for the placeholder alphabet[0].  -> the 7-tuple of hits_align_multi."""
+    tpool = templates if isinstance(templates, SeqPool) else SeqPool(templates)
+    cpool = None
+    if consensus is not None:
+        cpool = consensus if isinstance(consensus, SeqPool) else SeqPool(consensus)
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    n_hits = np.ascontiguousarray(n_hits, dtype=np.int32)
+    rows, K = hits.shape
+    N = int(max_alignments)
+    assert n_hits.shape == (rows,)
+    g = _const_gap(align_type, gi, ge)
+    maxq = max([len(p) + 2 for p in profiles.profiles[q_begin:q_begin + rows]] + [2])
+    maxt = max([len(s) for s in tpool.seqs] + [2])
+    if pair_stride is None:
+        pair_stride = min(maxq, maxt) + 3
+    if line_stride is None:
+        line_stride = maxq + maxt + 2
+    M = max(N, 1)
+    rec, pairs, tl, ql, lengths = _hit_outputs(rows, K * M, pair_stride, line_stride, want_pairs, want_lines)
+    n_found = np.zeros((rows, K), dtype=np.int32)
+    rc = lib().aln_hits_align_multi_profiles(ctx.h, C.byref(profiles.c), C.byref(cpool.c) if cpool is not None else None,
+                                             C.byref(tpool.c), C.byref(g), q_begin, q_begin + rows, int(K),
+                                             hits.ctypes.data_as(C.POINTER(AlnHit)), _i(n_hits), N, float(min_score), _i(n_found),
+                                             rec.ctypes.data_as(C.POINTER(AlnHitAlignment)), _i(pairs) if want_pairs else None,
+                                             int(pair_stride) if want_pairs else 0, tl, ql, int(line_stride) if want_lines else 0,
+                                             _i(lengths) if want_lines else None)
+    if rc != 0 and not (rec["status"] == rc).any():
+        _check(rc, ctx.h)
+    return _multi_results(rec, pairs, tl, ql, lengths, n_found, rc, rows, K, M, pair_stride, line_stride, want_pairs, want_lines)
 
 
 def masked_plane(q, t, alphabet, table, forbidden, value):
@@ -657,6 +702,57 @@ def hits_align_multi_detour(ctx, queries, templates, pairs_qt, alphabet, table, 
             part = alive[g0:g0 + group]
             planes = [masked_plane(qs[pairs_qt[p][0]][1:-1], ts[pairs_qt[p][1]][1:-1], alphabet, table, forb[p], neg[p]) for p in part]
             b = Batch(ctx, queries, templates, [pairs_qt[p][0] for p in part], [pairs_qt[p][1] for p in part])
+            try:
+                b.dp_simmatrix(planes, LOCAL, gi, ge)
+                scores, lists, status = b.optimal()
+                s2, ident, st2, tl, ql = b.optimal_strings()
+            finally:
+                b.close()
+            for k, p in enumerate(part):
+                sc = scores[k]
+                if not (sc >= min_score and (a == 0 or sc > 0)):
+                    continue
+                out[p].append((sc, lists[k], ident[k], tl[k], ql[k], int(status[k])))
+                if status[k] != 0:
+                    continue
+                Q, T = planes[k].shape
+                if a == 0:
+                    neg[p] = -(float(sc) + 1.0)
+                forb[p] += [(int(i), int(j)) for i, j in lists[k] if 1 <= i <= Q - 2 and 1 <= j <= T - 2]
+                nxt.append(p)
+        alive = nxt
+    return out
+
+
+def hits_align_multi_profiles_detour(ctx, profiles, templates, pairs_qt, gi, ge, max_alignments, min_score=-np.inf, consensus=None,
+                                     group=512):
+    """What hits_align_multi_profiles replaces (host glue only; the comparator of the tests and of
+    tools/bench_align_multi_profiles.py): hits_align_multi_detour with every round's plane — round 0's included — expanded from
+    the profile by profile_planes and masked on the host; the query letters of the batches are `consensus` (one string per
+    profile of the pool, no sentinels) or the placeholder alphabet[0].
+    -> per pair the list of its reported rounds, each (score, pair list, identity, tline, qline, status)."""
+    alphabet = profiles.alphabet
+    letters = consensus if consensus is not None else [alphabet[0] * len(p) for p in profiles.profiles]
+    letters = letters if isinstance(letters, SeqPool) else SeqPool(letters)
+    templates = templates if isinstance(templates, SeqPool) else SeqPool(templates)
+    ts = templates.seqs
+    out = [[] for _ in pairs_qt]
+    forb = [[] for _ in pairs_qt]
+    neg = [0.0] * len(pairs_qt)
+    alive = list(range(len(pairs_qt)))
+    for a in range(int(max_alignments)):
+        if not alive:
+            break
+        nxt = []
+        for g0 in range(0, len(alive), group):
+            part = alive[g0:g0 + group]
+            planes = []
+            for p in part:
+                S = profile_planes(profiles.profiles[pairs_qt[p][0]], ts[pairs_qt[p][1]][1:-1], alphabet)
+                for i, j in forb[p]:
+                    S[i, j] = neg[p]
+                planes.append(S)
+            b = Batch(ctx, letters, templates, [pairs_qt[p][0] for p in part], [pairs_qt[p][1] for p in part])
             try:
                 b.dp_simmatrix(planes, LOCAL, gi, ge)
                 scores, lists, status = b.optimal()

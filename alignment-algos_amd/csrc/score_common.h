@@ -38,6 +38,7 @@ struct ScoreArgs {
 //                 its wave ends, and such a query has no letters of its own (the identity is counted over characters)
 //   letters()     of a pool's codes and its characters, the one an alignment's identity is counted over (search_align.hip)
 //   kFusedLocal / kFusedGlobal   bit R set: class R runs in align_local_hit_kernel<R> / align_global_hit_kernel<R> (search_align.hip)
+//   kFusedMulti   bit R set: class R runs in align_local_multi_kernel<R> (search_align_multi.hip)
 // The row arrays never leave the kernel and the sweeps' text does not change with the side.
 struct ResidueQuery {
   typedef TableRows Rows;
@@ -46,6 +47,7 @@ struct ResidueQuery {
   // spilled into AGPRs; as the kernel stands today it would compile to 237 VGPRs and none (4.8j has the
   // figures).  The mask is a route, and changing a route is a change of behaviour of its own.
   static constexpr unsigned kFusedLocal = 0x0FEu, kFusedGlobal = 0x1FEu;
+  static constexpr unsigned kFusedMulti = 0x0FEu;                                       // R = 8 spills 12 VGPRs
   static __device__ __forceinline__ void stage(int* lds, const ScoreArgs& a) {          // the 32 x 32 table
     for (int k = threadIdx.x; k < 32 * 32; k += 64) lds[k] = a.table32[k];
     __syncthreads();
@@ -59,6 +61,7 @@ struct ProfileQuery {
   typedef ProfileRows Rows;
   static constexpr bool kStaged = true;
   static constexpr unsigned kFusedLocal = 0x1FEu, kFusedGlobal = 0x1FEu;                // no scratch, no VGPR spill
+  static constexpr unsigned kFusedMulti = 0x0FEu;                                       // R = 8 spills 20 VGPRs
   static __device__ __forceinline__ void stage(int*, const ScoreArgs&) {}
   static __device__ __forceinline__ const int4* rows(const ScoreArgs& a, int qi) {
     return reinterpret_cast<const int4*>(a.qcodes + a.qoff[qi] * 128);

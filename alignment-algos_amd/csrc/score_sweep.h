@@ -229,7 +229,7 @@ __device__ __forceinline__ int sweep_local(const int* tab, const LocalCols<R>& k
   return lmax;
 }
 
-// sweep_local over the table rows with a set of FORBIDDEN cells (search_align_multi.hip): one bit per cell, row i of the pair at
+// sweep_local with a set of FORBIDDEN cells (search_align_multi.hip): one bit per cell, row i of the pair at
 // mask + i * 8 R words, column c in bit c & 31 of word c / 32 — a lane's four columns of group r are nibble (lane & 7) of word
 // 8 r + lane / 8, one 32-byte-per-8-lanes load per group and row.  D is forced to 0 where the bit is set, directly after the
 // cell is formed and before anything reads it: row 1, column 1 with its free insertion from the origin and the edge groups
@@ -237,8 +237,24 @@ __device__ __forceinline__ int sweep_local(const int* tab, const LocalCols<R>& k
 // mask and is sweep_local's recurrence.  A sibling, not a policy of sweep_local: every existing user of that function compiles
 // from unchanged text (DESIGN 4.8h has the metadata comparison).  The mask is written by earlier rounds of the same wave, so it
 // is read through plain loads, never as __restrict__ / invariant data.
-template <int R, bool MASKED, class Obs>
-__device__ __forceinline__ int sweep_local_masked(const int* tab, const LocalCols<R>& k, const uint8_t* qc, int last,
+// Rows: the row source, as in sweep_local — the table's three lines spelled out under `if constexpr`, every other source
+// through first() / row().  A STAGED source (ProfileRows) shares the wave's one VM counter with the mask loads (R per row) and
+// with the observer's strip stores (R per row); gfx950 retires all of them in issue order.  Two things follow (DESIGN 4.8k
+// quotes the waits of the compiled loop):
+//   landed()   waits until at most ONE operation is outstanding, directly after chunk c + 1 is requested.  Whatever else is in
+//              flight, chunk c was requested eight rows (or, in first(), one instruction) before chunk c + 1, so it is never the
+//              newest outstanding operation and has landed when the wait returns.  More traffic only makes the wait stronger.
+//   order      the mask words of row i are requested BEFORE Rows::row(i): on a fill row landed() then covers them too (they are
+//              older than the copy), so the wait the compiler adds for them finds them there.  That wait is NOT counted: with
+//              copies into LDS among the outstanding operations the compiler waits for a plain load with s_waitcnt vmcnt(0) —
+//              once per masked row, before the second inner loop's first cell, behind the row's strip stores (on the table
+//              side the same place reads vmcnt(3), vmcnt(2) for R = 2).  So in the MASKED rounds every row drains its stores,
+//              and a fill row drains the copy it has just requested: chunk c + 1 lands in the row that asks for it, seven rows
+//              before its first use, hidden by the first inner loop only.  Round 0 (MASKED == false) has no such wait and
+//              keeps the copy one chunk ahead.  Requested after the copy, the mask words would change nothing about the
+//              drain and lose landed()'s cover; counting that wait by hand is the follow-up DESIGN 4.8k names.
+template <int R, bool MASKED, class Rows = TableRows, class Obs>
+__device__ __forceinline__ int sweep_local_masked(const int* tab, const LocalCols<R>& k, const typename Rows::Src* qc, int last,
                                                   const uint32_t* mask, int (&d)[R][4], Obs&& obs) {
   const int lane = threadIdx.x;
   const int cb = 4 * lane;
@@ -274,11 +290,15 @@ __device__ __forceinline__ int sweep_local_masked(const int* tab, const LocalCol
     }
   };
   if (last >= 1) {
-    const int qrow = (int)qc[1] * 128;
+    uint32_t mw1[R];                                         // row 1's mask words: requested before the first copies
+#pragma unroll
+    for (int r = 0; r < R; ++r) mw1[r] = MASKED ? mlane[8 * R + 8 * r] : 0u;
+    int qrow;
+    if constexpr (Rows::kInSweep) qrow = (int)qc[1] * 128;
+    else qrow = Rows::first(tab, qc);
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-      uint32_t nib = 0;
-      if (MASKED) nib = mlane[8 * R + 8 * r] >> msh;
+      const uint32_t nib = mw1[r] >> msh;
 #pragma unroll
       for (int x = 0; x < 4; ++x) {
         const int h = max(sweep_tab_at(tab, qrow, k.code4[r][x]), 0);
@@ -288,13 +308,18 @@ __device__ __forceinline__ int sweep_local_masked(const int* tab, const LocalCol
     finish_row();
     obs.row(1, d, lmax);
   }
-  int qcode_next = (last >= 2) ? (int)qc[2] : 0;
+  int qcode_next = 0;
+  if constexpr (Rows::kInSweep) qcode_next = (last >= 2) ? (int)qc[2] : 0;
   for (int i = 2; i <= last; ++i) {
-    const int qrow = qcode_next * 128;
-    if (i + 1 <= last) qcode_next = (int)qc[i + 1];
+    int qrow;
+    if constexpr (Rows::kInSweep) {
+      qrow = qcode_next * 128;
+      if (i + 1 <= last) qcode_next = (int)qc[i + 1];
+    }
     uint32_t mw[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) mw[r] = MASKED ? mlane[(size_t)i * (8 * R) + 8 * r] : 0u;
+    if constexpr (!Rows::kInSweep) qrow = Rows::row(tab, qc, i);   // after the mask words are requested (see above)
     const int roff = gi + ge * (i - 2);
     const int rowB = ge * (i - 1);
     int bk[R][4];

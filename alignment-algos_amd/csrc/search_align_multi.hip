@@ -1,9 +1,11 @@
-// search_align_multi.hip — several non-intersecting local alignments per search hit, on the device: aln_hits_align_multi (gfx950).
+// search_align_multi.hip — several non-intersecting local alignments per search hit, on the device: aln_hits_align_multi and,
+// for the hits of a profile search, aln_hits_align_multi_profiles (gfx950).
 //
 // Round 0 of a hit is Optimal's alignment (what aln_hits_align returns); round a >= 1 is Optimal's alignment of the matrix in
 // which every aligned pair of the rounds before is forbidden: D = 0 there, everything else the reference's recurrence
 // (include/aln_hip.h has the rule).  One wave per hit runs all rounds inside one launch:
-//   align_local_multi_kernel<R>   per round: sweep_local_masked (score_sweep.h) over ALL rows 1 .. Q-2 — the end cell is not
+//   align_local_multi_kernel<R, Side>   (Side: residue queries through the table, or position-specific rows staged into LDS)
+//                                 per round: sweep_local_masked (score_sweep.h) over ALL rows 1 .. Q-2 — the end cell is not
 //                                 known in advance — observed for the strip byte of every cell (search_align.hip defines it) and
 //                                 for find_max's end cell (score_local_end_kernel's rule) in the SAME sweep; the walk back of
 //                                 align_local_hit_kernel through the strip; the list, the identity count, and one bit per
@@ -14,7 +16,8 @@
 // a kernel's row arrays by reference; the walk's state is scalars after the sweep, and sharing it cost no register: 4.8i.)
 //   class_list_kernel, gapped_strings_kernel   unchanged: the lines of every (hit, round) list in one launch.
 // Templates beyond the kept classes, scoring systems ScoreRun sends through full builds and pairs without an interior go
-// through resident batches inside the call, round by round, on ALN_SIM_MATRIX planes expanded and masked on the host.
+// through resident batches inside the call, round by round, on ALN_SIM_MATRIX planes expanded and masked on the host (a
+// profile's planes in every round, round 0 included: there is no table to build from).
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -26,22 +29,41 @@ namespace aln {
 
 constexpr size_t kMultiBudget = (size_t)1 << 30;   // bytes of strips (of masks, of lists, of lines) resident at a time
 
-template <int R>
-__global__ __launch_bounds__(64) void align_local_multi_kernel(ScoreArgs a, MultiArgs g) {
-  __shared__ int tab[32 * 32];
+// One template over the query side (ResidueQuery, ProfileQuery: score_common.h), as the kernels of search_align.hip are.  qch /
+// tch: the character pools of the query letters and of the templates on the device — the staged side has no letters of its own
+// and counts the identity over CHARACTERS (the consensus pool or the placeholder, exactly what gapped_strings_kernel lays out);
+// the residue side counts over codes, never reads the pools and is passed nullptr.
+//
+// The staged side, round after round.  Every round's sweep calls Rows::first() again: chunks 0 and 1 go into slots 0 and 1 of
+// the ring.  The round before left ONE copy requested that nothing reads (the chunk after its last row's) and up to 32 stale
+// rows in the ring.  The stale rows are harmless — a sweep reads row i only after landed() has returned for the chunk that
+// holds it, and that chunk was requested by THIS sweep.  The copy is not: it targets one of the four slots, which the new
+// round's copies target too, and nothing but the counter's order would keep it from landing on top of them.  So the wave
+// drains its VM counter (s_waitcnt vmcnt(0)) directly after every sweep, which is before either way out of the round — the
+// break of a round that is not reported and the walk of one that is (whose fence waits for the strip stores anyway) — and so
+// before the next round's first() and before the wave ends: no copy targets LDS after the wave has gone.  The ring is private
+// to the wave, so the drain needs no barrier of its own; it stands next to the fence + barrier pair that the walk needs.
+// INVARIANT (ScoreRun::upload_profile_rows): a sweep over rows 1 .. Q-2 requests at most rows 0 .. Q + 13 of its profile.
+// The mask words stay what they were: set by atomicOr, made visible by fence + barrier, read through plain loads.
+template <int R, class Side>
+__global__ __launch_bounds__(64) void align_local_multi_kernel(ScoreArgs a, MultiArgs g, const char* __restrict__ qch,
+                                                              const char* __restrict__ tch) {
+  __shared__ __attribute__((aligned(16))) int lds[32 * 32];
   const int lane = threadIdx.x;
-  for (int k = lane; k < 32 * 32; k += 64) tab[k] = a.table32[k];
-  __syncthreads();
+  Side::stage(lds, a);
   const int hit = g.list[blockIdx.x];
   const MultiDesc hd = g.desc[hit];
   const int ti = hd.t, qi = hd.q;
-  const uint8_t* __restrict__ qc = a.qcodes + a.qoff[qi];
+  const typename Side::Rows::Src* __restrict__ qr = Side::rows(a, qi);
   const uint8_t* __restrict__ tc = a.tcodes + a.toff[ti];
+  const auto* __restrict__ qs = Side::letters(a.qcodes, qch) + a.qoff[qi];      // what the identity is counted over
+  const auto* __restrict__ ts = Side::letters(a.tcodes, tch) + a.toff[ti];
   const int Q = (int)(a.qoff[qi + 1] - a.qoff[qi]), T = (int)(a.toff[ti + 1] - a.toff[ti]);   // Q >= 3, T >= 3: the host's routing
   constexpr int kPitch = 256 * R;
   uint8_t* strip = g.strip + hd.strip_off;      // row i (2 .. Q-2) at strip + (i - 2) * kPitch
   uint32_t* mask = g.mask + hd.mask_off;        // row i (0 .. Q-1) at mask + i * 8 R
   const int cap = g.trav_stride;
+  auto drain = [] { if constexpr (Side::kStaged) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };   // the round's last copy
 
   LocalCols<R> cols;
   cols.load(tc, T, a.gi, a.ge);
@@ -52,8 +74,9 @@ __global__ __launch_bounds__(64) void align_local_multi_kernel(ScoreArgs a, Mult
     StripFirstMaxObserver ob;
     ob.strip = strip; ob.pitch = kPitch;
     int lmax;
-    if (round == 0) lmax = sweep_local_masked<R, false>(tab, cols, qc, Q - 2, mask, d, ob);   // nothing is forbidden yet: no mask loads
-    else lmax = sweep_local_masked<R, true>(tab, cols, qc, Q - 2, mask, d, ob);
+    if (round == 0) lmax = sweep_local_masked<R, false, typename Side::Rows>(lds, cols, qr, Q - 2, mask, d, ob);   // nothing is forbidden yet: no mask loads
+    else lmax = sweep_local_masked<R, true, typename Side::Rows>(lds, cols, qr, Q - 2, mask, d, ob);
+    drain();                                                   // before EITHER way out of the round: the break below, the walk
     int m = lmax;
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) m = max(m, __shfl_xor(m, o));
@@ -83,7 +106,7 @@ __global__ __launch_bounds__(64) void align_local_multi_kernel(ScoreArgs a, Mult
       if (more) atomicOr(mask + (size_t)q * (8 * R) + (t >> 5), 1u << (t & 31));
     };
     auto sink = [&](int k, int q, int t) {
-      if (k < cap) { o[2 * k] = q; o[2 * k + 1] = t; same += (qc[q] == tc[t]) ? 1 : 0; }
+      if (k < cap) { o[2 * k] = q; o[2 * k + 1] = t; same += (qs[q] == ts[t]) ? 1 : 0; }
     };
     auto emit1 = [&](int q, int t) { if (lane == 0) sink(n, q, t); ++n; };
     emit1(Q - 1, T - 1);
@@ -108,22 +131,23 @@ __global__ __launch_bounds__(64) void align_local_multi_kernel(ScoreArgs a, Mult
   if (lane == 0) g.n_found[hit] = found;
 }
 
-// The instantiations kept: every one compiles without scratch memory and without VGPR spills (DESIGN 4.8h has the table).
-constexpr unsigned kMultiClasses = 0x0FEu;                   // bit R set: class R runs in align_local_multi_kernel<R>
-
 // Is round `a` with this score reported?
 static bool reported(int a, float score, float min_score) { return score >= min_score && (a == 0 || score > 0.f); }
 
 // The batch route, round by round over the slots still alive: aln_batch_create + aln_batch_dp + aln_batch_optimal / _strings,
 // in the groups BatchGroup (score_common.h) cuts under the plane budget.  Round 0 is built from the table
 // itself, exactly as aln_hits_align builds it; later rounds from the pairs' Q x T planes, expanded on the host with every
-// forbidden cell at -(round 0's score + 1).
+// forbidden cell at -(round 0's score + 1).  prof != nullptr: `queries` holds the query letters (the consensus pool or the
+// placeholder), `sub` is not read and EVERY round, round 0 included, is built from the planes of its pairs, expanded by the
+// profile plane source (BatchSim, score_common.h) and, after round 0, masked in place.
 static int multi_through_batches(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
-                                 const aln_gap* gap, const std::vector<int32_t>& qi_all, const std::vector<int32_t>& ti_all,
-                                 const std::vector<size_t>& slot_all, int N, float min_score, int32_t* n_found, AlignOut& ao) {
+                                 const aln_qprofiles* prof, const aln_gap* gap, const std::vector<int32_t>& qi_all,
+                                 const std::vector<int32_t>& ti_all, const std::vector<size_t>& slot_all, int N, float min_score,
+                                 int32_t* n_found, AlignOut& ao) {
   int idx[256];
   for (int i = 0; i < 256; ++i) idx[i] = -1;
-  for (int i = 0; i < sub->n; ++i) idx[(unsigned char)sub->alphabet[i]] = i;
+  if (!prof)                                                   // side: the table's letter index (profiles: BatchSim has its own)
+    for (int i = 0; i < sub->n; ++i) idx[(unsigned char)sub->alphabet[i]] = i;
   const size_t np_all = qi_all.size();
   std::vector<std::vector<int32_t>> forbidden(np_all);       // per pair: (i, j) of every aligned pair so far
   std::vector<float> neg(np_all, 0.f);
@@ -138,7 +162,7 @@ static int multi_through_batches(aln_ctx* ctx, const aln_seqs* queries, const al
     aq.resize(alive.size()); at.resize(alive.size());          // the round's pair list: the slots still alive
     for (size_t k = 0; k < alive.size(); ++k) { aq[k] = qi_all[alive[k]]; at[k] = ti_all[alive[k]]; }
     BatchGroup grp;
-    while (grp.next(queries, templates, aq.data(), at.data(), alive.size(), a > 0)) {
+    while (grp.next(queries, templates, aq.data(), at.data(), alive.size(), a > 0 || prof != nullptr)) {
       const size_t g0 = grp.g0;
       const int32_t np = (int32_t)(grp.g1 - g0), stride = (int32_t)std::max<int64_t>(std::min(grp.max_q, grp.max_t) + 3, 4);
       const int32_t ls = (int32_t)(grp.max_sum + 2);
@@ -146,7 +170,16 @@ static int multi_through_batches(aln_ctx* ctx, const aln_seqs* queries, const al
       n.assign((size_t)np, 0); st.assign((size_t)np, 0); pairs.assign((size_t)np * stride * 2, 0);
       sc.assign((size_t)np, 0.f); ident.assign((size_t)np, 0.f); len.assign((size_t)np, 0);
       aln_sim sim = aln_sim();
-      if (a == 0) { sim.kind = ALN_SIM_SUBMATRIX; sim.sub = *sub; }
+      BatchSim bs;
+      auto forbid_in = [&](float* S, int64_t T, size_t p) {
+        for (size_t e = 0; e < forbidden[p].size(); e += 2) S[(int64_t)forbidden[p][e] * T + forbidden[p][e + 1]] = neg[p];
+      };
+      if (prof) {                                              // side: the planes of the group's pairs, every round
+        bs.set(nullptr, prof, templates, (size_t)np, gq, gt);
+        for (int32_t k = 0; k < np && a > 0; ++k)
+          forbid_in(bs.planes.data() + bs.plane_off[k], templates->offsets[gt[k] + 1] - templates->offsets[gt[k]], alive[g0 + k]);
+        sim = bs.sim;
+      } else if (a == 0) { sim.kind = ALN_SIM_SUBMATRIX; sim.sub = *sub; }
       else {
         plane_off.assign((size_t)np + 1, 0);
         for (int32_t k = 0; k < np; ++k) {
@@ -162,8 +195,7 @@ static int multi_through_batches(aln_ctx* ctx, const aln_seqs* queries, const al
             const float* row = sub->table + (size_t)idx[(unsigned char)queries->residues[q0 + i]] * sub->n;   // letters: checked by prepare()
             for (int64_t j = 1; j <= T - 2; ++j) S[i * T + j] = row[idx[(unsigned char)templates->residues[t0 + j]]];
           }
-          const size_t p = alive[g0 + k];
-          for (size_t e = 0; e < forbidden[p].size(); e += 2) S[(int64_t)forbidden[p][e] * T + forbidden[p][e + 1]] = neg[p];
+          forbid_in(S, T, alive[g0 + k]);
         }
         sim.kind = ALN_SIM_MATRIX; sim.planes = planes.data(); sim.plane_off = plane_off.data();
       }
@@ -201,17 +233,22 @@ static int multi_through_batches(aln_ctx* ctx, const aln_seqs* queries, const al
   return ALN_OK;
 }
 
-static int multi_block(ScoreRun& run, int32_t K, const aln_hit* hits, const int32_t* n_hits, int N, float min_score,
-                       int32_t* n_found, aln_hit_alignment* out, int32_t* pairs, int32_t pair_stride, char* tlines, char* qlines,
-                       int32_t line_stride, int32_t* lengths) {
+// The shared body of aln_hits_align_multi and aln_hits_align_multi_profiles (run: prepared; `queries`: the pool the query
+// letters and lengths are read from — run.queries, or the consensus pool of a profile run).  Lines that differ with the query
+// side are marked "side:".
+static int multi_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const aln_hit* hits, const int32_t* n_hits, int N,
+                       float min_score, int32_t* n_found, aln_hit_alignment* out, int32_t* pairs, int32_t pair_stride, char* tlines,
+                       char* qlines, int32_t line_stride, int32_t* lengths) {
   aln_ctx* ctx = run.ctx;
-  const aln_seqs* queries = run.queries;
   const aln_seqs* templates = run.templates;
+  const aln_qprofiles* prof = run.prof;
   const int32_t q_begin = run.q_begin;
   const bool want_lines = tlines || qlines;
   const int rows = run.rows, n_t = run.n_t;
   if (rows == 0) return ALN_OK;
   const bool fused_ok = run.route == ScoreRun::kFast;
+  // side: the instantiations kept — every one compiles without scratch memory and without VGPR spills
+  const unsigned fused_classes = prof ? ProfileQuery::kFusedMulti : ResidueQuery::kFusedMulti;
   auto q_len = [&](int q) { return (int64_t)(queries->offsets[q + 1] - queries->offsets[q]); };
   auto t_len = [&](int t) { return (int64_t)(templates->offsets[t + 1] - templates->offsets[t]); };
 
@@ -230,7 +267,7 @@ static int multi_block(ScoreRun& run, int32_t K, const aln_hit* hits, const int3
       if (h.t < 0 || h.t >= n_t) return ALN_E_ARG;
       const int64_t T = t_len(h.t);
       const int cls = (int)((T + 255) / 256);
-      if (fused_ok && Q >= 3 && T >= 3 && T <= 2048 && ((kMultiClasses >> cls) & 1u)) {
+      if (fused_ok && Q >= 3 && T >= 3 && T <= 2048 && ((fused_classes >> cls) & 1u)) {
         MultiDesc d = {q, h.t, cls, 0, 0, 0};
         fast.push_back(d); fast_slot.push_back(slot);
       } else { bq.push_back(q); bt.push_back(h.t); bslot.push_back(slot); }
@@ -293,6 +330,11 @@ static int multi_block(ScoreRun& run, int32_t K, const aln_hit* hits, const int3
     };
 #define STRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(e_); hipStreamSynchronize(ctx->stream); cleanup(); return ALN_E_HIP; } } while (0)
 #define RTRY(expr) do { int r_ = (expr); if (r_ != ALN_OK) { hipStreamSynchronize(ctx->stream); cleanup(); return r_; } } while (0)
+    // side: the device rows of [q_begin, q_end) are uploaded once when they fit the budget, else (or under the hint) every chunk
+    // uploads the rows of its own profiles — hits are row-major, so a chunk's rows are one contiguous range (aln_hits_align_profiles' rule)
+    if (prof)
+      run.rows_per_slab = ctx->hints.align_rows_per_chunk != 0 ||
+                          ((size_t)(prof->offsets[run.q_end] - prof->offsets[q_begin]) + kProfilePadRows) * 128 > kMultiBudget;
     RTRY(run.upload());
     STRY(hipMalloc((void**)&dstrip, max_strip));
     STRY(hipMalloc((void**)&dmask, max_mask * 4));
@@ -308,12 +350,14 @@ static int multi_block(ScoreRun& run, int32_t K, const aln_hit* hits, const int3
     std::vector<PairDesc> hpd;
     std::vector<StrOut> hso;
     std::vector<char> hlines;
-    if (want_lines) {
+    if (want_lines || prof) {              // side: the profile kernel counts the identity over the characters
       const size_t nq = (size_t)queries->offsets[queries->n_seqs], nt = (size_t)templates->offsets[n_t];
       STRY(hipMalloc((void**)&dqch, std::max<size_t>(nq, 1)));
       STRY(hipMalloc((void**)&dtch, std::max<size_t>(nt, 1)));
       STRY(hipMemcpyAsync(dqch, queries->residues, nq, hipMemcpyHostToDevice, ctx->stream));
       STRY(hipMemcpyAsync(dtch, templates->residues, nt, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (want_lines) {
       STRY(hipMalloc((void**)&dpd, max_e * sizeof(PairDesc)));
       STRY(hipMalloc((void**)&dso, max_e * sizeof(StrOut)));
       STRY(hipMalloc((void**)&dlines, max_e * 2 * (size_t)line_stride));
@@ -324,6 +368,7 @@ static int multi_block(ScoreRun& run, int32_t K, const aln_hit* hits, const int3
       const size_t ne = (size_t)n * N;
       ClassOff co = {};
       for (int k = 1; k < 9; ++k) co.off[k] = co.off[k - 1] + c.cls_cnt[k - 1];
+      if (prof && run.rows_per_slab) RTRY(run.upload_profile_rows(fast[c.h0].q, fast[c.h0 + c.n - 1].q + 1));   // side:
       STRY(hipMemcpyAsync(ddesc, fast.data() + c.h0, (size_t)n * sizeof(MultiDesc), hipMemcpyHostToDevice, ctx->stream));
       STRY(hipMemsetAsync(dfill, 0, 9 * 4, ctx->stream));
       STRY(hipMemsetAsync(dmask, 0, c.mask * 4, ctx->stream));
@@ -338,9 +383,17 @@ static int multi_block(ScoreRun& run, int32_t K, const aln_hit* hits, const int3
       for (int k = 1; k <= 8; ++k) {
         if (c.cls_cnt[k] == 0) continue;
         g.list = dlist + co.off[k];
-        dispatch_r<7>(k, [&](auto rc) {                         // (class 8 never gets here: kMultiClasses)
-          hipLaunchKernelGGL(align_local_multi_kernel<decltype(rc)::value>, dim3(c.cls_cnt[k]), dim3(64), 0, ctx->stream, run.a, g);
-        });
+        auto launch = [&](auto side) {                          // side: the instantiation, and the character pools it reads
+          typedef decltype(side) Side;
+          const char *qch = Side::kStaged ? dqch : nullptr, *tch = Side::kStaged ? dtch : nullptr;
+          constexpr int kMax = ((Side::kFusedMulti >> 8) & 1u) ? 8 : 7;   // a class the mask leaves out never gets here
+          dispatch_r<kMax>(k, [&](auto rc) {
+            hipLaunchKernelGGL((align_local_multi_kernel<decltype(rc)::value, Side>), dim3(c.cls_cnt[k]), dim3(64), 0, ctx->stream,
+                               run.a, g, qch, tch);
+          });
+        };
+        if (prof) launch(ProfileQuery());
+        else launch(ResidueQuery());
         STRY(hipGetLastError());
       }
       if (want_lines) {
@@ -374,7 +427,7 @@ static int multi_block(ScoreRun& run, int32_t K, const aln_hit* hits, const int3
     cleanup();
   }
   if (!bq.empty()) {
-    const int rc = multi_through_batches(ctx, queries, templates, run.sub, run.gap, bq, bt, bslot, N, min_score, n_found, ao);
+    const int rc = multi_through_batches(ctx, queries, templates, run.sub, prof, run.gap, bq, bt, bslot, N, min_score, n_found, ao);
     if (rc != ALN_OK) return rc;
   }
   return ao.worst;
@@ -396,6 +449,26 @@ extern "C" int aln_hits_align_multi(aln_ctx* ctx, const aln_seqs* queries, const
   int rc = run.prepare(ctx, queries, templates, sub, gap, q_begin, q_end);
   if (rc != ALN_OK) return rc;
   if (!run.local) return ALN_E_ARG;
-  return multi_block(run, K, hits, n_hits, max_alignments, min_score, n_found, out, pairs, pair_stride, tlines, qlines, line_stride,
-                     lengths);
+  return multi_block(run, run.queries, K, hits, n_hits, max_alignments, min_score, n_found, out, pairs, pair_stride, tlines, qlines,
+                     line_stride, lengths);
+}
+
+// The same for the hits of a profile search.  The query letters — the lines and the identity need them, the scores never do —
+// are the caller's consensus pool or, without one, the placeholder pool the run builds for profiles.
+extern "C" int aln_hits_align_multi_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_seqs* consensus,
+                                             const aln_seqs* templates, const aln_gap* gap, int32_t q_begin, int32_t q_end,
+                                             int32_t K, const aln_hit* hits, const int32_t* n_hits, int32_t max_alignments,
+                                             float min_score, int32_t* n_found, aln_hit_alignment* out, int32_t* pairs,
+                                             int32_t pair_stride, char* tlines, char* qlines, int32_t line_stride, int32_t* lengths) {
+  if (ctx) ctx->align_routes[0] = ctx->align_routes[1] = 0;
+  if (!n_found || max_alignments < 1 || max_alignments > 16) return ALN_E_ARG;
+  if (!profiles || !templates || !gap) return ALN_E_ARG;
+  if (!align_outputs_ok(K, hits, n_hits, out, pairs, pair_stride, tlines, qlines, line_stride, lengths)) return ALN_E_ARG;
+  ScoreRun run;
+  run.consensus = consensus;
+  int rc = run.prepare(ctx, nullptr, templates, nullptr, gap, q_begin, q_end, profiles);
+  if (rc != ALN_OK) return rc;
+  if (!run.local) return ALN_E_ARG;
+  return multi_block(run, consensus ? consensus : run.queries, K, hits, n_hits, max_alignments, min_score, n_found, out, pairs,
+                     pair_stride, tlines, qlines, line_stride, lengths);
 }

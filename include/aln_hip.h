@@ -224,7 +224,7 @@ int aln_has_gfx950(void);
  *   "align_fused_nonlocal"          aln_hits_align: 1 (default) = hits of the four non-local align types are aligned by the fused
  *                                   kernel where it applies; 0 = they all go through resident batches (environment default
  *                                   ALN_ALIGN_FUSED_NONLOCAL).  Same results.
- *   "align_rows_per_chunk"          aln_hits_align_profiles: 0 (default) = the device rows of the profiles [q_begin, q_end) are
+ *   "align_rows_per_chunk"          aln_hits_align_profiles, aln_hits_align_multi_profiles: 0 (default) = the device rows of the profiles [q_begin, q_end) are
  *                                   uploaded once when they fit 1 GiB, else chunk by chunk; 1 = every chunk of hits uploads the
  *                                   rows of its own profiles (environment default ALN_ALIGN_ROWS_PER_CHUNK).  Same results.
  * Unknown key -> ALN_E_ARG.  No hint changes any result. */
@@ -601,7 +601,36 @@ int aln_hits_align_multi(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* 
                          int32_t max_alignments /* N, 1..16 */, float min_score /* -INFINITY: none */,
                          int32_t* n_found /* rows x K */, aln_hit_alignment* out /* rows x K x N */,
                          int32_t* pairs, int32_t pair_stride, char* tlines, char* qlines, int32_t line_stride, int32_t* lengths);
-/* out[0]: the used slots the last aln_hits_align / aln_hits_align_profiles / aln_hits_align_multi call on this context sent through a fused kernel,
+/* aln_hits_align_multi for the hits of a profile search (aln_search_topk_profiles, or any (row, template) list in its layout).
+ * The round rule and the reporting rule, that only a slot's .t is read, the s * N + a layout of out / pairs / lines / lengths,
+ * n_found, the padding records, ALN_E_OVERFLOW per alignment (a truncated list still forbids all of its cells), the return value
+ * and q_begin == q_end (ALN_OK, nothing written) are those of aln_hits_align_multi, word for word.  ALN_LOCAL only.
+ * The pair's plane is the one aln_score_profiles_vs_all defines; every reported value is what aln_batch_create over (the query
+ * letters of the row, the template) + aln_batch_dp(ALN_SIM_MATRIX with the round's masked plane, gap, ALN_FWD, ALN_DP_AUTO) +
+ * aln_batch_optimal / aln_batch_optimal_strings give, bit for bit.
+ * Query letters: `consensus` exactly as in aln_hits_align_profiles — an ordinary pool with the profiles' n_seqs and offsets,
+ * never scored, not checked against the alphabet; NULL: the placeholder pool ('^', alphabet[0] .., '$').  The identity counts
+ * equal CHARACTERS of the two pools over the list's entries (then - 2).
+ * Routes: integer rows (of the interior rows of the whole pool) and gaps inside aln_score_all_vs_all's 2^23 bound, Q >= 3, T >= 3
+ * and a template of up to 1792 columns — one wave per hit runs all rounds in one launch (csrc/search_align_multi.hip, the kernel
+ * of aln_hits_align_multi instantiated for the profile side): the rows staged from HBM into LDS 8 at a time, per round one
+ * sweep of rows 1 .. Q-2 over the 1-bit-per-cell plane of forbidden cells, the 1 B/cell strip, the walk.  Everything else —
+ * fractional rows or gaps, values beyond the bound, longer templates, pairs without an interior — goes through resident batches
+ * inside the call, round by round, EVERY round (round 0 included) on planes expanded on the host, later rounds masked there
+ * (~12 GB of planes at a time).  The device rows of [q_begin, q_end) are uploaded once when they fit 1 GiB, else with every
+ * chunk of hits (hint "align_rows_per_chunk"); chunks obey "align_chunk_hits" and 1 GiB each of strips, masks, lists and lines.
+ * No hint of its own.  aln_hits_align_last_routes reports this call's slots too.
+ * Checks, in this order, nothing written when one fails: NULL n_found, max_alignments outside 1..16 and
+ * aln_hits_align_profiles' first group (ALN_E_ARG); aln_score_profiles_vs_all's, in its order, with the consensus pool where
+ * aln_hits_align_profiles checks it; an align type other than ALN_LOCAL (ALN_E_ARG); every n_hits[r] in 0..K; every used slot's
+ * t in [0, n_templates) (ALN_E_ARG). */
+int aln_hits_align_multi_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_seqs* consensus /* may be NULL */,
+                                  const aln_seqs* templates, const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K,
+                                  const aln_hit* hits, const int32_t* n_hits,
+                                  int32_t max_alignments /* N, 1..16 */, float min_score /* -INFINITY: none */,
+                                  int32_t* n_found /* rows x K */, aln_hit_alignment* out /* rows x K x N */,
+                                  int32_t* pairs, int32_t pair_stride, char* tlines, char* qlines, int32_t line_stride, int32_t* lengths);
+/* out[0]: the used slots the last aln_hits_align / aln_hits_align_profiles / aln_hits_align_multi / aln_hits_align_multi_profiles call on this context sent through a fused kernel,
  * out[1]: through resident batches; { 0, 0 } before any call and after a call that failed its checks.  NULL argument: ALN_E_ARG. */
 int aln_hits_align_last_routes(const aln_ctx* ctx, int64_t out[2]);
 
