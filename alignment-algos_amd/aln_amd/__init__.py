@@ -96,7 +96,7 @@ EXPORTS = [
     "aln_comm_last_error", "aln_gather_scores", "aln_gather_resident_enqueue", "aln_gather_resident_collect", "aln_search_topk",
     "aln_hits_zscores", "aln_hits_align", "aln_hits_align_last_routes", "aln_score_profiles_vs_all", "aln_search_topk_profiles",
     "aln_hits_align_profiles", "aln_hits_zscores_profiles", "aln_hits_align_multi",
-    "aln_hits_align_multi_profiles",
+    "aln_hits_align_multi_profiles", "aln_hits_column_counts", "aln_hits_column_counts_profiles",
 ]
 COMM_ID_BYTES = 128
 
@@ -186,6 +186,12 @@ def lib():
                                                     C.POINTER(AlnGap), C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.c_int32,
                                                     C.c_float, _ip, C.POINTER(AlnHitAlignment), _ip, C.c_int32, C.c_char_p, C.c_char_p,
                                                     C.c_int32, _ip]
+        L.aln_hits_column_counts.argtypes = [C.c_void_p, C.POINTER(AlnSeqs), C.POINTER(AlnSeqs), C.POINTER(AlnSubmatrix), C.POINTER(AlnGap),
+                                             C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, _ip, C.POINTER(AlnHitAlignment), _ip,
+                                             _ip]
+        L.aln_hits_column_counts_profiles.argtypes = [C.c_void_p, C.POINTER(AlnQProfiles), C.POINTER(AlnSeqs), C.POINTER(AlnSeqs),
+                                                      C.POINTER(AlnGap), C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, _ip,
+                                                      C.POINTER(AlnHitAlignment), _ip, _ip]
         L.aln_hits_align_last_routes.argtypes = [C.c_void_p, _lp]
         L.aln_hmap2_gap_arrays.argtypes = [_fp, C.c_int64, C.c_float, C.c_float, C.c_float, _fp, _fp]
         L.aln_batch_plane_bytes_per_cell.argtypes = [C.c_void_p]
@@ -773,6 +779,93 @@ def hits_align_multi_profiles_detour(ctx, profiles, templates, pairs_qt, gi, ge,
                 nxt.append(p)
         alive = nxt
     return out
+
+
+def _count_outputs(offsets, q_begin, rows, K, n, weights, want_covered):
+    n_rows = int(offsets[q_begin + rows] - offsets[q_begin])
+    rec = np.zeros((rows, K), dtype=HIT_ALIGNMENT_DTYPE)
+    counts = np.zeros((n_rows, n), dtype=np.int32)
+    covered = np.zeros(n_rows, dtype=np.int32) if want_covered else None
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, dtype=np.int32)
+        assert weights.shape == (rows, K)
+    return rec, counts, covered, weights
+
+
+def _count_results(rec, counts, covered, rc, offsets, q_begin, rows, ctx):
+    if rc != 0 and not (rec["status"] == rc).any():
+        _check(rc, ctx.h)
+    cut = [int(offsets[q_begin + r] - offsets[q_begin]) for r in range(rows + 1)]
+    return rec, [counts[cut[r]:cut[r + 1]] for r in range(rows)], covered, rc
+
+
+def hits_column_counts(ctx, queries, templates, hits, n_hits, alphabet, table, gi, ge, weights=None, q_begin=0, align_type=LOCAL,
+                       want_covered=True):
+    """aln_hits_column_counts: per query of the row block, how often each letter of `alphabet` stands under each query position
+    in the alignments hits_align reports for the used slots of hits[rows, K], tallied on the device — no alignment is downloaded.
+    weights: None (every used slot counts 1) or int32 [rows, K] in 0..65535.  -> rec[rows, K] (hits_align's records without
+    lists), counts (per row an int32 (Q, n) array, sentinel rows included and zero; views of one block), covered (int32, one
+    entry per row of the block's queries: the weighted alignments that span the position, aligned or opposite a gap; None when
+    not wanted), rc (0, or the lowest per-slot status).  Raises only when the call wrote nothing."""
+    qpool = queries if isinstance(queries, SeqPool) else SeqPool(queries)
+    tpool = templates if isinstance(templates, SeqPool) else SeqPool(templates)
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    n_hits = np.ascontiguousarray(n_hits, dtype=np.int32)
+    rows, K = hits.shape
+    assert n_hits.shape == (rows,)
+    tab = np.ascontiguousarray(table, dtype=np.float32)
+    ab = alphabet.encode()
+    sub = AlnSubmatrix(len(alphabet), ab, _f(tab))
+    g = _const_gap(align_type, gi, ge)
+    rec, counts, covered, weights = _count_outputs(qpool.offsets, q_begin, rows, K, len(alphabet), weights, want_covered)
+    rc = lib().aln_hits_column_counts(ctx.h, C.byref(qpool.c), C.byref(tpool.c), C.byref(sub), C.byref(g), q_begin, q_begin + rows,
+                                      int(K), hits.ctypes.data_as(C.POINTER(AlnHit)), _i(n_hits),
+                                      _i(weights) if weights is not None else None, rec.ctypes.data_as(C.POINTER(AlnHitAlignment)),
+                                      _i(counts), _i(covered) if want_covered else None)
+    return _count_results(rec, counts, covered, rc, qpool.offsets, q_begin, rows, ctx)
+
+
+def hits_column_counts_profiles(ctx, profiles, templates, hits, n_hits, gi, ge, consensus=None, weights=None, q_begin=0,
+                                align_type=LOCAL, want_covered=True):
+    """aln_hits_column_counts_profiles: hits_column_counts for the hits of a profile search (profiles: a QueryProfiles, whose
+    alphabet the counts' columns follow; consensus as in hits_align_profiles — it only enters the records' identity).
+    -> the 4-tuple of hits_column_counts."""
+    tpool = templates if isinstance(templates, SeqPool) else SeqPool(templates)
+    cpool = None
+    if consensus is not None:
+        cpool = consensus if isinstance(consensus, SeqPool) else SeqPool(consensus)
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    n_hits = np.ascontiguousarray(n_hits, dtype=np.int32)
+    rows, K = hits.shape
+    assert n_hits.shape == (rows,)
+    g = _const_gap(align_type, gi, ge)
+    rec, counts, covered, weights = _count_outputs(profiles.offsets, q_begin, rows, K, len(profiles.alphabet), weights, want_covered)
+    rc = lib().aln_hits_column_counts_profiles(ctx.h, C.byref(profiles.c), C.byref(cpool.c) if cpool is not None else None,
+                                               C.byref(tpool.c), C.byref(g), q_begin, q_begin + rows, int(K),
+                                               hits.ctypes.data_as(C.POINTER(AlnHit)), _i(n_hits),
+                                               _i(weights) if weights is not None else None,
+                                               rec.ctypes.data_as(C.POINTER(AlnHitAlignment)), _i(counts),
+                                               _i(covered) if want_covered else None)
+    return _count_results(rec, counts, covered, rc, profiles.offsets, q_begin, rows, ctx)
+
+
+def pssm_from_counts(counts, background, fallback_rows, pseudo=1.0, scale=2.0):
+    """Column counts -> the rows of a position-specific query (one entry of QueryProfiles), float64 numpy throughout.
+    counts: (L, n) — the INTERIOR rows of one entry of hits_column_counts' list (entry[1:-1]); background: n letter
+    frequencies, each > 0 (they need not sum to 1: only ratios to them enter); fallback_rows: (L, n), what a position nothing
+    was aligned to keeps — the round's own query rows, e.g. profiles_from_sequences(...).profiles[q].
+    With N_i = sum_a counts[i][a], a row with N_i > 0 becomes
+        rint(scale * log2((counts[i][a] + pseudo * bg[a]) / ((N_i + pseudo) * bg[a])))
+    — the log-odds, in 1/scale bits, of the observed frequencies smoothed by `pseudo` background-distributed pseudo-counts
+    (pseudo > 0, so no logarithm of 0) — and a row with N_i == 0 is fallback_rows[i].  -> float32 (L, n) with integer values
+    wherever the fallback's are: a profile made this way stays on the register-resident route."""
+    c = np.asarray(counts, dtype=np.float64)
+    bg = np.asarray(background, dtype=np.float64).reshape(1, -1)
+    fb = np.asarray(fallback_rows, dtype=np.float64)
+    assert c.ndim == 2 and c.shape == fb.shape and bg.shape[1] == c.shape[1] and (bg > 0).all() and pseudo > 0
+    N = c.sum(axis=1, keepdims=True)
+    odds = (c + pseudo * bg) / ((N + pseudo) * bg)
+    return np.where(N > 0, np.rint(scale * np.log2(odds)), fb).astype(np.float32)
 
 
 def hits_align_routes(ctx):

@@ -1,8 +1,8 @@
 // score_common.h — what the all-vs-all score kernels (score_only.hip) and the entries built on them (search_topk.hip,
-// search_zscore.hip, search_align.hip) share beside the row sweep itself (score_sweep.h): the kernels' argument block, the
-// query side a kernel is instantiated for (residues scored through the table, or position-specific rows), how work is listed
-// and launched by template length class, and ScoreRun, the host side of one all-vs-all scoring call cut into steps so that a
-// caller can leave the scores of a slab of query rows in a device buffer of its own.
+// search_zscore.hip, search_align.hip, search_counts.hip) share beside the row sweep itself (score_sweep.h): the kernels'
+// argument block, the query side a kernel is instantiated for (residues scored through the table, or position-specific rows),
+// how work is listed and launched by template length class, and ScoreRun, the host side of one all-vs-all scoring call cut
+// into steps so that a caller can leave the scores of a slab of query rows in a device buffer of its own.
 #pragma once
 #include <algorithm>
 #include <deque>
@@ -38,6 +38,7 @@ struct ScoreArgs {
 //                 its wave ends, and such a query has no letters of its own (the identity is counted over characters)
 //   letters()     of a pool's codes and its characters, the one an alignment's identity is counted over (search_align.hip)
 //   kFusedLocal / kFusedGlobal   bit R set: class R runs in align_local_hit_kernel<R> / align_global_hit_kernel<R> (search_align.hip)
+//                 and in count_local_hit_kernel<R> / count_global_hit_kernel<R> (search_counts.hip)
 //   kFusedMulti   bit R set: class R runs in align_local_multi_kernel<R> (search_align_multi.hip)
 // The row arrays never leave the kernel and the sweeps' text does not change with the side.
 struct ResidueQuery {

@@ -2,7 +2,8 @@
 // table in LDS, and for position-specific queries, rows staged into LDS) and search_align_multi.hip (several rounds per
 // hit) share: how a hit is described to a kernel, where its results go and how a slot's record, list and lines are written for
 // the caller (AlignOut, put_fused, pair_desc), the two observers that turn a row sweep into the strip bytes and the final
-// cell's pointer, and strip_walk, the walk back through the strip that all three kernels call.  The strip byte is defined at
+// cell's pointer, and strip_walk, the walk back through the strip that all three kernels call — and the two of
+// search_counts.hip, which tally the walk's entries instead of listing them.  The strip byte is defined at
 // the head of search_align.hip.  DESIGN 4.8 found that a helper which takes a kernel's ROW ARRAYS by reference costs
 // registers; the walk runs after the sweep on scalar state only (strip, i, j, n), and sharing it costs none.
 #pragma once
@@ -211,6 +212,50 @@ inline PairDesc pair_desc(const aln_seqs* queries, const aln_seqs* templates, in
   pd.q_seq = q; pd.t_seq = t; pd.q_off = queries->offsets[q]; pd.t_off = templates->offsets[t];
   return pd;
 }
+
+// The used slots of a hit list by route: the fused kernels' hits (row-major) and the batch route's pairs, each with its slot
+struct SlotRoutes {
+  std::vector<HitDesc> fast; std::vector<size_t> fast_slot;
+  std::vector<int32_t> bq, bt; std::vector<size_t> bslot;
+};
+
+// One walk over hits[rows x K] of a prepared run (`queries`: the pool lengths are read from): every n_hits[r] in 0..K, every
+// used slot's t in range and, local, its end cell in range, else ALN_E_ARG; each slot described for its route.  The fused
+// route takes integer scoring (ScoreRun::kFast), pairs with an interior, templates of up to 2048 columns and the length
+// classes an instantiation is kept for — every kept one compiles without scratch memory and without VGPR spills (the masks
+// are the side's); hint align_fused_nonlocal = 0 keeps the non-local types out of it.  Writes nothing but `sr`.
+inline int route_slots(const ScoreRun& run, const aln_seqs* queries, int32_t K, const aln_hit* hits, const int32_t* n_hits,
+                       SlotRoutes& sr) {
+  const aln_seqs* templates = run.templates;
+  const bool fused_ok = run.route == ScoreRun::kFast && (run.local || run.ctx->hints.align_fused_nonlocal);
+  const unsigned fused_classes = run.prof ? (run.local ? ProfileQuery::kFusedLocal : ProfileQuery::kFusedGlobal)
+                                          : (run.local ? ResidueQuery::kFusedLocal : ResidueQuery::kFusedGlobal);
+  for (int r = 0; r < run.rows; ++r) {
+    if (n_hits[r] < 0 || n_hits[r] > K) return ALN_E_ARG;
+    const int q = run.q_begin + r;
+    const int64_t Q = queries->offsets[q + 1] - queries->offsets[q];
+    for (int k = 0; k < n_hits[r]; ++k) {
+      const size_t slot = (size_t)r * K + k;
+      const aln_hit& h = hits[slot];
+      if (h.t < 0 || h.t >= run.n_t) return ALN_E_ARG;
+      const int64_t T = templates->offsets[h.t + 1] - templates->offsets[h.t];
+      const bool interior = Q >= 3 && T >= 3;
+      if (run.local && interior && (h.q_end < 1 || h.q_end > Q - 2 || h.t_end < 1 || h.t_end > T - 2)) return ALN_E_ARG;
+      const int cls = (int)((T + 255) / 256);
+      if (fused_ok && interior && T <= 2048 && ((fused_classes >> cls) & 1u)) {
+        HitDesc d = {q, h.t, 0, 0, 0.f, cls, 0};                 // non-local: the slot's end cell and score are ignored
+        if (run.local) { d.q_end = h.q_end; d.t_end = h.t_end; d.score = h.score; }
+        sr.fast.push_back(d); sr.fast_slot.push_back(slot);
+      } else { sr.bq.push_back(q); sr.bt.push_back(h.t); sr.bslot.push_back(slot); }
+    }
+  }
+  return ALN_OK;
+}
+
+// The batch route of hit alignment (search_align.hip): slot_all[k] of pair (qi_all[k], ti_all[k]) is where ao.put() files it
+int align_through_batches(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
+                          const aln_qprofiles* prof, const aln_gap* gap, const std::vector<int32_t>& qi_all,
+                          const std::vector<int32_t>& ti_all, const std::vector<size_t>& slot_all, AlignOut& ao);
 
 // the checks both entries make before ScoreRun's: the hit list, the record array, K, and the two optional output groups
 inline bool align_outputs_ok(int32_t K, const aln_hit* hits, const int32_t* n_hits, const aln_hit_alignment* out, const int32_t* pairs,

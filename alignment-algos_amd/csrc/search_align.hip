@@ -182,10 +182,10 @@ __global__ __launch_bounds__(64) void align_global_hit_kernel(ScoreArgs a, Align
 // The batch route over the listed slots: aln_batch_create + aln_batch_dp + aln_batch_optimal / _strings, in the groups
 // BatchGroup (score_common.h) cuts under the plane budget.  prof != nullptr: `queries` holds the query
 // letters (the consensus pool or the placeholder), `sub` is not read and every batch is built from the planes of its own pairs
-// (BatchSim), which its budget counts.
-static int align_through_batches(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
-                                 const aln_qprofiles* prof, const aln_gap* gap, const std::vector<int32_t>& qi_all,
-                                 const std::vector<int32_t>& ti_all, const std::vector<size_t>& slot_all, AlignOut& ao) {
+// (BatchSim), which its budget counts.  (Declared in search_align.h: search_counts.hip tallies the lists of this route.)
+int align_through_batches(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
+                          const aln_qprofiles* prof, const aln_gap* gap, const std::vector<int32_t>& qi_all,
+                          const std::vector<int32_t>& ti_all, const std::vector<size_t>& slot_all, AlignOut& ao) {
   std::vector<int32_t> n, st, pairs, len;
   std::vector<float> sc, ident;
   std::vector<char> tl, ql;
@@ -230,10 +230,6 @@ static int align_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
   int rc;
   const int rows = run.rows, n_t = run.n_t;
   if (rows == 0) return ALN_OK;
-  const bool fused_ok = run.route == ScoreRun::kFast && (run.local || ctx->hints.align_fused_nonlocal);
-  // the instantiations kept: every one compiles without scratch memory and without VGPR spills (the masks are the side's)
-  const unsigned fused_classes = prof ? (run.local ? ProfileQuery::kFusedLocal : ProfileQuery::kFusedGlobal)
-                                      : (run.local ? ResidueQuery::kFusedLocal : ResidueQuery::kFusedGlobal);
   // a fused hit's strip rows and the most entries its list can have
   auto strip_rows = [&](const HitDesc& d) {
     return run.local ? d.q_end - 1 : (int)(queries->offsets[d.q + 1] - queries->offsets[d.q]) - 3;
@@ -243,30 +239,13 @@ static int align_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
     return (int)std::min(queries->offsets[d.q + 1] - queries->offsets[d.q], templates->offsets[d.t + 1] - templates->offsets[d.t]) + 1;
   };
 
-  // one walk: validate every used slot, describe it for its route, count the classes (nothing is written before it ends)
-  std::vector<HitDesc> fast;            // the fused kernel's hits, row-major
-  std::vector<size_t> fast_slot;
-  std::vector<int32_t> bq, bt;          // the batch route's
-  std::vector<size_t> bslot;
-  for (int r = 0; r < rows; ++r) {
-    if (n_hits[r] < 0 || n_hits[r] > K) return ALN_E_ARG;
-    const int q = q_begin + r;
-    const int64_t Q = queries->offsets[q + 1] - queries->offsets[q];
-    for (int k = 0; k < n_hits[r]; ++k) {
-      const size_t slot = (size_t)r * K + k;
-      const aln_hit& h = hits[slot];
-      if (h.t < 0 || h.t >= n_t) return ALN_E_ARG;
-      const int64_t T = templates->offsets[h.t + 1] - templates->offsets[h.t];
-      const bool interior = Q >= 3 && T >= 3;
-      if (run.local && interior && (h.q_end < 1 || h.q_end > Q - 2 || h.t_end < 1 || h.t_end > T - 2)) return ALN_E_ARG;
-      const int cls = (int)((T + 255) / 256);
-      if (fused_ok && interior && T <= 2048 && ((fused_classes >> cls) & 1u)) {
-        HitDesc d = {q, h.t, 0, 0, 0.f, cls, 0};                 // non-local: the slot's end cell and score are ignored
-        if (run.local) { d.q_end = h.q_end; d.t_end = h.t_end; d.score = h.score; }
-        fast.push_back(d); fast_slot.push_back(slot);
-      } else { bq.push_back(q); bt.push_back(h.t); bslot.push_back(slot); }
-    }
-  }
+  // one walk: every used slot validated and described for its route (nothing is written before it ends)
+  SlotRoutes sr;
+  if ((rc = route_slots(run, queries, K, hits, n_hits, sr)) != ALN_OK) return rc;
+  std::vector<HitDesc>& fast = sr.fast;
+  const std::vector<size_t>& fast_slot = sr.fast_slot;
+  const std::vector<int32_t>&bq = sr.bq, &bt = sr.bt;
+  const std::vector<size_t>& bslot = sr.bslot;
   ctx->align_routes[0] = (int64_t)fast.size(); ctx->align_routes[1] = (int64_t)bq.size();
   AlignOut ao = {out, pairs, pair_stride, tlines, qlines, line_stride, lengths};
   for (int r = 0; r < rows; ++r)

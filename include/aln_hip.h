@@ -398,7 +398,10 @@ int aln_search_topk(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templ
 /* A pool of query profiles.  The reference builds a DPMatrix from any SimilarityMatrix, and a user Evaluator may return a
  * similarity that depends on the query POSITION, not on the query letter (evaluator.h:20-97): one score per template letter
  * for every query position — the second-round query of an iterative search, the query form of family databases.  Such a query
- * has no residue string to send through a substitution table. */
+ * has no residue string to send through a substitution table.  Where such rows come from is the caller's business; the step
+ * from a search round to the next one's rows is on the device too: aln_hits_column_counts (below, after
+ * aln_hits_align_profiles) tallies the aligned template letters of a round's hits per query position, and
+ * aln_amd.pssm_from_counts turns such counts into integer log-odds rows. */
 typedef struct {
   int32_t n_seqs;
   const int64_t* offsets;       /* n_seqs + 1, in ROWS: profile s owns rows offsets[s] .. offsets[s+1); its first and last row stand
@@ -560,6 +563,49 @@ int aln_hits_align_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, const a
                             const aln_hit* hits, const int32_t* n_hits, aln_hit_alignment* out,
                             int32_t* pairs, int32_t pair_stride,
                             char* tlines, char* qlines, int32_t line_stride, int32_t* lengths);
+/* ---- column counts of search hits: from one search round to the profile of the next, tallied on the device ----------- */
+/* For every query of the row block, how often each template letter stands under each query position in the alignments of the
+ * query's hits — what a position-specific query of the next round is made from — without an alignment leaving the device.
+ * The hit layout and which slots are used are aln_hits_align's (duplicates allowed).  The alignment of a slot is the pair list
+ * aln_hits_align reports for it: ALN_LOCAL trusts the slot's end cell (a sweep score that differs from .score gives the slot
+ * ALN_E_ARG, n_pairs 0, and the call goes on), the four other align types start at (Q-1, T-1).  out[s] is, byte for byte, the
+ * record aln_hits_align writes for the slot when called with pairs == NULL and no line group; unused slots hold { 0, 0, 0, 0 };
+ * ALN_E_OVERFLOW cannot occur.
+ * A slot contributes with weight w = weights[s] (weights == NULL: 1) when its status is 0, w > 0 and, ALN_LOCAL, its score is
+ * > 0 (a score-0 local list is the seed cell's, not an alignment).  With off = offsets[q_begin], row(i) = offsets[query] - off +
+ * i and n the alphabet's size, a contributing slot adds w to counts[row(i) * n + index(t[j])] for every list entry (i, j) with
+ * 1 <= i <= Q-2 and 1 <= j <= T-2 (index: the letter's position in the call's alphabet), and, with i_lo / i_hi the smallest /
+ * largest such i (when there is one), w to covered[row(i)] for every i_lo <= i <= i_hi: covered[r] - sum_a counts[r][a] is the
+ * weighted number of alignments that pass query position r opposite a gap.  counts (and covered, which may be NULL) are
+ * written in full by every successful call — zeros where nothing contributed, the sentinel rows included — and depend on
+ * neither the chunking (hints "align_chunk_hits", "align_rows_per_chunk"), the launch order nor the route: every add is an
+ * integer add.
+ * Routes: those of aln_hits_align — one wave per hit sweeps as there, writes the 1 B/cell strip, walks back through it and
+ * issues one integer atomic add per list entry into 32-wide int32 rows on the device (csrc/search_counts.hip), which are
+ * zeroed once per call and downloaded once at its end; no list, no line and no per-hit download but the 16-byte record.
+ * What those kernels do not take (longer templates, fractional scoring, pairs without an interior, ALN_LOCAL templates of
+ * 1793 .. 2048 columns) goes through resident batches whose pair lists the host tallies into the same outputs.
+ * aln_hits_align_last_routes reports this call's slots too.
+ * Checks, in this order, nothing written when one fails: NULL hits / n_hits / out / counts, K outside 1..1024 (ALN_E_ARG);
+ * aln_score_all_vs_all's, in its order; every n_hits[r] in 0..K, every used slot's t in [0, n_templates) and, local, its end
+ * cell in range (ALN_E_ARG); every used slot's weight in 0..65535 (ALN_E_ARG: with K <= 1024 no count can leave int32).
+ * q_begin == q_end: ALN_OK, nothing written.  Returns the lowest per-slot status, ALN_OK when all are 0. */
+int aln_hits_column_counts(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
+                           const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K,
+                           const aln_hit* hits, const int32_t* n_hits,
+                           const int32_t* weights /* rows x K, or NULL = every used slot 1 */,
+                           aln_hit_alignment* out /* rows x K */,
+                           int32_t* counts /* (offsets[q_end] - offsets[q_begin]) x sub->n */,
+                           int32_t* covered /* offsets[q_end] - offsets[q_begin], may be NULL */);
+/* The same for the hits of a profile search: the slots, records, routes and consensus pool are aln_hits_align_profiles', the
+ * weights, counts (x profiles->n, in the order of profiles->alphabet) and covered are those above, and the checks are NULL
+ * profiles / templates / gap / hits / n_hits / out / counts and K; aln_score_profiles_vs_all's, in its order, with the
+ * consensus pool where aln_hits_align_profiles checks it; n_hits, t and the end cells; the weights.  For profiles derived from
+ * residue queries under an integral table the outputs are byte-identical to aln_hits_column_counts' on those residues. */
+int aln_hits_column_counts_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_seqs* consensus /* may be NULL */,
+                                    const aln_seqs* templates, const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K,
+                                    const aln_hit* hits, const int32_t* n_hits, const int32_t* weights,
+                                    aln_hit_alignment* out, int32_t* counts /* ... x profiles->n */, int32_t* covered);
 /* Several NON-INTERSECTING local alignments per hit (the second, third .. HSP of a hit; Waterman-Eggert's declumping restated on
  * the reference's recurrence).  ALN_LOCAL only.  For one pair — query of Q residues, template of T, sentinels counted — under a
  * table and constant affine gaps:
@@ -630,7 +676,7 @@ int aln_hits_align_multi_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, c
                                   int32_t max_alignments /* N, 1..16 */, float min_score /* -INFINITY: none */,
                                   int32_t* n_found /* rows x K */, aln_hit_alignment* out /* rows x K x N */,
                                   int32_t* pairs, int32_t pair_stride, char* tlines, char* qlines, int32_t line_stride, int32_t* lengths);
-/* out[0]: the used slots the last aln_hits_align / aln_hits_align_profiles / aln_hits_align_multi / aln_hits_align_multi_profiles call on this context sent through a fused kernel,
+/* out[0]: the used slots the last aln_hits_align / aln_hits_align_profiles / aln_hits_align_multi / aln_hits_align_multi_profiles / aln_hits_column_counts(_profiles) call on this context sent through a fused kernel,
  * out[1]: through resident batches; { 0, 0 } before any call and after a call that failed its checks.  NULL argument: ALN_E_ARG. */
 int aln_hits_align_last_routes(const aln_ctx* ctx, int64_t out[2]);
 
