@@ -50,7 +50,7 @@ __device__ __forceinline__ int sweep_tab_at(const int* tab, int qrow, int c4) {
 // code of row i + 1 is fetched while row i is computed.  kInSweep: its three lines stay spelled out in the sweeps, under
 // `if constexpr`, and this struct only names them.  Routed through first() / row() like any other source the same loads reach
 // the optimiser in another shape (the address of qc[i + 1] is formed differently) and nine instantiations of
-// score_global_kernel, score_shuffled_kernel and align_global_hit_kernel change their SGPR spills.
+// score_global_kernel, score_shuffled_kernel and hit_global_kernel change their SGPR spills.
 struct TableRows {
   typedef uint8_t Src;
   static constexpr bool kInSweep = true;

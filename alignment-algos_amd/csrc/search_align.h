@@ -1,14 +1,17 @@
-// search_align.h — what the fused hit-alignment kernels of search_align.hip (one pair of kernels for residue queries, the
-// table in LDS, and for position-specific queries, rows staged into LDS) and search_align_multi.hip (several rounds per
-// hit) share: how a hit is described to a kernel, where its results go and how a slot's record, list and lines are written for
-// the caller (AlignOut, put_fused, pair_desc), the two observers that turn a row sweep into the strip bytes and the final
-// cell's pointer, and strip_walk, the walk back through the strip that all three kernels call — and the two of
-// search_counts.hip, which tally the walk's entries instead of listing them.  The strip byte is defined at
+// search_align.h — what the fused hit-alignment entries share.  Device: how a hit is described to a kernel (HitDesc), the two
+// observers that turn a row sweep into the strip bytes and the final cell's pointer, strip_walk, the walk back through the
+// strip, and the ONE pair of kernels around them, hit_local_kernel / hit_global_kernel<R, Side, Job>: what becomes of a walk
+// entry is the job's — ListJob here (search_align.hip: the pair list), CountJob in search_counts.hip (the column counts).
+// search_align_multi.hip (several rounds per hit) has a kernel of its own around the same walk.  Host: where a slot's record,
+// list and lines go (AlignOut, put_fused, pair_desc), the routing of slots (route_slots) and the fused route's driver that
+// the three entries run their chunks through (DeviceBufs, FusedRoute).  The strip byte is defined at
 // the head of search_align.hip.  DESIGN 4.8 found that a helper which takes a kernel's ROW ARRAYS by reference costs
-// registers; the walk runs after the sweep on scalar state only (strip, i, j, n), and sharing it costs none.
+// registers; the walk and the jobs run after the sweep on scalar state only, and sharing them costs none.
 #pragma once
 #include <algorithm>
 #include <cstring>
+#include <string>
+#include <vector>
 
 #include "score_common.h"
 
@@ -23,8 +26,9 @@ struct HitDesc {            // one used slot a fused kernel takes, 32 bytes
 };
 
 // hit of the chunk -> its length class (class_list_kernel, score_common.h)
+template <class Desc>
 struct DescClass {
-  const HitDesc* desc;
+  const Desc* desc;
   __device__ int operator()(int h) const { return desc[h].cls; }
 };
 
@@ -159,6 +163,157 @@ __device__ __forceinline__ bool strip_walk(const uint8_t* strip, int i, int j, i
   return false;
 }
 
+// The job that lists: entry k < cap of the walk into the hit's list, `same` counted over the entries kept.  A job has Args
+// (which begin with list, desc, strip and have res, same) and Sink<Letters>: built AFTER the sweep and its fences from the
+// argument block and scalars — nothing of a job is live across the sweep, and the kernels' row arrays never reach it —, called
+// per entry by exactly one lane, finish() by every lane after the walk, status(n) for the record, `same` for the identity.
+struct ListJob {
+  typedef AlignArgs Args;
+  template <class Letters>
+  struct Sink {
+    Letters qs, ts;                             // what the identity is counted over
+    int32_t* o; int cap;
+    int same = 0;
+    __device__ __forceinline__ Sink(const Args& g, const ScoreArgs&, int hit, int, Letters qs_, Letters ts_, const uint8_t*, int, int)
+        : qs(qs_), ts(ts_), o(g.trav + (size_t)hit * g.trav_stride * 2), cap(g.trav_stride) {}
+    __device__ __forceinline__ void operator()(int k, int q, int t) {
+      if (k < cap) {
+        o[2 * k] = q; o[2 * k + 1] = t;
+        same += (qs[q] == ts[t]) ? 1 : 0;
+      }
+    }
+    __device__ __forceinline__ void finish() {
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) same += __shfl_xor(same, off);
+    }
+    __device__ __forceinline__ int status(int n) const { return n <= cap ? 0 : ALN_E_OVERFLOW; }
+  };
+};
+
+// The two kernels, one wave per hit, templates over the length class, the query side (ResidueQuery, ProfileQuery:
+// score_common.h) and the job.  qch / tch: the character pools of the query letters (which share the queries' offsets) and of
+// the templates on the device.  A profile has no letters, so its identity is counted over CHARACTERS — the caller's consensus
+// pool, or the placeholder pool of ScoreRun, against the templates', exactly the comparison gapped_strings_kernel makes for
+// the lines; the residue side counts over codes, never reads the pools and is passed nullptr.
+//
+// The VM counter, staged side.  The row loop holds the strip stores (R per row) beside the staging copy, and gfx950 retires
+// loads, LDS copies and stores through ONE counter in issue order.  ProfileRows::landed() waits until at most one operation is
+// outstanding; it is called right after chunk c + 1 is requested, so chunk c has landed (it is older than everything waited
+// for) — and so has every strip store issued so far: once per 8 rows the stores are drained.  That is correct and is what ships:
+// a counted wait that leaves the stores in flight was built and measured, and did not separate from this one.
+// INVARIANT (ScoreRun::upload_profile_rows): a sweep requests at most rows 0 .. Q + 13 of its profile and the buffer is padded
+// for that; the local kernel stops at q_end <= Q - 2.  The last copy requested is never read: it is drained before the walk (and
+// before the kernel returns early) so that nothing is in flight into LDS when the wave ends.
+template <int R, class Side, class Job>
+__global__ __launch_bounds__(64) void hit_local_kernel(ScoreArgs a, typename Job::Args g, const char* __restrict__ qch,
+                                                      const char* __restrict__ tch) {
+  __shared__ __attribute__((aligned(16))) int lds[32 * 32];
+  const int lane = threadIdx.x;
+  Side::stage(lds, a);
+  const int hit = g.list[blockIdx.x];
+  const HitDesc hd = g.desc[hit];
+  const int ti = hd.t, qi = hd.q, q_end = hd.q_end, t_end = hd.t_end;
+  const typename Side::Rows::Src* __restrict__ qr = Side::rows(a, qi);
+  const uint8_t* __restrict__ tc = a.tcodes + a.toff[ti];
+  const auto* __restrict__ qs = Side::letters(a.qcodes, qch) + a.qoff[qi];      // what the identity is counted over
+  const auto* __restrict__ ts = Side::letters(a.tcodes, tch) + a.toff[ti];
+  const int Q = (int)(a.qoff[qi + 1] - a.qoff[qi]), T = (int)(a.toff[ti + 1] - a.toff[ti]);
+  constexpr int kPitch = 256 * R;
+  uint8_t* strip = g.strip + hd.strip_off;      // row i (2 .. q_end) at strip + (i - 2) * kPitch
+
+  // rows 1 .. q_end (1 <= q_end <= Q - 2: the host sends other pairs elsewhere); rows below q_end are not needed
+  LocalCols<R> cols;
+  cols.load(tc, T, a.gi, a.ge);
+  int d[R][4];
+  __builtin_assume(q_end >= 1);                 // row 1 always runs, as the host guarantees: no path around it to keep registers for
+  StripObserver<true> bytes;
+  bytes.strip = strip; bytes.pitch = kPitch;
+  sweep_local<R, typename Side::Rows>(lds, cols, qr, q_end, d, bytes);
+  if constexpr (Side::kStaged) {
+    __threadfence();                                         // the last copy has landed; the walk's lanes read bytes other lanes stored
+    __syncthreads();
+  }
+  // D[q_end][t_end]: row q_end is in d[], column t_end in slot (rs, xs) of lane ls
+  const int dend = __shfl(sweep_pick<R>(d, t_end / 256, t_end & 3, 0), (t_end & 255) >> 2);
+  PairResult res = {};
+  res.best = (float)dend; res.corner = 0.f; res.best_q = q_end; res.best_t = t_end;
+  if (!((float)dend == hd.score)) {                          // not the cell the slot's score stands in: refuse the slot
+    if (lane == 0) { res.best = 0.f; res.status = ALN_E_ARG; res.n_path = 0; g.res[hit] = res; g.same[hit] = 0; }
+    return;
+  }
+  if constexpr (!Side::kStaged) {
+    __threadfence();                                         // the walk's lanes read bytes other lanes stored
+    __syncthreads();
+  }
+
+  // ---- the walk back (optimal.h:79-105), its entries handed to the job in traversal order ------------------------------------
+  typename Job::template Sink<decltype(Side::letters(a.tcodes, tch))> sink(g, a, hit, qi, qs, ts, tc, Q, T);
+  int n = 0;
+  auto emit1 = [&](int q, int t) { if (lane == 0) sink(n, q, t); ++n; };
+  emit1(Q - 1, T - 1);
+  emit1(q_end, t_end);
+  if (strip_walk<kPitch, true>(strip, q_end, t_end, n, sink)) emit1(0, 0);
+  sink.finish();
+  if (lane == 0) {
+    res.n_path = n;
+    res.status = sink.status(n);
+    g.res[hit] = res;
+    g.same[hit] = sink.same;
+  }
+}
+
+// The same for the four non-local align types (sweep_global): every row 1 .. Q-2 is swept, and the walk starts at the cell
+// the final cell's pointer names.
+template <int R, class Side, class Job>
+__global__ __launch_bounds__(64) void hit_global_kernel(ScoreArgs a, typename Job::Args g, const char* __restrict__ qch,
+                                                       const char* __restrict__ tch, int free_del, int free_ins) {
+  __shared__ __attribute__((aligned(16))) int lds[32 * 32];
+  const int lane = threadIdx.x;
+  Side::stage(lds, a);
+  const int hit = g.list[blockIdx.x];
+  const HitDesc hd = g.desc[hit];
+  const int ti = hd.t, qi = hd.q;
+  const typename Side::Rows::Src* __restrict__ qr = Side::rows(a, qi);
+  const uint8_t* __restrict__ tc = a.tcodes + a.toff[ti];
+  const auto* __restrict__ qs = Side::letters(a.qcodes, qch) + a.qoff[qi];      // what the identity is counted over
+  const auto* __restrict__ ts = Side::letters(a.tcodes, tch) + a.toff[ti];
+  const int Q = (int)(a.qoff[qi + 1] - a.qoff[qi]), T = (int)(a.toff[ti + 1] - a.toff[ti]);   // Q >= 3, T >= 3: the host's routing
+  const int gi = a.gi, ge = a.ge;
+  constexpr int kPitch = 256 * R;
+  uint8_t* strip = g.strip + hd.strip_off;      // row i (2 .. Q-2) at strip + (i - 2) * kPitch
+
+  GlobalCols<R> cols;
+  cols.load(tc, T, gi, ge);
+  GlobalObserver<R> ob(cols, free_del, free_ins ? 0 : ge, Q - 3);
+  ob.strip = strip; ob.pitch = kPitch;
+  int score = sweep_global<R, typename Side::Rows>(lds, cols, qr, Q, free_del, free_ins, ob);
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) score = max(score, __shfl_xor(score, off));
+
+  int i, j;
+  ob.final_cell(free_ins, i, j);
+  __threadfence();                                           // (staged side: the last copy has landed;) the walk's lanes read bytes other lanes stored
+  __syncthreads();
+
+  // ---- the walk back (optimal.h:56-74): it always runs to a cell of row 1 or column 1, which points at (0,0) -------------------
+  typename Job::template Sink<decltype(Side::letters(a.tcodes, tch))> sink(g, a, hit, qi, qs, ts, tc, Q, T);
+  int n = 0;
+  auto emit1 = [&](int q, int t) { if (lane == 0) sink(n, q, t); ++n; };
+  emit1(Q - 1, T - 1);
+  emit1(i, j);
+  strip_walk<kPitch, false>(strip, i, j, n, sink);
+  emit1(0, 0);
+  sink.finish();
+  if (lane == 0) {
+    PairResult res = {};
+    res.best = (float)score; res.corner = 0.f; res.best_q = Q - 1; res.best_t = T - 1;
+    res.n_path = n;
+    res.status = sink.status(n);
+    g.res[hit] = res;
+    g.same[hit] = sink.same;
+  }
+}
+
 // Where the results of one slot go, and how they are written (the same for both routes)
 struct AlignOut {
   aln_hit_alignment* out; int32_t* pairs; int32_t pair_stride; char* tlines; char* qlines; int32_t line_stride; int32_t* lengths;
@@ -219,17 +374,22 @@ struct SlotRoutes {
   std::vector<int32_t> bq, bt; std::vector<size_t> bslot;
 };
 
+// the length classes hit_local_kernel / hit_global_kernel are kept for on the run's side
+inline unsigned hit_kernel_classes(const ScoreRun& run) {
+  return run.prof ? (run.local ? ProfileQuery::kFusedLocal : ProfileQuery::kFusedGlobal)
+                  : (run.local ? ResidueQuery::kFusedLocal : ResidueQuery::kFusedGlobal);
+}
+
 // One walk over hits[rows x K] of a prepared run (`queries`: the pool lengths are read from): every n_hits[r] in 0..K, every
-// used slot's t in range and, local, its end cell in range, else ALN_E_ARG; each slot described for its route.  The fused
-// route takes integer scoring (ScoreRun::kFast), pairs with an interior, templates of up to 2048 columns and the length
-// classes an instantiation is kept for — every kept one compiles without scratch memory and without VGPR spills (the masks
-// are the side's); hint align_fused_nonlocal = 0 keeps the non-local types out of it.  Writes nothing but `sr`.
+// used slot's t in range and, with end_cell, its end cell in range, else ALN_E_ARG; each slot described for its route.  The
+// fused route takes integer scoring (ScoreRun::kFast), pairs with an interior, templates of up to 2048 columns and the length
+// classes of fused_classes, the caller's kernels' mask — every kept instantiation compiles without scratch memory and
+// without VGPR spills; hint align_fused_nonlocal = 0 keeps the non-local types out of it.  end_cell: the kernels take the
+// slot's end cell and score (hit_local_kernel); without it they are neither read nor checked.  Writes nothing but `sr`.
 inline int route_slots(const ScoreRun& run, const aln_seqs* queries, int32_t K, const aln_hit* hits, const int32_t* n_hits,
-                       SlotRoutes& sr) {
+                       unsigned fused_classes, bool end_cell, SlotRoutes& sr) {
   const aln_seqs* templates = run.templates;
   const bool fused_ok = run.route == ScoreRun::kFast && (run.local || run.ctx->hints.align_fused_nonlocal);
-  const unsigned fused_classes = run.prof ? (run.local ? ProfileQuery::kFusedLocal : ProfileQuery::kFusedGlobal)
-                                          : (run.local ? ResidueQuery::kFusedLocal : ResidueQuery::kFusedGlobal);
   for (int r = 0; r < run.rows; ++r) {
     if (n_hits[r] < 0 || n_hits[r] > K) return ALN_E_ARG;
     const int q = run.q_begin + r;
@@ -240,11 +400,11 @@ inline int route_slots(const ScoreRun& run, const aln_seqs* queries, int32_t K, 
       if (h.t < 0 || h.t >= run.n_t) return ALN_E_ARG;
       const int64_t T = templates->offsets[h.t + 1] - templates->offsets[h.t];
       const bool interior = Q >= 3 && T >= 3;
-      if (run.local && interior && (h.q_end < 1 || h.q_end > Q - 2 || h.t_end < 1 || h.t_end > T - 2)) return ALN_E_ARG;
+      if (end_cell && interior && (h.q_end < 1 || h.q_end > Q - 2 || h.t_end < 1 || h.t_end > T - 2)) return ALN_E_ARG;
       const int cls = (int)((T + 255) / 256);
       if (fused_ok && interior && T <= 2048 && ((fused_classes >> cls) & 1u)) {
-        HitDesc d = {q, h.t, 0, 0, 0.f, cls, 0};                 // non-local: the slot's end cell and score are ignored
-        if (run.local) { d.q_end = h.q_end; d.t_end = h.t_end; d.score = h.score; }
+        HitDesc d = {q, h.t, 0, 0, 0.f, cls, 0};                 // !end_cell: the slot's end cell and score are ignored
+        if (end_cell) { d.q_end = h.q_end; d.t_end = h.t_end; d.score = h.score; }
         sr.fast.push_back(d); sr.fast_slot.push_back(slot);
       } else { sr.bq.push_back(q); sr.bt.push_back(h.t); sr.bslot.push_back(slot); }
     }
@@ -266,5 +426,130 @@ inline bool align_outputs_ok(int32_t K, const aln_hit* hits, const int32_t* n_hi
   if (want_lines ? (!tlines || !qlines || line_stride < 1) : lengths != nullptr) return false;
   return true;
 }
+
+// ---- the fused route's driver: what aln_hits_align, aln_hits_align_multi and aln_hits_column_counts run their chunks through ----
+constexpr size_t kFusedBudget = (size_t)1 << 30;   // bytes of strips (of masks, of lists, of lines) resident at a time
+
+// Both leave the enclosing function (`ctx` in scope) only after the stream has been synchronised: a DeviceBufs of that
+// function, or of its caller, frees after that and never under work in flight — as long as every exit past the first
+// enqueue goes through them.  The three .hip files that include this header #undef both at their end.
+#define STRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(e_); hipStreamSynchronize(ctx->stream); return ALN_E_HIP; } } while (0)
+#define RTRY(expr) do { int r_ = (expr); if (r_ != ALN_OK) { hipStreamSynchronize(ctx->stream); return r_; } } while (0)
+
+// Device buffers with an owner: freed, and the run's device state released, when it goes out of scope
+struct DeviceBufs {
+  ScoreRun& run;
+  std::vector<void*> owned;
+  explicit DeviceBufs(ScoreRun& r) : run(r) {}
+  DeviceBufs(const DeviceBufs&) = delete;
+  ~DeviceBufs() { for (void* p : owned) hipFree(p); run.release(); }
+  template <class T>
+  hipError_t get(T*& p, size_t count) {
+    const hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
+    if (e == hipSuccess) owned.push_back(p);
+    return e;
+  }
+};
+
+struct HitNeed { size_t strip, mask; int cap; };   // of one hit: strip bytes, words of a forbidden-cell plane (0: none), most list entries
+struct FusedChunk { size_t h0, n, strip, mask; int trav_stride; int cls_cnt[9]; };   // hits [h0, h0 + n) and what they need together
+inline void place(HitDesc& d, size_t strip, size_t) { d.strip_off = (int64_t)strip; }
+
+// The fused hits of one call (Desc: HitDesc, MultiDesc), cut into chunks, and the device state every entry's chunks need.  The
+// caller gets its own buffers from `bufs`, and between stage() and launch() enqueues what else its kernels read.
+template <class Desc>
+struct FusedRoute {
+  ScoreRun& run; const aln_seqs* queries; std::vector<Desc>& fast;
+  std::vector<FusedChunk> chunks;
+  size_t max_n = 1, max_strip = 1, max_mask = 1, max_trav = 1;   // the maxima over the chunks, which size the buffers
+  DeviceBufs bufs;
+  uint8_t* dstrip = nullptr; Desc* ddesc = nullptr; int32_t *dlist = nullptr, *dfill = nullptr; char *dqch = nullptr, *dtch = nullptr;
+  FusedRoute(ScoreRun& r, const aln_seqs* q, std::vector<Desc>& f) : run(r), queries(q), fast(f), bufs(r) {}
+
+  // Every hit has N lists (0: none) of up to need(d).cap entries and, want_lines, N pairs of lines: strips, masks, lists and
+  // lines each stay below the budget; hint align_chunk_hits only asks for fewer hits.  Sets the hits' offsets into the chunk.
+  template <class Need>
+  void cut(int N, bool want_lines, int line_stride, Need&& need) {
+    const size_t forced = run.ctx->hints.align_chunk_hits > 0 ? (size_t)run.ctx->hints.align_chunk_hits : (size_t)-1;
+    auto close = [&](const FusedChunk& c) {
+      chunks.push_back(c);
+      max_n = std::max(max_n, c.n); max_strip = std::max(max_strip, c.strip); max_mask = std::max(max_mask, c.mask);
+      max_trav = std::max(max_trav, c.n * (size_t)N * c.trav_stride * 2);
+    };
+    FusedChunk c = {0, 0, 0, 0, 4, {}};
+    for (size_t h = 0; h < fast.size(); ++h) {
+      const HitNeed nd = need(fast[h]);
+      const int ts = std::max(c.trav_stride, nd.cap);
+      const bool full = c.n >= forced || c.strip + nd.strip > kFusedBudget || (c.mask + nd.mask) * 4 > kFusedBudget ||
+                        (c.n + 1) * (size_t)N * ts * 8 > kFusedBudget ||
+                        (want_lines && (c.n + 1) * (size_t)N * 2 * (size_t)line_stride > kFusedBudget);
+      if (c.n > 0 && full) {
+        close(c);
+        c = {h, 0, 0, 0, 4, {}};
+      }
+      place(fast[h], c.strip, c.mask);
+      c.strip += nd.strip; c.mask += nd.mask; c.n++; c.cls_cnt[fast[h].cls]++;
+      c.trav_stride = std::max(c.trav_stride, nd.cap);
+    }
+    if (c.n > 0) close(c);
+  }
+
+  // Profiles: the device rows of [q_begin, q_end) are uploaded once when they fit the budget, else (or under the hint) every
+  // chunk uploads the rows of its own profiles — hits are row-major, so a chunk's rows are one contiguous range.
+  int begin() {
+    aln_ctx* ctx = run.ctx;
+    if (run.prof)
+      run.rows_per_slab = ctx->hints.align_rows_per_chunk != 0 ||
+                          ((size_t)(run.prof->offsets[run.q_end] - run.prof->offsets[run.q_begin]) + kProfilePadRows) * 128 > kFusedBudget;
+    RTRY(run.upload());
+    STRY(bufs.get(dstrip, max_strip));
+    STRY(bufs.get(ddesc, max_n));
+    STRY(bufs.get(dlist, max_n));
+    STRY(bufs.get(dfill, 9));
+    return ALN_OK;
+  }
+  // The two character pools: what lines are laid out from, and what the profile kernels count the identity over
+  int upload_pools() {
+    aln_ctx* ctx = run.ctx;
+    const size_t nq = (size_t)queries->offsets[queries->n_seqs], nt = (size_t)run.templates->offsets[run.n_t];
+    STRY(bufs.get(dqch, std::max<size_t>(nq, 1)));
+    STRY(bufs.get(dtch, std::max<size_t>(nt, 1)));
+    STRY(hipMemcpyAsync(dqch, queries->residues, nq, hipMemcpyHostToDevice, ctx->stream));
+    STRY(hipMemcpyAsync(dtch, run.templates->residues, nt, hipMemcpyHostToDevice, ctx->stream));
+    return ALN_OK;
+  }
+  // The chunk's profile rows (where they go per chunk) and descriptors, then also(), the caller's own uploads that stand
+  // here in the stream's order, then `fill` zeroed for class_list_kernel
+  template <class Also>
+  int stage(const FusedChunk& c, Also&& also) {
+    aln_ctx* ctx = run.ctx;
+    if (run.prof && run.rows_per_slab) RTRY(run.upload_profile_rows(fast[c.h0].q, fast[c.h0 + c.n - 1].q + 1));
+    STRY(hipMemcpyAsync(ddesc, fast.data() + c.h0, c.n * sizeof(Desc), hipMemcpyHostToDevice, ctx->stream));
+    RTRY(also());
+    STRY(hipMemsetAsync(dfill, 0, 9 * 4, ctx->stream));
+    return ALN_OK;
+  }
+  int stage(const FusedChunk& c) { return stage(c, [] { return (int)ALN_OK; }); }
+
+  // The chunk's hits listed by class, then per class present kernel(side, k, hits of the class, their list, qch, tch): the
+  // caller's kernel<R = k, Side> over that list; the residue side never reads the pools and is passed nullptr.
+  template <class Launch>
+  int launch(const FusedChunk& c, Launch&& kernel) {
+    aln_ctx* ctx = run.ctx;
+    const int n = (int)c.n;
+    ClassOff co = {};
+    for (int k = 1; k < 9; ++k) co.off[k] = co.off[k - 1] + c.cls_cnt[k - 1];
+    const DescClass<Desc> dc = {ddesc};
+    hipLaunchKernelGGL(class_list_kernel<DescClass<Desc>>, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, dc, n, co, dfill, dlist);
+    STRY(hipGetLastError());
+    for (int k = 1; k <= 8; ++k) {
+      if (c.cls_cnt[k] == 0) continue;
+      if (run.prof) kernel(ProfileQuery(), k, c.cls_cnt[k], dlist + co.off[k], dqch, dtch);
+      else kernel(ResidueQuery(), k, c.cls_cnt[k], dlist + co.off[k], nullptr, nullptr);
+      STRY(hipGetLastError());
+    }
+    return ALN_OK;
+  }
+};
 
 }  // namespace aln

@@ -3,9 +3,9 @@
 // aln_search_topk reports, per hit, the cell the optimal local alignment ends in.  Traceback through the collapsed recurrence of
 // score_only.hip needs neither scores nor (prev_q, prev_t) pointers: five bits per cell, all of them comparisons between values
 // the row sweep already holds, say which candidate won and where a gap jump lands.  So one wave per hit
-//   align_local_hit_kernel<R>   sweeps rows 1 .. q_end (sweep_local, score_sweep.h), writes ONE byte per cell into a
-//                               transient strip of its own, walks back from the given end cell through that strip, writes
-//                               Optimal's pair list and counts the identities;
+//   hit_local_kernel<R, Side, ListJob>   (search_align.h) sweeps rows 1 .. q_end (sweep_local, score_sweep.h), writes ONE byte per cell into a
+//                               transient strip of its own, walks back from the given end cell through that strip and hands
+//                               every entry to its job: ListJob writes Optimal's pair list and counts the identities;
 //   class_list_kernel           (score_common.h) lists a chunk's hits by template length class R = ceil(T / 256);
 //   gapped_strings_kernel       (gapped_strings.hip, unchanged) lays the two lines of every list out.
 // No aln_batch, no planes, no find_max.  The strip byte of row i (2 .. q_end), column slot c:
@@ -21,7 +21,7 @@
 //   bit 4     D[i-1][c] > 0: Optimal's local walk stops BEFORE a cell whose score is <= 0 (optimal.h:100).
 // Bits 2-4 of row i describe row i-1, whose values the sweep holds while it computes row i: the last row the walk needs them
 // for is q_end - 1.  Rows 1 and columns 1 need no move: their cells point at the origin (dpmatrix.h:579-599).
-//   align_global_hit_kernel<R>  the same for the four non-local align types (sweep_global): every row 1 .. Q-2 is swept, since
+//   hit_global_kernel<R, Side, ListJob>  the same for the four non-local align types (sweep_global): every row 1 .. Q-2 is swept, since
 //                               Optimal starts at (Q-1, T-1); the byte has bits 0-3 only (nothing is clipped, so the move rule is
 //                               the reference's at every interior cell, dpmatrix.h:447-486, and no walk stops at a score); the
 //                               final cell's pointer (dpmatrix.h:505-534) comes from row Q-2, still in registers, and from what
@@ -30,6 +30,7 @@
 // without an interior, a length class an instantiation was not kept for — goes through resident batches inside the call.
 // aln_hits_align_profiles is the same call for the hits of a profile search: the same host driver (align_block), the same two
 // kernels instantiated for the profile side, and batches built from the profiles' planes for what those do not take.
+// The chunks of fused hits run through FusedRoute (search_align.h), which aln_hits_align_multi and aln_hits_column_counts share.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -38,146 +39,6 @@
 #include "search_align.h"
 
 namespace aln {
-
-constexpr size_t kAlignBudget = (size_t)1 << 30;   // bytes of strips (and of lists, and of lines) resident at a time
-
-// Both kernels are templates over the query side (ResidueQuery, ProfileQuery: score_common.h).  qch / tch: the character pools
-// of the query letters (which share the queries' offsets) and of the templates on the device.  A profile has no letters, so its
-// identity is counted over CHARACTERS — the caller's consensus pool, or the placeholder pool of ScoreRun, against the templates',
-// exactly the comparison gapped_strings_kernel makes for the lines; the residue side counts over codes, never reads the pools
-// and is passed nullptr.
-//
-// The VM counter, staged side.  The row loop holds the strip stores (R per row) beside the staging copy, and gfx950 retires
-// loads, LDS copies and stores through ONE counter in issue order.  ProfileRows::landed() waits until at most one operation is
-// outstanding; it is called right after chunk c + 1 is requested, so chunk c has landed (it is older than everything waited
-// for) — and so has every strip store issued so far: once per 8 rows the stores are drained.  That is correct and is what ships:
-// a counted wait that leaves the stores in flight was built and measured, and did not separate from this one.
-// INVARIANT (ScoreRun::upload_profile_rows): a sweep requests at most rows 0 .. Q + 13 of its profile and the buffer is padded
-// for that; the local kernel stops at q_end <= Q - 2.  The last copy requested is never read: it is drained before the walk (and
-// before the kernel returns early) so that nothing is in flight into LDS when the wave ends.
-template <int R, class Side>
-__global__ __launch_bounds__(64) void align_local_hit_kernel(ScoreArgs a, AlignArgs g, const char* __restrict__ qch,
-                                                            const char* __restrict__ tch) {
-  __shared__ __attribute__((aligned(16))) int lds[32 * 32];
-  const int lane = threadIdx.x;
-  Side::stage(lds, a);
-  const int hit = g.list[blockIdx.x];
-  const HitDesc hd = g.desc[hit];
-  const int ti = hd.t, qi = hd.q, q_end = hd.q_end, t_end = hd.t_end;
-  const typename Side::Rows::Src* __restrict__ qr = Side::rows(a, qi);
-  const uint8_t* __restrict__ tc = a.tcodes + a.toff[ti];
-  const auto* __restrict__ qs = Side::letters(a.qcodes, qch) + a.qoff[qi];      // what the identity is counted over
-  const auto* __restrict__ ts = Side::letters(a.tcodes, tch) + a.toff[ti];
-  const int Q = (int)(a.qoff[qi + 1] - a.qoff[qi]), T = (int)(a.toff[ti + 1] - a.toff[ti]);
-  constexpr int kPitch = 256 * R;
-  uint8_t* strip = g.strip + hd.strip_off;      // row i (2 .. q_end) at strip + (i - 2) * kPitch
-
-  // rows 1 .. q_end (1 <= q_end <= Q - 2: the host sends other pairs elsewhere); rows below q_end are not needed
-  LocalCols<R> cols;
-  cols.load(tc, T, a.gi, a.ge);
-  int d[R][4];
-  __builtin_assume(q_end >= 1);                 // row 1 always runs, as the host guarantees: no path around it to keep registers for
-  StripObserver<true> bytes;
-  bytes.strip = strip; bytes.pitch = kPitch;
-  sweep_local<R, typename Side::Rows>(lds, cols, qr, q_end, d, bytes);
-  if constexpr (Side::kStaged) {
-    __threadfence();                                         // the last copy has landed; the walk's lanes read bytes other lanes stored
-    __syncthreads();
-  }
-  // D[q_end][t_end]: row q_end is in d[], column t_end in slot (rs, xs) of lane ls
-  const int dend = __shfl(sweep_pick<R>(d, t_end / 256, t_end & 3, 0), (t_end & 255) >> 2);
-  PairResult res = {};
-  res.best = (float)dend; res.corner = 0.f; res.best_q = q_end; res.best_t = t_end;
-  if (!((float)dend == hd.score)) {                          // not the cell the slot's score stands in: refuse the slot
-    if (lane == 0) { res.best = 0.f; res.status = ALN_E_ARG; res.n_path = 0; g.res[hit] = res; g.same[hit] = 0; }
-    return;
-  }
-  if constexpr (!Side::kStaged) {
-    __threadfence();                                         // the walk's lanes read bytes other lanes stored
-    __syncthreads();
-  }
-
-  // ---- the walk back (optimal.h:79-105), emitted in traversal order ---------------------------------------------------------
-  int32_t* o = g.trav + (size_t)hit * g.trav_stride * 2;
-  const int cap = g.trav_stride;
-  int n = 0, same = 0;
-  auto sink = [&](int k, int q, int t) {
-    if (k < cap) {
-      o[2 * k] = q; o[2 * k + 1] = t;
-      same += (qs[q] == ts[t]) ? 1 : 0;
-    }
-  };
-  auto emit1 = [&](int q, int t) { if (lane == 0) sink(n, q, t); ++n; };
-  emit1(Q - 1, T - 1);
-  emit1(q_end, t_end);
-  if (strip_walk<kPitch, true>(strip, q_end, t_end, n, sink)) emit1(0, 0);
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) same += __shfl_xor(same, off);
-  if (lane == 0) {
-    res.n_path = n;
-    res.status = n <= cap ? 0 : ALN_E_OVERFLOW;
-    g.res[hit] = res;
-    g.same[hit] = same;
-  }
-}
-
-template <int R, class Side>
-__global__ __launch_bounds__(64) void align_global_hit_kernel(ScoreArgs a, AlignArgs g, const char* __restrict__ qch,
-                                                             const char* __restrict__ tch, int free_del, int free_ins) {
-  __shared__ __attribute__((aligned(16))) int lds[32 * 32];
-  const int lane = threadIdx.x;
-  Side::stage(lds, a);
-  const int hit = g.list[blockIdx.x];
-  const HitDesc hd = g.desc[hit];
-  const int ti = hd.t, qi = hd.q;
-  const typename Side::Rows::Src* __restrict__ qr = Side::rows(a, qi);
-  const uint8_t* __restrict__ tc = a.tcodes + a.toff[ti];
-  const auto* __restrict__ qs = Side::letters(a.qcodes, qch) + a.qoff[qi];      // what the identity is counted over
-  const auto* __restrict__ ts = Side::letters(a.tcodes, tch) + a.toff[ti];
-  const int Q = (int)(a.qoff[qi + 1] - a.qoff[qi]), T = (int)(a.toff[ti + 1] - a.toff[ti]);   // Q >= 3, T >= 3: the host's routing
-  const int gi = a.gi, ge = a.ge;
-  constexpr int kPitch = 256 * R;
-  uint8_t* strip = g.strip + hd.strip_off;      // row i (2 .. Q-2) at strip + (i - 2) * kPitch
-
-  GlobalCols<R> cols;
-  cols.load(tc, T, gi, ge);
-  GlobalObserver<R> ob(cols, free_del, free_ins ? 0 : ge, Q - 3);
-  ob.strip = strip; ob.pitch = kPitch;
-  int score = sweep_global<R, typename Side::Rows>(lds, cols, qr, Q, free_del, free_ins, ob);
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) score = max(score, __shfl_xor(score, off));
-
-  int i, j;
-  ob.final_cell(free_ins, i, j);
-  __threadfence();                                           // (staged side: the last copy has landed;) the walk's lanes read bytes other lanes stored
-  __syncthreads();
-
-  // ---- the walk back (optimal.h:56-74): it always runs to a cell of row 1 or column 1, which points at (0,0) -------------------
-  int32_t* o = g.trav + (size_t)hit * g.trav_stride * 2;
-  const int cap = g.trav_stride;
-  int n = 0, same = 0;
-  auto sink = [&](int k, int q, int t) {
-    if (k < cap) {
-      o[2 * k] = q; o[2 * k + 1] = t;
-      same += (qs[q] == ts[t]) ? 1 : 0;
-    }
-  };
-  auto emit1 = [&](int q, int t) { if (lane == 0) sink(n, q, t); ++n; };
-  emit1(Q - 1, T - 1);
-  emit1(i, j);
-  strip_walk<kPitch, false>(strip, i, j, n, sink);
-  emit1(0, 0);
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) same += __shfl_xor(same, off);
-  if (lane == 0) {
-    PairResult res = {};
-    res.best = (float)score; res.corner = 0.f; res.best_q = Q - 1; res.best_t = T - 1;
-    res.n_path = n;
-    res.status = n <= cap ? 0 : ALN_E_OVERFLOW;
-    g.res[hit] = res;
-    g.same[hit] = same;
-  }
-}
 
 // The batch route over the listed slots: aln_batch_create + aln_batch_dp + aln_batch_optimal / _strings, in the groups
 // BatchGroup (score_common.h) cuts under the plane budget.  prof != nullptr: `queries` holds the query
@@ -225,10 +86,9 @@ static int align_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
   aln_ctx* ctx = run.ctx;
   const aln_seqs* templates = run.templates;
   const aln_qprofiles* prof = run.prof;
-  const int32_t q_begin = run.q_begin;
   const bool want_lines = tlines || qlines;
   int rc;
-  const int rows = run.rows, n_t = run.n_t;
+  const int rows = run.rows;
   if (rows == 0) return ALN_OK;
   // a fused hit's strip rows and the most entries its list can have
   auto strip_rows = [&](const HitDesc& d) {
@@ -241,7 +101,7 @@ static int align_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
 
   // one walk: every used slot validated and described for its route (nothing is written before it ends)
   SlotRoutes sr;
-  if ((rc = route_slots(run, queries, K, hits, n_hits, sr)) != ALN_OK) return rc;
+  if ((rc = route_slots(run, queries, K, hits, n_hits, hit_kernel_classes(run), run.local, sr)) != ALN_OK) return rc;
   std::vector<HitDesc>& fast = sr.fast;
   const std::vector<size_t>& fast_slot = sr.fast_slot;
   const std::vector<int32_t>&bq = sr.bq, &bt = sr.bt;
@@ -257,114 +117,55 @@ static int align_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
       if (lengths) lengths[slot] = 0;
     }
 
-  // chunks of fused hits: strips, lists and lines each stay below the budget; the hint only asks for fewer
-  struct Chunk { size_t h0, n; size_t strip; int trav_stride; int cls_cnt[9]; };
-  std::vector<Chunk> chunks;
-  {
-    const size_t forced = ctx->hints.align_chunk_hits > 0 ? (size_t)ctx->hints.align_chunk_hits : (size_t)-1;
-    Chunk c = {0, 0, 0, 4, {0, 0, 0, 0, 0, 0, 0, 0, 0}};
-    for (size_t h = 0; h < fast.size(); ++h) {
-      HitDesc& d = fast[h];
-      const size_t need = (size_t)std::max(strip_rows(d), 1) * 256 * (size_t)d.cls;
-      const int ts = std::max(c.trav_stride, list_cap(d));
-      const bool full = c.n >= forced || c.strip + need > kAlignBudget || (c.n + 1) * (size_t)ts * 8 > kAlignBudget ||
-                        (want_lines && (c.n + 1) * 2 * (size_t)line_stride > kAlignBudget);
-      if (c.n > 0 && full) {
-        chunks.push_back(c);
-        c = {h, 0, 0, 4, {0, 0, 0, 0, 0, 0, 0, 0, 0}};
-      }
-      d.strip_off = (int64_t)c.strip;
-      c.strip += need; c.n++; c.cls_cnt[d.cls]++;
-      c.trav_stride = std::max(c.trav_stride, list_cap(d));
-    }
-    if (c.n > 0) chunks.push_back(c);
-  }
-
-  if (!chunks.empty()) {
-    size_t max_n = 1, max_strip = 1, max_trav = 1;
-    for (const Chunk& c : chunks) {
-      max_n = std::max(max_n, c.n); max_strip = std::max(max_strip, c.strip);
-      max_trav = std::max(max_trav, c.n * (size_t)c.trav_stride * 2);
-    }
-    uint8_t* dstrip = nullptr; HitDesc* ddesc = nullptr; int32_t *dlist = nullptr, *dfill = nullptr, *dtrav = nullptr, *dsame = nullptr;
-    PairResult* dres = nullptr; PairDesc* dpd = nullptr; StrOut* dso = nullptr; char *dlines = nullptr, *dqch = nullptr, *dtch = nullptr;
-    auto cleanup = [&]() {
-      hipFree(dstrip); hipFree(ddesc); hipFree(dlist); hipFree(dfill); hipFree(dtrav); hipFree(dsame); hipFree(dres); hipFree(dpd);
-      hipFree(dso); hipFree(dlines); hipFree(dqch); hipFree(dtch);
-      run.release();
-    };
-#define STRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(e_); hipStreamSynchronize(ctx->stream); cleanup(); return ALN_E_HIP; } } while (0)
-#define RTRY(expr) do { int r_ = (expr); if (r_ != ALN_OK) { hipStreamSynchronize(ctx->stream); cleanup(); return r_; } } while (0)
-    // profiles: the device rows of [q_begin, q_end) are uploaded once when they fit the budget, else (or under the hint) every
-    // chunk uploads the rows of its own profiles — hits are row-major, so a chunk's rows are one contiguous range
-    if (prof)
-      run.rows_per_slab = ctx->hints.align_rows_per_chunk != 0 ||
-                          ((size_t)(prof->offsets[run.q_end] - prof->offsets[q_begin]) + kProfilePadRows) * 128 > kAlignBudget;
-    RTRY(run.upload());
-    STRY(hipMalloc((void**)&dstrip, max_strip));
-    STRY(hipMalloc((void**)&ddesc, max_n * sizeof(HitDesc)));
-    STRY(hipMalloc((void**)&dlist, max_n * 4));
-    STRY(hipMalloc((void**)&dfill, 9 * 4));
-    STRY(hipMalloc((void**)&dtrav, max_trav * 4));
-    STRY(hipMalloc((void**)&dsame, max_n * 4));
-    STRY(hipMalloc((void**)&dres, max_n * sizeof(PairResult)));
+  // chunks of fused hits: one list each, and the two lines where wanted
+  if (!fast.empty()) {
+    FusedRoute<HitDesc> fr(run, queries, fast);
+    fr.cut(1, want_lines, line_stride, [&](const HitDesc& d) {
+      return HitNeed{(size_t)std::max(strip_rows(d), 1) * 256 * (size_t)d.cls, 0, list_cap(d)};
+    });
+    const size_t max_n = fr.max_n, max_trav = fr.max_trav;
+    int32_t *dtrav = nullptr, *dsame = nullptr; PairResult* dres = nullptr; PairDesc* dpd = nullptr; StrOut* dso = nullptr; char* dlines = nullptr;
+    RTRY(fr.begin());
+    STRY(fr.bufs.get(dtrav, max_trav));
+    STRY(fr.bufs.get(dsame, max_n));
+    STRY(fr.bufs.get(dres, max_n));
     std::vector<PairResult> hres(max_n);
     std::vector<int32_t> hsame(max_n), htrav(max_trav);
     std::vector<PairDesc> hpd;
     std::vector<StrOut> hso;
     std::vector<char> hlines;
-    if (want_lines || prof) {              // the profile kernels count the identity over the characters
-      const size_t nq = (size_t)queries->offsets[queries->n_seqs], nt = (size_t)templates->offsets[n_t];
-      STRY(hipMalloc((void**)&dqch, std::max<size_t>(nq, 1)));
-      STRY(hipMalloc((void**)&dtch, std::max<size_t>(nt, 1)));
-      STRY(hipMemcpyAsync(dqch, queries->residues, nq, hipMemcpyHostToDevice, ctx->stream));
-      STRY(hipMemcpyAsync(dtch, templates->residues, nt, hipMemcpyHostToDevice, ctx->stream));
-    }
+    if (want_lines || prof) RTRY(fr.upload_pools());
     if (want_lines) {
-      STRY(hipMalloc((void**)&dpd, max_n * sizeof(PairDesc)));
-      STRY(hipMalloc((void**)&dso, max_n * sizeof(StrOut)));
-      STRY(hipMalloc((void**)&dlines, max_n * 2 * (size_t)line_stride));
+      STRY(fr.bufs.get(dpd, max_n));
+      STRY(fr.bufs.get(dso, max_n));
+      STRY(fr.bufs.get(dlines, max_n * 2 * (size_t)line_stride));
       hpd.resize(max_n); hso.resize(max_n); hlines.resize(max_n * 2 * (size_t)line_stride);
     }
-    for (const Chunk& c : chunks) {
+    for (const FusedChunk& c : fr.chunks) {
       const int n = (int)c.n;
-      ClassOff co = {};
-      for (int k = 1; k < 9; ++k) co.off[k] = co.off[k - 1] + c.cls_cnt[k - 1];
-      if (prof && run.rows_per_slab) RTRY(run.upload_profile_rows(fast[c.h0].q, fast[c.h0 + c.n - 1].q + 1));
-      STRY(hipMemcpyAsync(ddesc, fast.data() + c.h0, (size_t)n * sizeof(HitDesc), hipMemcpyHostToDevice, ctx->stream));
-      STRY(hipMemsetAsync(dfill, 0, 9 * 4, ctx->stream));
-      const DescClass dc = {ddesc};
-      hipLaunchKernelGGL(class_list_kernel<DescClass>, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, dc, n, co, dfill, dlist);
-      STRY(hipGetLastError());
+      RTRY(fr.stage(c));
       AlignArgs g = {};
-      g.desc = ddesc; g.strip = dstrip; g.trav = dtrav; g.trav_stride = c.trav_stride; g.res = dres; g.same = dsame;
-      for (int k = 1; k <= 8; ++k) {
-        if (c.cls_cnt[k] == 0) continue;
-        g.list = dlist + co.off[k];
-        auto launch = [&](auto side) {
-          typedef decltype(side) Side;
-          const dim3 grid(c.cls_cnt[k]), block(64);
-          const char *qch = Side::kStaged ? dqch : nullptr, *tch = Side::kStaged ? dtch : nullptr;
-          constexpr int kLocalMax = ((Side::kFusedLocal >> 8) & 1u) ? 8 : 7;   // a class the mask leaves out never gets here
-          if (run.local)
-            dispatch_r<kLocalMax>(k, [&](auto rc) {
-              hipLaunchKernelGGL((align_local_hit_kernel<decltype(rc)::value, Side>), grid, block, 0, ctx->stream, run.a, g, qch, tch);
-            });
-          else
-            dispatch_r<8>(k, [&](auto rc) {
-              hipLaunchKernelGGL((align_global_hit_kernel<decltype(rc)::value, Side>), grid, block, 0, ctx->stream, run.a, g, qch, tch,
-                                 run.free_del, run.free_ins);
-            });
-        };
-        if (prof) launch(ProfileQuery());
-        else launch(ResidueQuery());
-        STRY(hipGetLastError());
-      }
+      g.desc = fr.ddesc; g.strip = fr.dstrip; g.trav = dtrav; g.trav_stride = c.trav_stride; g.res = dres; g.same = dsame;
+      RTRY(fr.launch(c, [&](auto side, int k, int cnt, const int32_t* list, const char* qch, const char* tch) {
+        typedef decltype(side) Side;
+        const dim3 grid(cnt), block(64);
+        g.list = list;
+        constexpr int kLocalMax = ((Side::kFusedLocal >> 8) & 1u) ? 8 : 7;   // a class the mask leaves out never gets here
+        if (run.local)
+          dispatch_r<kLocalMax>(k, [&](auto rc) {
+            hipLaunchKernelGGL((hit_local_kernel<decltype(rc)::value, Side, ListJob>), grid, block, 0, ctx->stream, run.a, g, qch, tch);
+          });
+        else
+          dispatch_r<8>(k, [&](auto rc) {
+            hipLaunchKernelGGL((hit_global_kernel<decltype(rc)::value, Side, ListJob>), grid, block, 0, ctx->stream, run.a, g, qch, tch,
+                               run.free_del, run.free_ins);
+          });
+      }));
       if (want_lines) {
         for (int h = 0; h < n; ++h) hpd[h] = pair_desc(queries, templates, fast[c.h0 + h].q, fast[c.h0 + h].t);
         STRY(hipMemcpyAsync(dpd, hpd.data(), (size_t)n * sizeof(PairDesc), hipMemcpyHostToDevice, ctx->stream));
         StrParams prm = {c.trav_stride, 1, 0, line_stride};
-        RTRY(launch_gapped_strings(ctx, n, dpd, dres, dtrav, dqch, dtch, dlines, dso, prm));
+        RTRY(launch_gapped_strings(ctx, n, dpd, dres, dtrav, fr.dqch, fr.dtch, dlines, dso, prm));
         STRY(hipMemcpyAsync(hso.data(), dso, (size_t)n * sizeof(StrOut), hipMemcpyDeviceToHost, ctx->stream));
         STRY(hipMemcpyAsync(hlines.data(), dlines, (size_t)n * 2 * (size_t)line_stride, hipMemcpyDeviceToHost, ctx->stream));
       }
@@ -379,9 +180,6 @@ static int align_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
                   want_lines ? &hso[h] : nullptr, want_lines ? hlines.data() + (size_t)h * 2 * line_stride : nullptr, line_stride);
       }
     }
-#undef STRY
-#undef RTRY
-    cleanup();
   }
   if (!bq.empty()) {
     rc = align_through_batches(ctx, queries, templates, run.sub, prof, run.gap, bq, bt, bslot, ao);
@@ -428,3 +226,6 @@ extern "C" int aln_hits_align_last_routes(const aln_ctx* ctx, int64_t out[2]) {
   out[0] = ctx->align_routes[0]; out[1] = ctx->align_routes[1];
   return ALN_OK;
 }
+
+#undef STRY
+#undef RTRY

@@ -14,10 +14,7 @@ struct MultiDesc {          // one used slot the fused kernel takes, 32 bytes
   int64_t mask_off;         // first 32-bit word of the hit's forbidden-cell plane: Q rows of 8 cls words
 };
 
-struct MultiClass {
-  const MultiDesc* desc;
-  __device__ int operator()(int h) const { return desc[h].cls; }
-};
+inline void place(MultiDesc& d, size_t strip, size_t mask) { d.strip_off = (int64_t)strip; d.mask_off = (int64_t)mask; }   // FusedRoute::cut
 
 struct MultiArgs {
   const int32_t* list;      // blockIdx.x -> hit of the chunk

@@ -8,11 +8,11 @@
 //                                 per round: sweep_local_masked (score_sweep.h) over ALL rows 1 .. Q-2 — the end cell is not
 //                                 known in advance — observed for the strip byte of every cell (search_align.hip defines it) and
 //                                 for find_max's end cell (score_local_end_kernel's rule) in the SAME sweep; the walk back of
-//                                 align_local_hit_kernel through the strip; the list, the identity count, and one bit per
+//                                 hit_local_kernel (search_align.h) through the strip; the list, the identity count, and one bit per
 //                                 aligned pair into the hit's forbidden-cell plane (1/8 B per cell) for the rounds that follow.
 // The walk needs no change: a forbidden cell holds 0 when the next row's strip byte takes its score bit, so a walk that reaches
 // one — diagonally or as a gap source — stops before it, as Optimal's does (optimal.h:100).  It is strip_walk (search_align.h), the
-// one align_local_hit_kernel calls, with a sink that also sets the pair's bit.  (DESIGN 4.8's finding is about helpers that take
+// one hit_local_kernel calls, with a sink that also sets the pair's bit.  (DESIGN 4.8's finding is about helpers that take
 // a kernel's row arrays by reference; the walk's state is scalars after the sweep, and sharing it cost no register: 4.8i.)
 //   class_list_kernel, gapped_strings_kernel   unchanged: the lines of every (hit, round) list in one launch.
 // Templates beyond the kept classes, scoring systems ScoreRun sends through full builds and pairs without an interior go
@@ -27,9 +27,7 @@
 
 namespace aln {
 
-constexpr size_t kMultiBudget = (size_t)1 << 30;   // bytes of strips (of masks, of lists, of lines) resident at a time
-
-// One template over the query side (ResidueQuery, ProfileQuery: score_common.h), as the kernels of search_align.hip are.  qch /
+// One template over the query side (ResidueQuery, ProfileQuery: score_common.h), as the kernels of search_align.h are.  qch /
 // tch: the character pools of the query letters and of the templates on the device — the staged side has no letters of its own
 // and counts the identity over CHARACTERS (the consensus pool or the placeholder, exactly what gapped_strings_kernel lays out);
 // the residue side counts over codes, never reads the pools and is passed nullptr.
@@ -242,37 +240,23 @@ static int multi_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
   aln_ctx* ctx = run.ctx;
   const aln_seqs* templates = run.templates;
   const aln_qprofiles* prof = run.prof;
-  const int32_t q_begin = run.q_begin;
   const bool want_lines = tlines || qlines;
-  const int rows = run.rows, n_t = run.n_t;
+  const int rows = run.rows;
   if (rows == 0) return ALN_OK;
-  const bool fused_ok = run.route == ScoreRun::kFast;
-  // side: the instantiations kept — every one compiles without scratch memory and without VGPR spills
-  const unsigned fused_classes = prof ? ProfileQuery::kFusedMulti : ResidueQuery::kFusedMulti;
   auto q_len = [&](int q) { return (int64_t)(queries->offsets[q + 1] - queries->offsets[q]); };
   auto t_len = [&](int t) { return (int64_t)(templates->offsets[t + 1] - templates->offsets[t]); };
 
-  // one walk: validate every used slot and describe it for its route (nothing is written before it ends)
-  std::vector<MultiDesc> fast;
-  std::vector<size_t> fast_slot;
-  std::vector<int32_t> bq, bt;
-  std::vector<size_t> bslot;
-  for (int r = 0; r < rows; ++r) {
-    if (n_hits[r] < 0 || n_hits[r] > K) return ALN_E_ARG;
-    const int q = q_begin + r;
-    const int64_t Q = q_len(q);
-    for (int k = 0; k < n_hits[r]; ++k) {
-      const size_t slot = (size_t)r * K + k;
-      const aln_hit& h = hits[slot];
-      if (h.t < 0 || h.t >= n_t) return ALN_E_ARG;
-      const int64_t T = t_len(h.t);
-      const int cls = (int)((T + 255) / 256);
-      if (fused_ok && Q >= 3 && T >= 3 && T <= 2048 && ((fused_classes >> cls) & 1u)) {
-        MultiDesc d = {q, h.t, cls, 0, 0, 0};
-        fast.push_back(d); fast_slot.push_back(slot);
-      } else { bq.push_back(q); bt.push_back(h.t); bslot.push_back(slot); }
-    }
-  }
+  // one walk: validate every used slot and describe it for its route (nothing is written before it ends).  The kernel finds
+  // every round's end cell itself: the slots' are neither read nor checked.  side: the instantiations kept — every one
+  // compiles without scratch memory and without VGPR spills
+  SlotRoutes sr;
+  int rc = route_slots(run, queries, K, hits, n_hits, prof ? ProfileQuery::kFusedMulti : ResidueQuery::kFusedMulti, false, sr);
+  if (rc != ALN_OK) return rc;
+  std::vector<MultiDesc> fast;                                 // (HitDesc is only route_slots' carrier here: its end cell and score stay 0)
+  for (const HitDesc& d : sr.fast) fast.push_back(MultiDesc{d.q, d.t, d.cls, 0, 0, 0});
+  const std::vector<size_t>& fast_slot = sr.fast_slot;
+  const std::vector<int32_t>&bq = sr.bq, &bt = sr.bt;
+  const std::vector<size_t>& bslot = sr.bslot;
   ctx->align_routes[0] = (int64_t)fast.size(); ctx->align_routes[1] = (int64_t)bq.size();
   AlignOut ao = {out, pairs, pair_stride, tlines, qlines, line_stride, lengths};
   for (size_t s = 0; s < (size_t)rows * K; ++s) {              // every record starts as "not reported"
@@ -286,122 +270,58 @@ static int multi_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
     }
   }
 
-  // chunks of fused hits: strips, masks, lists x N and lines x N each stay below the budget; the hint only asks for fewer
-  struct Chunk { size_t h0, n; size_t strip, mask; int trav_stride; int cls_cnt[9]; };
-  std::vector<Chunk> chunks;
-  {
-    const size_t forced = ctx->hints.align_chunk_hits > 0 ? (size_t)ctx->hints.align_chunk_hits : (size_t)-1;
-    Chunk c = {0, 0, 0, 0, 4, {0, 0, 0, 0, 0, 0, 0, 0, 0}};
-    for (size_t h = 0; h < fast.size(); ++h) {
-      MultiDesc& d = fast[h];
+  // chunks of fused hits: a strip, a forbidden-cell plane, N lists and, where wanted, N pairs of lines each
+  if (!fast.empty()) {
+    FusedRoute<MultiDesc> fr(run, queries, fast);
+    fr.cut(N, want_lines, line_stride, [&](const MultiDesc& d) {
       const int64_t Q = q_len(d.q), T = t_len(d.t);
-      const size_t need = (size_t)std::max<int64_t>(Q - 3, 1) * 256 * (size_t)d.cls;
-      const size_t mneed = (size_t)Q * 8 * (size_t)d.cls;       // words
-      const int lc = (int)std::min(Q, T) + 1;
-      const int ts = std::max(c.trav_stride, lc);
-      const bool full = c.n >= forced || c.strip + need > kMultiBudget || (c.mask + mneed) * 4 > kMultiBudget ||
-                        (c.n + 1) * (size_t)N * ts * 8 > kMultiBudget ||
-                        (want_lines && (c.n + 1) * (size_t)N * 2 * (size_t)line_stride > kMultiBudget);
-      if (c.n > 0 && full) {
-        chunks.push_back(c);
-        c = {h, 0, 0, 0, 4, {0, 0, 0, 0, 0, 0, 0, 0, 0}};
-      }
-      d.strip_off = (int64_t)c.strip; d.mask_off = (int64_t)c.mask;
-      c.strip += need; c.mask += mneed; c.n++; c.cls_cnt[d.cls]++;
-      c.trav_stride = std::max(c.trav_stride, lc);
-    }
-    if (c.n > 0) chunks.push_back(c);
-  }
-
-  if (!chunks.empty()) {
-    size_t max_n = 1, max_strip = 1, max_mask = 1, max_trav = 1;
-    for (const Chunk& c : chunks) {
-      max_n = std::max(max_n, c.n); max_strip = std::max(max_strip, c.strip); max_mask = std::max(max_mask, c.mask);
-      max_trav = std::max(max_trav, c.n * (size_t)N * c.trav_stride * 2);
-    }
-    const size_t max_e = max_n * (size_t)N;
-    uint8_t* dstrip = nullptr; uint32_t* dmask = nullptr; MultiDesc* ddesc = nullptr;
-    int32_t *dlist = nullptr, *dfill = nullptr, *dtrav = nullptr, *dsame = nullptr, *dfound = nullptr;
-    PairResult* dres = nullptr; PairDesc* dpd = nullptr; StrOut* dso = nullptr; char *dlines = nullptr, *dqch = nullptr, *dtch = nullptr;
-    auto cleanup = [&]() {
-      hipFree(dstrip); hipFree(dmask); hipFree(ddesc); hipFree(dlist); hipFree(dfill); hipFree(dtrav); hipFree(dsame); hipFree(dfound);
-      hipFree(dres); hipFree(dpd); hipFree(dso); hipFree(dlines); hipFree(dqch); hipFree(dtch);
-      run.release();
-    };
-#define STRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(e_); hipStreamSynchronize(ctx->stream); cleanup(); return ALN_E_HIP; } } while (0)
-#define RTRY(expr) do { int r_ = (expr); if (r_ != ALN_OK) { hipStreamSynchronize(ctx->stream); cleanup(); return r_; } } while (0)
-    // side: the device rows of [q_begin, q_end) are uploaded once when they fit the budget, else (or under the hint) every chunk
-    // uploads the rows of its own profiles — hits are row-major, so a chunk's rows are one contiguous range (aln_hits_align_profiles' rule)
-    if (prof)
-      run.rows_per_slab = ctx->hints.align_rows_per_chunk != 0 ||
-                          ((size_t)(prof->offsets[run.q_end] - prof->offsets[q_begin]) + kProfilePadRows) * 128 > kMultiBudget;
-    RTRY(run.upload());
-    STRY(hipMalloc((void**)&dstrip, max_strip));
-    STRY(hipMalloc((void**)&dmask, max_mask * 4));
-    STRY(hipMalloc((void**)&ddesc, max_n * sizeof(MultiDesc)));
-    STRY(hipMalloc((void**)&dlist, max_n * 4));
-    STRY(hipMalloc((void**)&dfill, 9 * 4));
-    STRY(hipMalloc((void**)&dtrav, max_trav * 4));
-    STRY(hipMalloc((void**)&dsame, max_e * 4));
-    STRY(hipMalloc((void**)&dfound, max_n * 4));
-    STRY(hipMalloc((void**)&dres, max_e * sizeof(PairResult)));
+      return HitNeed{(size_t)std::max<int64_t>(Q - 3, 1) * 256 * (size_t)d.cls, (size_t)Q * 8 * (size_t)d.cls, (int)std::min(Q, T) + 1};
+    });
+    const size_t max_n = fr.max_n, max_trav = fr.max_trav, max_e = max_n * (size_t)N;
+    uint32_t* dmask = nullptr; int32_t *dtrav = nullptr, *dsame = nullptr, *dfound = nullptr;
+    PairResult* dres = nullptr; PairDesc* dpd = nullptr; StrOut* dso = nullptr; char* dlines = nullptr;
+    RTRY(fr.begin());
+    STRY(fr.bufs.get(dmask, fr.max_mask));
+    STRY(fr.bufs.get(dtrav, max_trav));
+    STRY(fr.bufs.get(dsame, max_e));
+    STRY(fr.bufs.get(dfound, max_n));
+    STRY(fr.bufs.get(dres, max_e));
     std::vector<PairResult> hres(max_e);
     std::vector<int32_t> hsame(max_e), hfound(max_n), htrav(max_trav);
     std::vector<PairDesc> hpd;
     std::vector<StrOut> hso;
     std::vector<char> hlines;
-    if (want_lines || prof) {              // side: the profile kernel counts the identity over the characters
-      const size_t nq = (size_t)queries->offsets[queries->n_seqs], nt = (size_t)templates->offsets[n_t];
-      STRY(hipMalloc((void**)&dqch, std::max<size_t>(nq, 1)));
-      STRY(hipMalloc((void**)&dtch, std::max<size_t>(nt, 1)));
-      STRY(hipMemcpyAsync(dqch, queries->residues, nq, hipMemcpyHostToDevice, ctx->stream));
-      STRY(hipMemcpyAsync(dtch, templates->residues, nt, hipMemcpyHostToDevice, ctx->stream));
-    }
+    if (want_lines || prof) RTRY(fr.upload_pools());
     if (want_lines) {
-      STRY(hipMalloc((void**)&dpd, max_e * sizeof(PairDesc)));
-      STRY(hipMalloc((void**)&dso, max_e * sizeof(StrOut)));
-      STRY(hipMalloc((void**)&dlines, max_e * 2 * (size_t)line_stride));
+      STRY(fr.bufs.get(dpd, max_e));
+      STRY(fr.bufs.get(dso, max_e));
+      STRY(fr.bufs.get(dlines, max_e * 2 * (size_t)line_stride));
       hpd.resize(max_e); hso.resize(max_e); hlines.resize(max_e * 2 * (size_t)line_stride);
     }
-    for (const Chunk& c : chunks) {
+    for (const FusedChunk& c : fr.chunks) {
       const int n = (int)c.n;
       const size_t ne = (size_t)n * N;
-      ClassOff co = {};
-      for (int k = 1; k < 9; ++k) co.off[k] = co.off[k - 1] + c.cls_cnt[k - 1];
-      if (prof && run.rows_per_slab) RTRY(run.upload_profile_rows(fast[c.h0].q, fast[c.h0 + c.n - 1].q + 1));   // side:
-      STRY(hipMemcpyAsync(ddesc, fast.data() + c.h0, (size_t)n * sizeof(MultiDesc), hipMemcpyHostToDevice, ctx->stream));
-      STRY(hipMemsetAsync(dfill, 0, 9 * 4, ctx->stream));
+      RTRY(fr.stage(c));
       STRY(hipMemsetAsync(dmask, 0, c.mask * 4, ctx->stream));
       STRY(hipMemsetAsync(dres, 0, ne * sizeof(PairResult), ctx->stream));   // rounds that are not reported: n_path 0, empty lines
       STRY(hipMemsetAsync(dsame, 0, ne * 4, ctx->stream));
-      const MultiClass mc = {ddesc};
-      hipLaunchKernelGGL(class_list_kernel<MultiClass>, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, mc, n, co, dfill, dlist);
-      STRY(hipGetLastError());
       MultiArgs g = {};
-      g.desc = ddesc; g.strip = dstrip; g.mask = dmask; g.trav = dtrav; g.trav_stride = c.trav_stride; g.n_rounds = N;
+      g.desc = fr.ddesc; g.strip = fr.dstrip; g.mask = dmask; g.trav = dtrav; g.trav_stride = c.trav_stride; g.n_rounds = N;
       g.min_score = min_score; g.res = dres; g.same = dsame; g.n_found = dfound;
-      for (int k = 1; k <= 8; ++k) {
-        if (c.cls_cnt[k] == 0) continue;
-        g.list = dlist + co.off[k];
-        auto launch = [&](auto side) {                          // side: the instantiation, and the character pools it reads
-          typedef decltype(side) Side;
-          const char *qch = Side::kStaged ? dqch : nullptr, *tch = Side::kStaged ? dtch : nullptr;
-          constexpr int kMax = ((Side::kFusedMulti >> 8) & 1u) ? 8 : 7;   // a class the mask leaves out never gets here
-          dispatch_r<kMax>(k, [&](auto rc) {
-            hipLaunchKernelGGL((align_local_multi_kernel<decltype(rc)::value, Side>), dim3(c.cls_cnt[k]), dim3(64), 0, ctx->stream,
-                               run.a, g, qch, tch);
-          });
-        };
-        if (prof) launch(ProfileQuery());
-        else launch(ResidueQuery());
-        STRY(hipGetLastError());
-      }
+      RTRY(fr.launch(c, [&](auto side, int k, int cnt, const int32_t* list, const char* qch, const char* tch) {
+        typedef decltype(side) Side;
+        g.list = list;
+        constexpr int kMax = ((Side::kFusedMulti >> 8) & 1u) ? 8 : 7;   // a class the mask leaves out never gets here
+        dispatch_r<kMax>(k, [&](auto rc) {
+          hipLaunchKernelGGL((align_local_multi_kernel<decltype(rc)::value, Side>), dim3(cnt), dim3(64), 0, ctx->stream, run.a, g, qch, tch);
+        });
+      }));
       if (want_lines) {
         for (int h = 0; h < n; ++h)
           std::fill_n(hpd.begin() + (size_t)h * N, N, pair_desc(queries, templates, fast[c.h0 + h].q, fast[c.h0 + h].t));
         STRY(hipMemcpyAsync(dpd, hpd.data(), ne * sizeof(PairDesc), hipMemcpyHostToDevice, ctx->stream));
         StrParams prm = {c.trav_stride, 1, 0, line_stride};
-        RTRY(launch_gapped_strings(ctx, (int)ne, dpd, dres, dtrav, dqch, dtch, dlines, dso, prm));
+        RTRY(launch_gapped_strings(ctx, (int)ne, dpd, dres, dtrav, fr.dqch, fr.dtch, dlines, dso, prm));
         STRY(hipMemcpyAsync(hso.data(), dso, ne * sizeof(StrOut), hipMemcpyDeviceToHost, ctx->stream));
         STRY(hipMemcpyAsync(hlines.data(), dlines, ne * 2 * (size_t)line_stride, hipMemcpyDeviceToHost, ctx->stream));
       }
@@ -422,12 +342,9 @@ static int multi_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
         }
       }
     }
-#undef STRY
-#undef RTRY
-    cleanup();
   }
   if (!bq.empty()) {
-    const int rc = multi_through_batches(ctx, queries, templates, run.sub, prof, run.gap, bq, bt, bslot, N, min_score, n_found, ao);
+    rc = multi_through_batches(ctx, queries, templates, run.sub, prof, run.gap, bq, bt, bslot, N, min_score, n_found, ao);
     if (rc != ALN_OK) return rc;
   }
   return ao.worst;
@@ -472,3 +389,6 @@ extern "C" int aln_hits_align_multi_profiles(aln_ctx* ctx, const aln_qprofiles* 
   return multi_block(run, consensus ? consensus : run.queries, K, hits, n_hits, max_alignments, min_score, n_found, out, pairs,
                      pair_stride, tlines, qlines, line_stride, lengths);
 }
+
+#undef STRY
+#undef RTRY

@@ -1,5 +1,5 @@
 """Shared by tests/test_nonlocal_strip_rules.py (CPU) and tests/test_gpu_hits_align_nonlocal.py: the tie inputs, a numpy
-restatement of what align_global_hit_kernel (csrc/search_align.hip) does — the strip byte of every cell, the final cell's
+restatement of what hit_global_kernel (csrc/search_align.h) does — the strip byte of every cell, the final cell's
 pointer, the walk — computed from the oracle's D plane, and the census of the cases a set of lists went through."""
 import numpy as np
 

@@ -1,5 +1,5 @@
 """-m gpu: aln_hits_column_counts / aln_hits_column_counts_profiles — the column counts of search hits tallied on the device
-(count_local_hit_kernel, count_global_hit_kernel, csrc/search_counts.hip).  Everything is an integer and every comparison is
+(hit_local_kernel, hit_global_kernel under CountJob, csrc/search_counts.hip).  Everything is an integer and every comparison is
 equality: counts and covered against the numpy tally over the oracle's pair lists (column_count_cases), the records byte for
 byte against aln_hits_align called without lists and lines.
 

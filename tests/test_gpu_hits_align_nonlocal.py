@@ -1,4 +1,4 @@
-"""-m gpu: aln_hits_align under the four non-local align types — align_global_hit_kernel<R>: one wave per hit sweeps every
+"""-m gpu: aln_hits_align under the four non-local align types — hit_global_kernel<R>: one wave per hit sweeps every
 row, 1 byte per cell into a transient strip, the final cell's pointer from the last row and column, a walk back to the origin.
 Every comparison is exact: pair lists and lengths as integers, scores and identities as uint32, lines byte for byte.  The
 comparators are the batch route (the same call with hint align_fused_nonlocal = 0, and one resident Batch over the pairs) and,

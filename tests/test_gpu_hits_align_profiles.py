@@ -1,5 +1,5 @@
-"""-m gpu: aln_hits_align_profiles — the hits of a profile search aligned on the device (align_local_hit_kernel<R, ProfileQuery>,
-align_global_hit_kernel<R, ProfileQuery>, csrc/search_align.hip).  Every comparison is exact: pair lists and lengths as integers,
+"""-m gpu: aln_hits_align_profiles — the hits of a profile search aligned on the device (hit_local_kernel<R, ProfileQuery>,
+hit_global_kernel<R, ProfileQuery>, csrc/search_align.h).  Every comparison is exact: pair lists and lengths as integers,
 scores and identities as uint32, lines byte for byte.
 
   1  profiles derived from residue strings, consensus = those strings: aln_hits_align's outputs (search_cases.CASES)

@@ -1,4 +1,4 @@
-"""No GPU: the rules of align_global_hit_kernel (csrc/search_align.hip) — strip byte, final cell, walk — restated in numpy from
+"""No GPU: the rules of hit_global_kernel (csrc/search_align.h) — strip byte, final cell, walk — restated in numpy from
 the oracle's D plane (tests/nonlocal_cases.py) reproduce orc.optimal's list on the tie inputs, for the four non-local align
 types and the four gap families, and those inputs meet every case the GPU test's census asks for."""
 import numpy as np
