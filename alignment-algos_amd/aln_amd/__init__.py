@@ -290,45 +290,15 @@ class Context:
 
 def score_all_vs_all(ctx, queries, templates, alphabet, table, gi, ge, q_begin=0, q_end=None, align_type=LOCAL):
     """The score Optimal(align_type) reports for queries[q_begin:q_end] against every template, no planes (aln_score_all_vs_all)."""
-    qpool = queries if isinstance(queries, SeqPool) else SeqPool(queries)
-    tpool = templates if isinstance(templates, SeqPool) else SeqPool(templates)
-    if q_end is None:
-        q_end = len(qpool.seqs)
-    tab = np.ascontiguousarray(table, dtype=np.float32)
-    ab = alphabet.encode()
-    sub = AlnSubmatrix(len(alphabet), ab, _f(tab))
-    g = AlnGap()
-    g.model = GAP_AFFINE_CONST
-    g.align_type = int(align_type)
-    g.gap_init = float(np.float32(gi))
-    g.gap_extn = float(np.float32(ge))
-    out = np.empty((q_end - q_begin, len(tpool.seqs)), dtype=np.float32)
-    _check(lib().aln_score_all_vs_all(ctx.h, C.byref(qpool.c), C.byref(tpool.c), C.byref(sub), C.byref(g), q_begin, q_end, _f(out)), ctx.h)
-    return out
+    return _score(ctx, _ResidueSide("aln_score_all_vs_all", queries, templates, alphabet, table), gi, ge, q_begin, q_end, align_type)
 
 
 def search_topk(ctx, queries, templates, alphabet, table, gi, ge, K, min_score=-np.inf, q_begin=0, q_end=None, align_type=LOCAL):
     """aln_search_topk: for queries[q_begin:q_end] the K best templates with score >= min_score (score descending, ties by
     template index), selected on the device.  -> hits[rows, K] (fields t, score, q_end, t_end; unused slots -1, 0, -1, -1),
     n_hits[rows]."""
-    qpool = queries if isinstance(queries, SeqPool) else SeqPool(queries)
-    tpool = templates if isinstance(templates, SeqPool) else SeqPool(templates)
-    if q_end is None:
-        q_end = len(qpool.seqs)
-    tab = np.ascontiguousarray(table, dtype=np.float32)
-    ab = alphabet.encode()
-    sub = AlnSubmatrix(len(alphabet), ab, _f(tab))
-    g = AlnGap()
-    g.model = GAP_AFFINE_CONST
-    g.align_type = int(align_type)
-    g.gap_init = float(np.float32(gi))
-    g.gap_extn = float(np.float32(ge))
-    rows = max(q_end - q_begin, 0)
-    hits = np.zeros((rows, max(int(K), 0)), dtype=HIT_DTYPE)
-    n_hits = np.zeros(rows, dtype=np.int32)
-    _check(lib().aln_search_topk(ctx.h, C.byref(qpool.c), C.byref(tpool.c), C.byref(sub), C.byref(g), q_begin, q_end, int(K),
-                                 float(min_score), hits.ctypes.data_as(C.POINTER(AlnHit)), _i(n_hits)), ctx.h)
-    return hits, n_hits
+    return _search(ctx, _ResidueSide("aln_search_topk", queries, templates, alphabet, table), gi, ge, K, min_score, q_begin, q_end,
+                   align_type)
 
 
 class QueryProfiles:
@@ -383,27 +353,92 @@ def _const_gap(align_type, gi, ge):
 def score_profiles_vs_all(ctx, profiles, templates, gi, ge, q_begin=0, q_end=None, align_type=LOCAL):
     """aln_score_profiles_vs_all: the score Optimal(align_type) reports for profiles[q_begin:q_end] (a QueryProfiles) against
     every template, no planes -> float32 [rows, n_templates]."""
-    tpool = templates if isinstance(templates, SeqPool) else SeqPool(templates)
-    if q_end is None:
-        q_end = len(profiles)
-    g = _const_gap(align_type, gi, ge)
-    out = np.empty((q_end - q_begin, len(tpool.seqs)), dtype=np.float32)
-    _check(lib().aln_score_profiles_vs_all(ctx.h, C.byref(profiles.c), C.byref(tpool.c), C.byref(g), q_begin, q_end, _f(out)), ctx.h)
-    return out
+    return _score(ctx, _ProfileSide("aln_score_profiles_vs_all", profiles, templates), gi, ge, q_begin, q_end, align_type)
 
 
 def search_topk_profiles(ctx, profiles, templates, gi, ge, K, min_score=-np.inf, q_begin=0, q_end=None, align_type=LOCAL):
     """aln_search_topk_profiles: search_topk for position-specific queries (a QueryProfiles) -> hits[rows, K], n_hits[rows]."""
-    tpool = templates if isinstance(templates, SeqPool) else SeqPool(templates)
+    return _search(ctx, _ProfileSide("aln_search_topk_profiles", profiles, templates), gi, ge, K, min_score, q_begin, q_end, align_type)
+
+
+# ---- what the search family's entries share ---------------------------------------------------------------------------------
+# A residue entry and its profile twin differ in the leading ctypes arguments, in where query lengths and offsets come from and
+# in the entry called: that is a side.  Everything else of a pair is one body (_score, _search, _zscores, _align, _counts).
+def _pool(seqs):
+    return seqs if isinstance(seqs, SeqPool) else SeqPool(seqs)
+
+
+def _submatrix(alphabet, table):
+    """The aln_submatrix of a call.  A ctypes struct keeps the object behind a c_char_p field (the alphabet's bytes are in its
+    _objects) but NOT the array a pointer field was made from — storing the pointer copies the address only — so the table
+    rides along as an attribute and lives as long as the struct."""
+    tab = np.ascontiguousarray(table, dtype=np.float32)
+    sub = AlnSubmatrix(len(alphabet), alphabet.encode(), _f(tab))
+    sub.table_array = tab
+    return sub
+
+
+class _Side:
+    """lead: the arguments between the context and the gap (byref keeps its struct, the side keeps what the structs point to);
+    offsets: the query pool's, sentinels included, which give the queries' number and lengths; n_letters: columns of a count row."""
+
+    def call(self, ctx, gap, *tail):
+        return getattr(lib(), self.entry)(ctx.h, *(self.lead + (C.byref(gap),) + tail))
+
+
+class _ResidueSide(_Side):
+    def __init__(self, entry, queries, templates, alphabet, table):
+        self.entry, self.qpool, self.tpool, self.sub = entry, _pool(queries), _pool(templates), _submatrix(alphabet, table)
+        self.lead = (C.byref(self.qpool.c), C.byref(self.tpool.c), C.byref(self.sub))
+        self.offsets, self.n_letters = self.qpool.offsets, len(alphabet)
+
+
+class _ProfileSide(_Side):
+    def __init__(self, entry, profiles, templates, consensus=False):
+        """consensus: False for an entry without the argument, else the caller's (None: NULL)"""
+        self.entry, self.profiles, self.tpool = entry, profiles, _pool(templates)
+        self.cpool = None if consensus is None or consensus is False else _pool(consensus)
+        cons = () if consensus is False else (C.byref(self.cpool.c) if self.cpool is not None else None,)
+        self.lead = (C.byref(profiles.c),) + cons + (C.byref(self.tpool.c),)
+        self.offsets, self.n_letters = profiles.offsets, len(profiles.alphabet)
+
+
+def _as(a, struct):
+    return a.ctypes.data_as(C.POINTER(struct))
+
+
+def _score(ctx, side, gi, ge, q_begin, q_end, align_type):
     if q_end is None:
-        q_end = len(profiles)
-    g = _const_gap(align_type, gi, ge)
+        q_end = len(side.offsets) - 1
+    out = np.empty((q_end - q_begin, len(side.tpool.seqs)), dtype=np.float32)
+    _check(side.call(ctx, _const_gap(align_type, gi, ge), q_begin, q_end, _f(out)), ctx.h)
+    return out
+
+
+def _search(ctx, side, gi, ge, K, min_score, q_begin, q_end, align_type):
+    if q_end is None:
+        q_end = len(side.offsets) - 1
     rows = max(q_end - q_begin, 0)
     hits = np.zeros((rows, max(int(K), 0)), dtype=HIT_DTYPE)
     n_hits = np.zeros(rows, dtype=np.int32)
-    _check(lib().aln_search_topk_profiles(ctx.h, C.byref(profiles.c), C.byref(tpool.c), C.byref(g), q_begin, q_end, int(K),
-                                          float(min_score), hits.ctypes.data_as(C.POINTER(AlnHit)), _i(n_hits)), ctx.h)
+    _check(side.call(ctx, _const_gap(align_type, gi, ge), q_begin, q_end, int(K), float(min_score), _as(hits, AlnHit), _i(n_hits)), ctx.h)
     return hits, n_hits
+
+
+def _hit_list(hits, n_hits):
+    """a search's result as the entries take it -> hits, n_hits, rows, K"""
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    n_hits = np.ascontiguousarray(n_hits, dtype=np.int32)
+    rows, K = hits.shape
+    assert n_hits.shape == (rows,)
+    return hits, n_hits, rows, K
+
+
+def _strides(side, q_begin, rows, pair_stride, line_stride):
+    """the defaults: the longest list and line a pair of the block can have"""
+    maxq = int(np.diff(side.offsets[q_begin:q_begin + rows + 1]).max(initial=2))
+    maxt = int(np.diff(side.tpool.offsets).max(initial=2))
+    return (min(maxq, maxt) + 3 if pair_stride is None else pair_stride), (maxq + maxt + 2 if line_stride is None else line_stride)
 
 
 def _fmix32(x):
@@ -429,12 +464,7 @@ def shuffle_order(seed, q_index, s, n):
 def shuffle_query(seed, q_index, s, residues):
     """Shuffle s of query q_index (its index in the pool) under `seed`, as aln_hits_zscores permutes it (include/aln_hip.h):
     pure Python over the interior residues — `residues` comes WITHOUT sentinels.  Reproduces a background sample."""
-    key = _fmix32((_fmix32((_fmix32((seed ^ 0x9E3779B9) & 0xFFFFFFFF) + q_index) & 0xFFFFFFFF) + s) & 0xFFFFFFFF)
-    a = list(residues)
-    for i in range(len(a) - 1, 0, -1):
-        j = (_fmix32((key + i * 0x9E3779B9) & 0xFFFFFFFF) * (i + 1)) >> 32
-        a[i], a[j] = a[j], a[i]
-    return "".join(a)
+    return "".join(residues[i] for i in shuffle_order(seed, q_index, s, len(residues)))
 
 
 def hits_zscores(ctx, queries, templates, hits, n_hits, alphabet, table, gi, ge, n_shuffles, seed=0, q_begin=0, align_type=LOCAL):
@@ -442,24 +472,15 @@ def hits_zscores(ctx, queries, templates, hits, n_hits, alphabet, table, gi, ge,
     sum of squares of the scores of n_shuffles permutations of the query against the hit's template, scored and reduced on
     the device, and the z-score of the hit's own score against that sample.  Integer scoring only.
     -> stats[rows, K] (fields sum, sumsq, n, z; unused slots 0)."""
-    qpool = queries if isinstance(queries, SeqPool) else SeqPool(queries)
-    tpool = templates if isinstance(templates, SeqPool) else SeqPool(templates)
-    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
-    n_hits = np.ascontiguousarray(n_hits, dtype=np.int32)
-    rows, K = hits.shape
-    assert n_hits.shape == (rows,)
-    tab = np.ascontiguousarray(table, dtype=np.float32)
-    ab = alphabet.encode()
-    sub = AlnSubmatrix(len(alphabet), ab, _f(tab))
-    g = AlnGap()
-    g.model = GAP_AFFINE_CONST
-    g.align_type = int(align_type)
-    g.gap_init = float(np.float32(gi))
-    g.gap_extn = float(np.float32(ge))
+    return _zscores(ctx, _ResidueSide("aln_hits_zscores", queries, templates, alphabet, table), hits, n_hits, gi, ge, n_shuffles, seed,
+                    q_begin, align_type)
+
+
+def _zscores(ctx, side, hits, n_hits, gi, ge, n_shuffles, seed, q_begin, align_type):
+    hits, n_hits, rows, K = _hit_list(hits, n_hits)
     stats = np.zeros((rows, K), dtype=HIT_STATS_DTYPE)
-    _check(lib().aln_hits_zscores(ctx.h, C.byref(qpool.c), C.byref(tpool.c), C.byref(sub), C.byref(g), q_begin, q_begin + rows, int(K),
-                                  hits.ctypes.data_as(C.POINTER(AlnHit)), _i(n_hits), int(n_shuffles), int(seed) & 0xFFFFFFFF,
-                                  stats.ctypes.data_as(C.POINTER(AlnHitStats))), ctx.h)
+    _check(side.call(ctx, _const_gap(align_type, gi, ge), q_begin, q_begin + rows, int(K), _as(hits, AlnHit), _i(n_hits),
+                     int(n_shuffles), int(seed) & 0xFFFFFFFF, _as(stats, AlnHitStats)), ctx.h)
     return stats
 
 
@@ -468,17 +489,8 @@ def hits_zscores_profiles(ctx, profiles, templates, hits, n_hits, gi, ge, n_shuf
     search_topk_profiles' layout, row r is profile q_begin + r).  Shuffle s of a profile is the profile with its interior rows in
     the order shuffle_order gives; the device reads one resident copy of the rows in that order.  Integer scoring only.
     -> stats[rows, K] (fields sum, sumsq, n, z; unused slots 0)."""
-    tpool = templates if isinstance(templates, SeqPool) else SeqPool(templates)
-    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
-    n_hits = np.ascontiguousarray(n_hits, dtype=np.int32)
-    rows, K = hits.shape
-    assert n_hits.shape == (rows,)
-    g = _const_gap(align_type, gi, ge)
-    stats = np.zeros((rows, K), dtype=HIT_STATS_DTYPE)
-    _check(lib().aln_hits_zscores_profiles(ctx.h, C.byref(profiles.c), C.byref(tpool.c), C.byref(g), q_begin, q_begin + rows, int(K),
-                                           hits.ctypes.data_as(C.POINTER(AlnHit)), _i(n_hits), int(n_shuffles),
-                                           int(seed) & 0xFFFFFFFF, stats.ctypes.data_as(C.POINTER(AlnHitStats))), ctx.h)
-    return stats
+    return _zscores(ctx, _ProfileSide("aln_hits_zscores_profiles", profiles, templates), hits, n_hits, gi, ge, n_shuffles, seed,
+                    q_begin, align_type)
 
 
 def hits_align(ctx, queries, templates, hits, n_hits, alphabet, table, gi, ge, q_begin=0, align_type=LOCAL, want_pairs=True,
@@ -487,47 +499,8 @@ def hits_align(ctx, queries, templates, hits, n_hits, alphabet, table, gi, ge, q
     traced on the device from the end cell the search reported.  -> rec[rows, K] (fields n_pairs, status, score, identity;
     unused slots 0), lists (rows x K pair arrays in list order, or None), tlines, qlines (rows x K str, or None), lengths[rows, K]
     (or None), rc (the call's status: 0, or the lowest per-slot status).  Raises only when the call wrote nothing."""
-    qpool = queries if isinstance(queries, SeqPool) else SeqPool(queries)
-    tpool = templates if isinstance(templates, SeqPool) else SeqPool(templates)
-    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
-    n_hits = np.ascontiguousarray(n_hits, dtype=np.int32)
-    rows, K = hits.shape
-    assert n_hits.shape == (rows,)
-    tab = np.ascontiguousarray(table, dtype=np.float32)
-    ab = alphabet.encode()
-    sub = AlnSubmatrix(len(alphabet), ab, _f(tab))
-    g = AlnGap()
-    g.model = GAP_AFFINE_CONST
-    g.align_type = int(align_type)
-    g.gap_init = float(np.float32(gi))
-    g.gap_extn = float(np.float32(ge))
-    maxq = max([len(s) for s in qpool.seqs[q_begin:q_begin + rows]] + [2])
-    maxt = max([len(s) for s in tpool.seqs] + [2])
-    if pair_stride is None:
-        pair_stride = min(maxq, maxt) + 3
-    if line_stride is None:
-        line_stride = maxq + maxt + 2
-    rec = np.zeros((rows, K), dtype=HIT_ALIGNMENT_DTYPE)
-    pairs = np.zeros((rows, K, pair_stride, 2), dtype=np.int32) if want_pairs else None
-    tl = C.create_string_buffer(max(rows * K * line_stride, 1)) if want_lines else None
-    ql = C.create_string_buffer(max(rows * K * line_stride, 1)) if want_lines else None
-    lengths = np.zeros((rows, K), dtype=np.int32) if want_lines else None
-    rc = lib().aln_hits_align(ctx.h, C.byref(qpool.c), C.byref(tpool.c), C.byref(sub), C.byref(g), q_begin, q_begin + rows, int(K),
-                              hits.ctypes.data_as(C.POINTER(AlnHit)), _i(n_hits), rec.ctypes.data_as(C.POINTER(AlnHitAlignment)),
-                              _i(pairs) if want_pairs else None, int(pair_stride) if want_pairs else 0, tl, ql,
-                              int(line_stride) if want_lines else 0, _i(lengths) if want_lines else None)
-    if rc != 0 and not (rec["status"] == rc).any():
-        _check(rc, ctx.h)
-    lists = tlines = qlines = None
-    if want_pairs:
-        lists = [[pairs[r, k, :min(int(rec["n_pairs"][r, k]), pair_stride)].copy() for k in range(K)] for r in range(rows)]
-    if want_lines:
-        def cut(buf):
-            raw = buf.raw
-            return [[raw[(r * K + k) * line_stride:(r * K + k) * line_stride + int(lengths[r, k])].decode() for k in range(K)]
-                    for r in range(rows)]
-        tlines, qlines = cut(tl), cut(ql)
-    return rec, lists, tlines, qlines, lengths, rc
+    return _align(ctx, _ResidueSide("aln_hits_align", queries, templates, alphabet, table), hits, n_hits, gi, ge, q_begin, align_type,
+                  want_pairs, want_lines, pair_stride, line_stride)
 
 
 def _hit_outputs(rows, K, pair_stride, line_stride, want_pairs, want_lines):
@@ -539,45 +512,54 @@ def _hit_outputs(rows, K, pair_stride, line_stride, want_pairs, want_lines):
     return rec, pairs, tl, ql, lengths
 
 
+def _nest(flat, shape):
+    """a flat list as nested lists of `shape`"""
+    a = np.empty(len(flat), dtype=object)
+    for i, v in enumerate(flat):
+        a[i] = v
+    return a.reshape(shape).tolist()
+
+
+def _cut(buf, lengths, line_stride):
+    """a line buffer, one slot of line_stride bytes per entry of `lengths` ([r][k] or [r][k][a]) -> str, nested like `lengths`"""
+    raw = buf.raw
+    return _nest([raw[i * line_stride:i * line_stride + int(n)].decode() for i, n in enumerate(lengths.reshape(-1))], lengths.shape)
+
+
+def _align(ctx, side, hits, n_hits, gi, ge, q_begin, align_type, want_pairs, want_lines, pair_stride, line_stride, multi=None):
+    """hits_align's body and, with multi = (max_alignments, min_score), hits_align_multi's: M = max(N, 1) alignments per slot,
+    outputs [r][k][a] instead of [r][k], and n_found in front of rc"""
+    hits, n_hits, rows, K = _hit_list(hits, n_hits)
+    pair_stride, line_stride = _strides(side, q_begin, rows, pair_stride, line_stride)
+    shape, more = (rows, K), ()
+    if multi is not None:
+        n_found = np.zeros((rows, K), dtype=np.int32)
+        shape, more = (rows, K, max(int(multi[0]), 1)), (int(multi[0]), float(multi[1]), _i(n_found))
+    rec, pairs, tl, ql, lengths = _hit_outputs(rows, int(np.prod(shape[1:])), pair_stride, line_stride, want_pairs, want_lines)
+    rc = side.call(ctx, _const_gap(align_type, gi, ge), q_begin, q_begin + rows, int(K), _as(hits, AlnHit), _i(n_hits), *more,
+                   _as(rec, AlnHitAlignment), _i(pairs) if want_pairs else None, int(pair_stride) if want_pairs else 0, tl, ql,
+                   int(line_stride) if want_lines else 0, _i(lengths) if want_lines else None)
+    if rc != 0 and not (rec["status"] == rc).any():
+        _check(rc, ctx.h)
+    rec = rec.reshape(shape)
+    lists = tlines = qlines = None
+    if want_pairs:
+        flat = pairs.reshape(rec.size, pair_stride, 2)
+        lists = _nest([flat[i, :min(int(n), pair_stride)].copy() for i, n in enumerate(rec["n_pairs"].reshape(-1))], shape)
+    if want_lines:
+        lengths = lengths.reshape(shape)
+        tlines, qlines = _cut(tl, lengths, line_stride), _cut(ql, lengths, line_stride)
+    return (rec, lists, tlines, qlines, lengths) + (() if multi is None else (n_found,)) + (rc,)
+
+
 def hits_align_profiles(ctx, profiles, templates, hits, n_hits, gi, ge, consensus=None, q_begin=0, align_type=LOCAL, want_pairs=True,
                         want_lines=True, pair_stride=None, line_stride=None):
     """aln_hits_align_profiles: hits_align for the hits of a profile search (profiles: a QueryProfiles; hits / n_hits in
     search_topk_profiles' layout, row r is profile q_begin + r).  consensus: the query letters the lines and the identity are made
     of — one string per profile of the POOL, without sentinels and of the profile's length (or a SeqPool of such) — or None for
     the placeholder alphabet[0].  -> the 6-tuple of hits_align."""
-    tpool = templates if isinstance(templates, SeqPool) else SeqPool(templates)
-    cpool = None
-    if consensus is not None:
-        cpool = consensus if isinstance(consensus, SeqPool) else SeqPool(consensus)
-    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
-    n_hits = np.ascontiguousarray(n_hits, dtype=np.int32)
-    rows, K = hits.shape
-    assert n_hits.shape == (rows,)
-    g = _const_gap(align_type, gi, ge)
-    maxq = max([len(p) + 2 for p in profiles.profiles[q_begin:q_begin + rows]] + [2])
-    maxt = max([len(s) for s in tpool.seqs] + [2])
-    if pair_stride is None:
-        pair_stride = min(maxq, maxt) + 3
-    if line_stride is None:
-        line_stride = maxq + maxt + 2
-    rec, pairs, tl, ql, lengths = _hit_outputs(rows, K, pair_stride, line_stride, want_pairs, want_lines)
-    rc = lib().aln_hits_align_profiles(ctx.h, C.byref(profiles.c), C.byref(cpool.c) if cpool is not None else None, C.byref(tpool.c),
-                                       C.byref(g), q_begin, q_begin + rows, int(K), hits.ctypes.data_as(C.POINTER(AlnHit)), _i(n_hits),
-                                       rec.ctypes.data_as(C.POINTER(AlnHitAlignment)), _i(pairs) if want_pairs else None,
-                                       int(pair_stride) if want_pairs else 0, tl, ql, int(line_stride) if want_lines else 0,
-                                       _i(lengths) if want_lines else None)
-    if rc != 0 and not (rec["status"] == rc).any():
-        _check(rc, ctx.h)
-    lists = tlines = qlines = None
-    if want_pairs:
-        lists = [[pairs[r, k, :min(int(rec["n_pairs"][r, k]), pair_stride)].copy() for k in range(K)] for r in range(rows)]
-    if want_lines:
-        def cut(buf):
-            raw = buf.raw
-            return [[raw[(r * K + k) * line_stride:(r * K + k) * line_stride + int(lengths[r, k])].decode() for k in range(K)]
-                    for r in range(rows)]
-        tlines, qlines = cut(tl), cut(ql)
-    return rec, lists, tlines, qlines, lengths, rc
+    return _align(ctx, _ProfileSide("aln_hits_align_profiles", profiles, templates, consensus), hits, n_hits, gi, ge, q_begin, align_type,
+                  want_pairs, want_lines, pair_stride, line_stride)
 
 
 def hits_align_multi(ctx, queries, templates, hits, n_hits, alphabet, table, gi, ge, max_alignments, min_score=-np.inf, q_begin=0,
@@ -587,53 +569,8 @@ def hits_align_multi(ctx, queries, templates, hits, n_hits, alphabet, table, gi,
     the earlier rounds forbidden.  -> rec[rows, K, N] (unreported rounds 0), lists (rows x K x N pair arrays in list order, or
     None), tlines, qlines (rows x K x N str, or None), lengths[rows, K, N] (or None), n_found[rows, K], rc (0, or the lowest
     per-alignment status).  Raises only when the call wrote nothing."""
-    qpool = queries if isinstance(queries, SeqPool) else SeqPool(queries)
-    tpool = templates if isinstance(templates, SeqPool) else SeqPool(templates)
-    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
-    n_hits = np.ascontiguousarray(n_hits, dtype=np.int32)
-    rows, K = hits.shape
-    N = int(max_alignments)
-    assert n_hits.shape == (rows,)
-    tab = np.ascontiguousarray(table, dtype=np.float32)
-    ab = alphabet.encode()
-    sub = AlnSubmatrix(len(alphabet), ab, _f(tab))
-    g = _const_gap(align_type, gi, ge)
-    maxq = max([len(s) for s in qpool.seqs[q_begin:q_begin + rows]] + [2])
-    maxt = max([len(s) for s in tpool.seqs] + [2])
-    if pair_stride is None:
-        pair_stride = min(maxq, maxt) + 3
-    if line_stride is None:
-        line_stride = maxq + maxt + 2
-    M = max(N, 1)
-    rec, pairs, tl, ql, lengths = _hit_outputs(rows, K * M, pair_stride, line_stride, want_pairs, want_lines)
-    n_found = np.zeros((rows, K), dtype=np.int32)
-    rc = lib().aln_hits_align_multi(ctx.h, C.byref(qpool.c), C.byref(tpool.c), C.byref(sub), C.byref(g), q_begin, q_begin + rows, int(K),
-                                    hits.ctypes.data_as(C.POINTER(AlnHit)), _i(n_hits), N, float(min_score), _i(n_found),
-                                    rec.ctypes.data_as(C.POINTER(AlnHitAlignment)), _i(pairs) if want_pairs else None,
-                                    int(pair_stride) if want_pairs else 0, tl, ql, int(line_stride) if want_lines else 0,
-                                    _i(lengths) if want_lines else None)
-    if rc != 0 and not (rec["status"] == rc).any():
-        _check(rc, ctx.h)
-    return _multi_results(rec, pairs, tl, ql, lengths, n_found, rc, rows, K, M, pair_stride, line_stride, want_pairs, want_lines)
-
-
-def _multi_results(rec, pairs, tl, ql, lengths, n_found, rc, rows, K, M, pair_stride, line_stride, want_pairs, want_lines):
-    """the flat outputs of aln_hits_align_multi / aln_hits_align_multi_profiles -> hits_align_multi's 7-tuple"""
-    rec = rec.reshape(rows, K, M)
-    lists = tlines = qlines = None
-    if want_pairs:
-        pairs = pairs.reshape(rows, K, M, pair_stride, 2)
-        lists = [[[pairs[r, k, a, :min(int(rec["n_pairs"][r, k, a]), pair_stride)].copy() for a in range(M)] for k in range(K)]
-                 for r in range(rows)]
-    if want_lines:
-        lengths = lengths.reshape(rows, K, M)
-
-        def cut(buf):
-            raw = buf.raw
-            return [[[raw[((r * K + k) * M + a) * line_stride:((r * K + k) * M + a) * line_stride + int(lengths[r, k, a])].decode()
-                      for a in range(M)] for k in range(K)] for r in range(rows)]
-        tlines, qlines = cut(tl), cut(ql)
-    return rec, lists, tlines, qlines, lengths, n_found, rc
+    return _align(ctx, _ResidueSide("aln_hits_align_multi", queries, templates, alphabet, table), hits, n_hits, gi, ge, q_begin,
+                  align_type, want_pairs, want_lines, pair_stride, line_stride, multi=(max_alignments, min_score))
 
 
 def hits_align_multi_profiles(ctx, profiles, templates, hits, n_hits, gi, ge, max_alignments, min_score=-np.inf, consensus=None,
@@ -641,34 +578,8 @@ def hits_align_multi_profiles(ctx, profiles, templates, hits, n_hits, gi, ge, ma
     """aln_hits_align_multi_profiles: hits_align_multi for the hits of a profile search (profiles: a QueryProfiles; row r is
     profile q_begin + r; only the slots' t is read).  consensus: the query letters of the lines and the identity, as in
     hits_align_profiles, or None for the placeholder alphabet[0].  -> the 7-tuple of hits_align_multi."""
-    tpool = templates if isinstance(templates, SeqPool) else SeqPool(templates)
-    cpool = None
-    if consensus is not None:
-        cpool = consensus if isinstance(consensus, SeqPool) else SeqPool(consensus)
-    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
-    n_hits = np.ascontiguousarray(n_hits, dtype=np.int32)
-    rows, K = hits.shape
-    N = int(max_alignments)
-    assert n_hits.shape == (rows,)
-    g = _const_gap(align_type, gi, ge)
-    maxq = max([len(p) + 2 for p in profiles.profiles[q_begin:q_begin + rows]] + [2])
-    maxt = max([len(s) for s in tpool.seqs] + [2])
-    if pair_stride is None:
-        pair_stride = min(maxq, maxt) + 3
-    if line_stride is None:
-        line_stride = maxq + maxt + 2
-    M = max(N, 1)
-    rec, pairs, tl, ql, lengths = _hit_outputs(rows, K * M, pair_stride, line_stride, want_pairs, want_lines)
-    n_found = np.zeros((rows, K), dtype=np.int32)
-    rc = lib().aln_hits_align_multi_profiles(ctx.h, C.byref(profiles.c), C.byref(cpool.c) if cpool is not None else None,
-                                             C.byref(tpool.c), C.byref(g), q_begin, q_begin + rows, int(K),
-                                             hits.ctypes.data_as(C.POINTER(AlnHit)), _i(n_hits), N, float(min_score), _i(n_found),
-                                             rec.ctypes.data_as(C.POINTER(AlnHitAlignment)), _i(pairs) if want_pairs else None,
-                                             int(pair_stride) if want_pairs else 0, tl, ql, int(line_stride) if want_lines else 0,
-                                             _i(lengths) if want_lines else None)
-    if rc != 0 and not (rec["status"] == rc).any():
-        _check(rc, ctx.h)
-    return _multi_results(rec, pairs, tl, ql, lengths, n_found, rc, rows, K, M, pair_stride, line_stride, want_pairs, want_lines)
+    return _align(ctx, _ProfileSide("aln_hits_align_multi_profiles", profiles, templates, consensus), hits, n_hits, gi, ge, q_begin,
+                  align_type, want_pairs, want_lines, pair_stride, line_stride, multi=(max_alignments, min_score))
 
 
 def masked_plane(q, t, alphabet, table, forbidden, value):
@@ -693,9 +604,14 @@ def hits_align_multi_detour(ctx, queries, templates, pairs_qt, alphabet, table, 
     dp_simmatrix from planes expanded and masked on the host, then optimal + optimal_strings (`group` pairs per Batch, so that the
     host planes stay small).
     -> per pair the list of its reported rounds, each (score, pair list, identity, tline, qline, status)."""
-    queries = queries if isinstance(queries, SeqPool) else SeqPool(queries)
-    templates = templates if isinstance(templates, SeqPool) else SeqPool(templates)
-    qs, ts = queries.seqs, templates.seqs
+    queries, templates = _pool(queries), _pool(templates)
+    return _multi_detour(ctx, queries, templates, pairs_qt, gi, ge, max_alignments, min_score, group,
+                         lambda q, t: masked_plane(queries.seqs[q][1:-1], templates.seqs[t][1:-1], alphabet, table, (), 0.0))
+
+
+def _multi_detour(ctx, letters, templates, pairs_qt, gi, ge, max_alignments, min_score, group, plane):
+    """The rounds of both detours.  letters: the pool the batches take their query letters from; plane(q, t): the pair's
+    similarity plane before any cell is forbidden."""
     out = [[] for _ in pairs_qt]
     forb = [[] for _ in pairs_qt]
     neg = [0.0] * len(pairs_qt)
@@ -706,8 +622,13 @@ def hits_align_multi_detour(ctx, queries, templates, pairs_qt, alphabet, table, 
         nxt = []
         for g0 in range(0, len(alive), group):
             part = alive[g0:g0 + group]
-            planes = [masked_plane(qs[pairs_qt[p][0]][1:-1], ts[pairs_qt[p][1]][1:-1], alphabet, table, forb[p], neg[p]) for p in part]
-            b = Batch(ctx, queries, templates, [pairs_qt[p][0] for p in part], [pairs_qt[p][1] for p in part])
+            planes = []
+            for p in part:
+                S = plane(*pairs_qt[p])
+                for i, j in forb[p]:
+                    S[i, j] = neg[p]
+                planes.append(S)
+            b = Batch(ctx, letters, templates, [pairs_qt[p][0] for p in part], [pairs_qt[p][1] for p in part])
             try:
                 b.dp_simmatrix(planes, LOCAL, gi, ge)
                 scores, lists, status = b.optimal()
@@ -737,65 +658,26 @@ def hits_align_multi_profiles_detour(ctx, profiles, templates, pairs_qt, gi, ge,
     the profile by profile_planes and masked on the host; the query letters of the batches are `consensus` (one string per
     profile of the pool, no sentinels) or the placeholder alphabet[0].
     -> per pair the list of its reported rounds, each (score, pair list, identity, tline, qline, status)."""
-    alphabet = profiles.alphabet
-    letters = consensus if consensus is not None else [alphabet[0] * len(p) for p in profiles.profiles]
-    letters = letters if isinstance(letters, SeqPool) else SeqPool(letters)
-    templates = templates if isinstance(templates, SeqPool) else SeqPool(templates)
-    ts = templates.seqs
-    out = [[] for _ in pairs_qt]
-    forb = [[] for _ in pairs_qt]
-    neg = [0.0] * len(pairs_qt)
-    alive = list(range(len(pairs_qt)))
-    for a in range(int(max_alignments)):
-        if not alive:
-            break
-        nxt = []
-        for g0 in range(0, len(alive), group):
-            part = alive[g0:g0 + group]
-            planes = []
-            for p in part:
-                S = profile_planes(profiles.profiles[pairs_qt[p][0]], ts[pairs_qt[p][1]][1:-1], alphabet)
-                for i, j in forb[p]:
-                    S[i, j] = neg[p]
-                planes.append(S)
-            b = Batch(ctx, letters, templates, [pairs_qt[p][0] for p in part], [pairs_qt[p][1] for p in part])
-            try:
-                b.dp_simmatrix(planes, LOCAL, gi, ge)
-                scores, lists, status = b.optimal()
-                s2, ident, st2, tl, ql = b.optimal_strings()
-            finally:
-                b.close()
-            for k, p in enumerate(part):
-                sc = scores[k]
-                if not (sc >= min_score and (a == 0 or sc > 0)):
-                    continue
-                out[p].append((sc, lists[k], ident[k], tl[k], ql[k], int(status[k])))
-                if status[k] != 0:
-                    continue
-                Q, T = planes[k].shape
-                if a == 0:
-                    neg[p] = -(float(sc) + 1.0)
-                forb[p] += [(int(i), int(j)) for i, j in lists[k] if 1 <= i <= Q - 2 and 1 <= j <= T - 2]
-                nxt.append(p)
-        alive = nxt
-    return out
+    alphabet, templates = profiles.alphabet, _pool(templates)
+    letters = _pool(consensus if consensus is not None else [alphabet[0] * len(p) for p in profiles.profiles])
+    return _multi_detour(ctx, letters, templates, pairs_qt, gi, ge, max_alignments, min_score, group,
+                         lambda q, t: profile_planes(profiles.profiles[q], templates.seqs[t][1:-1], alphabet))
 
 
-def _count_outputs(offsets, q_begin, rows, K, n, weights, want_covered):
-    n_rows = int(offsets[q_begin + rows] - offsets[q_begin])
+def _counts(ctx, side, hits, n_hits, gi, ge, weights, q_begin, align_type, want_covered):
+    hits, n_hits, rows, K = _hit_list(hits, n_hits)
+    cut = [int(side.offsets[q_begin + r] - side.offsets[q_begin]) for r in range(rows + 1)]
     rec = np.zeros((rows, K), dtype=HIT_ALIGNMENT_DTYPE)
-    counts = np.zeros((n_rows, n), dtype=np.int32)
-    covered = np.zeros(n_rows, dtype=np.int32) if want_covered else None
+    counts = np.zeros((cut[rows], side.n_letters), dtype=np.int32)
+    covered = np.zeros(cut[rows], dtype=np.int32) if want_covered else None
     if weights is not None:
         weights = np.ascontiguousarray(weights, dtype=np.int32)
         assert weights.shape == (rows, K)
-    return rec, counts, covered, weights
-
-
-def _count_results(rec, counts, covered, rc, offsets, q_begin, rows, ctx):
+    rc = side.call(ctx, _const_gap(align_type, gi, ge), q_begin, q_begin + rows, int(K), _as(hits, AlnHit), _i(n_hits),
+                   _i(weights) if weights is not None else None, _as(rec, AlnHitAlignment), _i(counts),
+                   _i(covered) if want_covered else None)
     if rc != 0 and not (rec["status"] == rc).any():
         _check(rc, ctx.h)
-    cut = [int(offsets[q_begin + r] - offsets[q_begin]) for r in range(rows + 1)]
     return rec, [counts[cut[r]:cut[r + 1]] for r in range(rows)], covered, rc
 
 
@@ -807,22 +689,8 @@ def hits_column_counts(ctx, queries, templates, hits, n_hits, alphabet, table, g
     lists), counts (per row an int32 (Q, n) array, sentinel rows included and zero; views of one block), covered (int32, one
     entry per row of the block's queries: the weighted alignments that span the position, aligned or opposite a gap; None when
     not wanted), rc (0, or the lowest per-slot status).  Raises only when the call wrote nothing."""
-    qpool = queries if isinstance(queries, SeqPool) else SeqPool(queries)
-    tpool = templates if isinstance(templates, SeqPool) else SeqPool(templates)
-    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
-    n_hits = np.ascontiguousarray(n_hits, dtype=np.int32)
-    rows, K = hits.shape
-    assert n_hits.shape == (rows,)
-    tab = np.ascontiguousarray(table, dtype=np.float32)
-    ab = alphabet.encode()
-    sub = AlnSubmatrix(len(alphabet), ab, _f(tab))
-    g = _const_gap(align_type, gi, ge)
-    rec, counts, covered, weights = _count_outputs(qpool.offsets, q_begin, rows, K, len(alphabet), weights, want_covered)
-    rc = lib().aln_hits_column_counts(ctx.h, C.byref(qpool.c), C.byref(tpool.c), C.byref(sub), C.byref(g), q_begin, q_begin + rows,
-                                      int(K), hits.ctypes.data_as(C.POINTER(AlnHit)), _i(n_hits),
-                                      _i(weights) if weights is not None else None, rec.ctypes.data_as(C.POINTER(AlnHitAlignment)),
-                                      _i(counts), _i(covered) if want_covered else None)
-    return _count_results(rec, counts, covered, rc, qpool.offsets, q_begin, rows, ctx)
+    return _counts(ctx, _ResidueSide("aln_hits_column_counts", queries, templates, alphabet, table), hits, n_hits, gi, ge, weights,
+                   q_begin, align_type, want_covered)
 
 
 def hits_column_counts_profiles(ctx, profiles, templates, hits, n_hits, gi, ge, consensus=None, weights=None, q_begin=0,
@@ -830,23 +698,8 @@ def hits_column_counts_profiles(ctx, profiles, templates, hits, n_hits, gi, ge, 
     """aln_hits_column_counts_profiles: hits_column_counts for the hits of a profile search (profiles: a QueryProfiles, whose
     alphabet the counts' columns follow; consensus as in hits_align_profiles — it only enters the records' identity).
     -> the 4-tuple of hits_column_counts."""
-    tpool = templates if isinstance(templates, SeqPool) else SeqPool(templates)
-    cpool = None
-    if consensus is not None:
-        cpool = consensus if isinstance(consensus, SeqPool) else SeqPool(consensus)
-    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
-    n_hits = np.ascontiguousarray(n_hits, dtype=np.int32)
-    rows, K = hits.shape
-    assert n_hits.shape == (rows,)
-    g = _const_gap(align_type, gi, ge)
-    rec, counts, covered, weights = _count_outputs(profiles.offsets, q_begin, rows, K, len(profiles.alphabet), weights, want_covered)
-    rc = lib().aln_hits_column_counts_profiles(ctx.h, C.byref(profiles.c), C.byref(cpool.c) if cpool is not None else None,
-                                               C.byref(tpool.c), C.byref(g), q_begin, q_begin + rows, int(K),
-                                               hits.ctypes.data_as(C.POINTER(AlnHit)), _i(n_hits),
-                                               _i(weights) if weights is not None else None,
-                                               rec.ctypes.data_as(C.POINTER(AlnHitAlignment)), _i(counts),
-                                               _i(covered) if want_covered else None)
-    return _count_results(rec, counts, covered, rc, profiles.offsets, q_begin, rows, ctx)
+    return _counts(ctx, _ProfileSide("aln_hits_column_counts_profiles", profiles, templates, consensus), hits, n_hits, gi, ge, weights,
+                   q_begin, align_type, want_covered)
 
 
 def pssm_from_counts(counts, background, fallback_rows, pseudo=1.0, scale=2.0):
@@ -928,10 +781,7 @@ class Batch:
 
     # --- DP ---------------------------------------------------------------------------------
     def _gap(self, align_type, gi, ge, tgi=None, tge=None, tcn=None, del_tables=None, ins_tables=None):
-        g = AlnGap()
-        g.align_type = int(align_type)
-        g.gap_init = float(np.float32(gi))
-        g.gap_extn = float(np.float32(ge))
+        g = _const_gap(align_type, gi, ge)                      # the model unless one of the following replaces it
         if ins_tables is not None:
             # fully tabulated gap functions: one T x T deletion table per template sequence, three T x Q insertion planes per pair
             g.model = GAP_TABLES
@@ -962,8 +812,6 @@ class Batch:
             b = np.ascontiguousarray(tge, dtype=np.float32)
             self._keep += [a, b]
             g.t_gap_init, g.t_gap_extn = _f(a), _f(b)
-        else:
-            g.model = GAP_AFFINE_CONST
         return g
 
     def dp_submatrix(self, alphabet, table, align_type, gi, ge, direction=FWD, algo=DP_AUTO, bug_b4=False, tgi=None, tge=None):

@@ -1,8 +1,9 @@
 // score_common.h — what the all-vs-all score kernels (score_only.hip) and the entries built on them (search_topk.hip,
 // search_zscore.hip, search_align.hip, search_counts.hip) share beside the row sweep itself (score_sweep.h): the kernels'
 // argument block, the query side a kernel is instantiated for (residues scored through the table, or position-specific rows),
-// how work is listed and launched by template length class, and ScoreRun, the host side of one all-vs-all scoring call cut
-// into steps so that a caller can leave the scores of a slab of query rows in a device buffer of its own.
+// how work is listed and launched by template length class (ClassOff, class_list_kernel, launch_classes), ScoreRun, the host
+// side of one all-vs-all scoring call cut into steps so that a caller can leave the scores of a slab of query rows in a device
+// buffer of its own, and what every driver of the family leaves through and owns its device buffers with (STRY / RTRY, DeviceBufs).
 #pragma once
 #include <algorithm>
 #include <deque>
@@ -80,7 +81,33 @@ inline void dispatch_r(int r, F&& f) {
   f(std::integral_constant<int, RMAX>());
 }
 
-struct ClassOff { int off[9]; };
+struct ClassOff {
+  int off[9];
+  // a list that holds cnt[c] slots of class c, class by class: class c starts at off[c]
+  static ClassOff of(const int (&cnt)[9]) {
+    ClassOff co = {};
+    for (int k = 1; k < 9; ++k) co.off[k] = co.off[k - 1] + cnt[k - 1];
+    return co;
+  }
+};
+
+// One launch per length class present (cnt[1 .. 8]; class 0 is the full-build route's and never launched here): calls
+// f(side, std::integral_constant<int, R>(), cnt[R], ClassOff::of(cnt).off[R]) — side: ProfileQuery() or ResidueQuery() — which
+// launches the caller's kernel<R, Side> over the class's part of the list, and stops at the first launch that failed.
+template <class F>
+inline hipError_t launch_classes(bool profiles, const int (&cnt)[9], F&& f) {
+  const ClassOff co = ClassOff::of(cnt);
+  for (int k = 1; k <= 8; ++k) {
+    if (cnt[k] == 0) continue;
+    dispatch_r<8>(k, [&](auto rc) {
+      if (profiles) f(ProfileQuery(), rc, cnt[k], co.off[k]);
+      else f(ResidueQuery(), rc, cnt[k], co.off[k]);
+    });
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
 
 // list[off[c] ..) = the slots h < n_slots with cls(h) == c (cls(h) < 0: unused slot), in no particular order; fill[9] starts at 0
 template <class ClassOf>
@@ -121,7 +148,8 @@ struct FirstMaxObserver : NoObserver {
 
 // One all-vs-all scoring call (the arguments of aln_score_all_vs_all): prepare() checks them and decides the route, upload()
 // puts what the register-resident kernels read on the device, launch() enqueues those kernels for a block of query rows
-// into a device buffer of the caller.  Nothing here synchronises; the object must outlive the stream work it enqueued.
+// into a device buffer of the caller.  Nothing here synchronises but an error exit (STRY / RTRY below, which leave the device
+// state to release()'s later callers); the object must outlive the stream work it enqueued.
 // The query side is either a residue pool scored through `sub` or a pool of position-specific profiles (aln_qprofiles: `prof`
 // set, no `sub`).  For profiles `queries` is a placeholder pool the run makes itself — the profiles' offsets, every interior
 // residue alphabet[0] — so that lengths are read in one place and the full-build route has residues to create batches with.
@@ -165,8 +193,30 @@ struct ScoreRun {
   int upload_profile_rows(int32_t qa, int32_t qb);   // kFast, profiles: the rows of profiles [qa, qb) become the resident ones
   // kFast: scores of query rows [q_begin + row0, q_begin + row0 + nr) against the templates of `order` -> dscores[nr x n_t]
   int launch(int row0, int nr, float* dscores);
-  void release();
+  void release();                               // idempotent
   ~ScoreRun() { release(); }
+};
+
+// The family's one error exit.  Both leave the enclosing function (`ctx` in scope: a local, or ScoreRun's member) only after
+// the stream has been synchronised, so whatever an owner frees afterwards — a DeviceBufs of that function or of its caller,
+// ScoreRun's destructor — is never freed under work in flight, as long as every exit past the first enqueue goes through
+// them.  Every .hip file that sees them #undefs both at its end.
+#define STRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(e_); hipStreamSynchronize(ctx->stream); return ALN_E_HIP; } } while (0)
+#define RTRY(expr) do { int r_ = (expr); if (r_ != ALN_OK) { hipStreamSynchronize(ctx->stream); return r_; } } while (0)
+
+// Device buffers with an owner: freed, and the run's device state released, when it goes out of scope
+struct DeviceBufs {
+  ScoreRun& run;
+  std::vector<void*> owned;
+  explicit DeviceBufs(ScoreRun& r) : run(r) {}
+  DeviceBufs(const DeviceBufs&) = delete;
+  ~DeviceBufs() { for (void* p : owned) hipFree(p); run.release(); }
+  template <class T>
+  hipError_t get(T*& p, size_t count) {
+    const hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
+    if (e == hipSuccess) owned.push_back(p);
+    return e;
+  }
 };
 
 // scores[(q - q_begin) * ld + col[t]] for the templates of `tlist` through resident batches of full builds

@@ -411,8 +411,8 @@ void ScoreRun::release() {
   dq = dt = nullptr; dqo = dto = nullptr; dtab = dsel = dqsel = nullptr; dprows = nullptr; dprows_bytes = 0;
 }
 
-#define STRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(e_); hipStreamSynchronize(ctx->stream); release(); return ALN_E_HIP; } } while (0)
-
+// (The member functions below leave through score_common.h's STRY / RTRY over the member ctx; what they allocated is released
+// by the caller's DeviceBufs or by the destructor.)
 int ScoreRun::upload_offsets() {
   STRY(hipMalloc((void**)&dqo, (size_t)(queries->n_seqs + 1) * 8)); STRY(hipMalloc((void**)&dto, (size_t)(n_t + 1) * 8));
   STRY(hipMemcpyAsync(dqo, queries->offsets, (size_t)(queries->n_seqs + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -450,11 +450,10 @@ int ScoreRun::upload() {
     STRY(hipMemcpyAsync(dq, qc.data(), qc.size(), hipMemcpyHostToDevice, ctx->stream));
   }
   STRY(hipMemcpyAsync(dt, tc.data(), tc.size(), hipMemcpyHostToDevice, ctx->stream));
-  int rc = upload_offsets();
-  if (rc != ALN_OK) return rc;
+  RTRY(upload_offsets());
   if (!prof) STRY(hipMemcpyAsync(dtab, ti, sizeof ti, hipMemcpyHostToDevice, ctx->stream));
   a.qcodes = dq; a.qoff = dqo; a.tcodes = dt; a.toff = dto; a.table32 = dtab;
-  if (prof && !rows_per_slab && (rc = upload_profile_rows(q_begin, q_end)) != ALN_OK) return rc;
+  if (prof && !rows_per_slab) RTRY(upload_profile_rows(q_begin, q_end));
   a.q_begin = q_begin; a.n_t = n_t; a.gi = (int)gap->gap_init; a.ge = (int)gap->gap_extn;
   STRY(hipMalloc((void**)&dsel, (size_t)n_t * 4));
   if (!order.empty()) STRY(hipMemcpyAsync(dsel, order.data(), order.size() * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -482,38 +481,27 @@ int ScoreRun::launch(int row0, int nrows, float* dscores) {
     }
     STRY(hipMemcpyAsync(dqsel + row0, qo_all.data(), (size_t)nrows * 4, hipMemcpyHostToDevice, ctx->stream));
   }
-  if (prof && rows_per_slab) {
-    int rc = upload_profile_rows(q_begin + row0, q_begin + row0 + nrows);
-    if (rc != ALN_OK) return rc;
-  }
+  if (prof && rows_per_slab) RTRY(upload_profile_rows(q_begin + row0, q_begin + row0 + nrows));
+  int cls_cnt[9] = {};                                    // `order` holds the templates class by class, from class 1 on
+  for (int r = 1; r <= 8; ++r) cls_cnt[r] = cls_begin[r + 1] - cls_begin[r];
   for (int r0 = 0; r0 < nrows; r0 += 32768) {
     const int nr = std::min(32768, nrows - r0);
-    for (int r = 1; r <= 8; ++r) {
-      const int nc = cls_begin[r + 1] - cls_begin[r];
-      if (nc == 0) continue;
+    STRY(launch_classes(prof != nullptr, cls_cnt, [&](auto side, auto rc, int nc, int off) {
+      typedef decltype(side) Side;
+      constexpr int R = decltype(rc)::value;
       ScoreArgs s = a;
       s.q_begin = q_begin + row0 + r0;
       s.scores = dscores + (size_t)r0 * n_t;
-      s.tsel = dsel + cls_begin[r];
+      s.tsel = dsel + off;
       s.qsel = dqsel ? dqsel + row0 + r0 : nullptr;
       const dim3 grid(nc, packed ? (nr + 1) / 2 : nr);   // packed: two query rows per wave
-      dispatch_r<8>(r, [&](auto rc) {
-        constexpr int R = decltype(rc)::value;
-        if (packed) hipLaunchKernelGGL(score_local_pk_kernel<R>, grid, block, 0, ctx->stream, s, nr);
-        else if (prof) {
-          if (local) hipLaunchKernelGGL((score_local_kernel<R, ProfileQuery>), grid, block, 0, ctx->stream, s);
-          else hipLaunchKernelGGL((score_global_kernel<R, ProfileQuery>), grid, block, 0, ctx->stream, s, free_del, free_ins);
-        } else {
-          if (local) hipLaunchKernelGGL((score_local_kernel<R, ResidueQuery>), grid, block, 0, ctx->stream, s);
-          else hipLaunchKernelGGL((score_global_kernel<R, ResidueQuery>), grid, block, 0, ctx->stream, s, free_del, free_ins);
-        }
-      });
-      STRY(hipGetLastError());
-    }
+      if (packed) hipLaunchKernelGGL(score_local_pk_kernel<R>, grid, block, 0, ctx->stream, s, nr);   // (residues only: no side)
+      else if (local) hipLaunchKernelGGL((score_local_kernel<R, Side>), grid, block, 0, ctx->stream, s);
+      else hipLaunchKernelGGL((score_global_kernel<R, Side>), grid, block, 0, ctx->stream, s, free_del, free_ins);
+    }));
   }
   return ALN_OK;
 }
-#undef STRY
 
 }  // namespace aln
 
@@ -522,22 +510,20 @@ using namespace aln;
 // The shared body of aln_score_all_vs_all and aln_score_profiles_vs_all (run: prepared)
 static int score_block(ScoreRun& run, float* scores) {
   aln_ctx* ctx = run.ctx;
-  if (run.route == ScoreRun::kAllFull)
-    return score_through_batches(ctx, run.queries, run.templates, run.sub, run.gap, run.q_begin, run.q_end, run.every_t, scores, nullptr, 0, run.prof);
-  const int rows = run.rows, n_t = run.n_t;
-  float* dsc = nullptr;
-  int rc;
-#define STRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(e_); hipFree(dsc); return ALN_E_HIP; } } while (0)
-  STRY(hipMalloc((void**)&dsc, (size_t)rows * n_t * 4));
-  if ((rc = run.upload()) != ALN_OK || (rc = run.launch(0, rows, dsc)) != ALN_OK) { hipFree(dsc); return rc; }
-  STRY(hipMemcpyAsync(scores, dsc, (size_t)rows * n_t * 4, hipMemcpyDeviceToHost, ctx->stream));
-  STRY(hipStreamSynchronize(ctx->stream));
-#undef STRY
-  hipFree(dsc);
-  run.release();
-  if (!run.long_t.empty())
-    return score_through_batches(ctx, run.queries, run.templates, run.sub, run.gap, run.q_begin, run.q_end, run.long_t, scores, nullptr, 0, run.prof);
-  return ALN_OK;
+  const std::vector<int32_t>* full_t = &run.every_t;     // the templates that go through full builds
+  if (run.route != ScoreRun::kAllFull) {
+    const size_t n = (size_t)run.rows * run.n_t;
+    DeviceBufs bufs(run);                                  // this scope: the score buffer is freed and the run released BEFORE
+    float* dsc = nullptr;                                  // the full builds below, which want the memory
+    STRY(bufs.get(dsc, n));
+    RTRY(run.upload());
+    RTRY(run.launch(0, run.rows, dsc));
+    STRY(hipMemcpyAsync(scores, dsc, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    STRY(hipStreamSynchronize(ctx->stream));
+    full_t = &run.long_t;
+  }
+  if (full_t->empty()) return ALN_OK;
+  return score_through_batches(ctx, run.queries, run.templates, run.sub, run.gap, run.q_begin, run.q_end, *full_t, scores, nullptr, 0, run.prof);
 }
 
 // The score Optimal reports for queries[q_begin .. q_end) against every template: scores[(q - q_begin) * n_t + t].
@@ -562,3 +548,6 @@ extern "C" int aln_score_profiles_vs_all(aln_ctx* ctx, const aln_qprofiles* prof
   if (rc != ALN_OK || run.route == ScoreRun::kNothing) return rc;
   return score_block(run, scores);
 }
+
+#undef STRY
+#undef RTRY

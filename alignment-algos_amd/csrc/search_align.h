@@ -4,8 +4,8 @@
 // entry is the job's — ListJob here (search_align.hip: the pair list), CountJob in search_counts.hip (the column counts).
 // search_align_multi.hip (several rounds per hit) has a kernel of its own around the same walk.  Host: where a slot's record,
 // list and lines go (AlignOut, put_fused, pair_desc), the routing of slots (route_slots) and the fused route's driver that
-// the three entries run their chunks through (DeviceBufs, FusedRoute).  The strip byte is defined at
-// the head of search_align.hip.  DESIGN 4.8 found that a helper which takes a kernel's ROW ARRAYS by reference costs
+// the three entries run their chunks through (FusedRoute, over score_common.h's DeviceBufs, STRY / RTRY and launch_classes).
+// The strip byte is defined at the head of search_align.hip.  DESIGN 4.8 found that a helper which takes a kernel's ROW ARRAYS by reference costs
 // registers; the walk and the jobs run after the sweep on scalar state only, and sharing them costs none.
 #pragma once
 #include <algorithm>
@@ -430,27 +430,7 @@ inline bool align_outputs_ok(int32_t K, const aln_hit* hits, const int32_t* n_hi
 // ---- the fused route's driver: what aln_hits_align, aln_hits_align_multi and aln_hits_column_counts run their chunks through ----
 constexpr size_t kFusedBudget = (size_t)1 << 30;   // bytes of strips (of masks, of lists, of lines) resident at a time
 
-// Both leave the enclosing function (`ctx` in scope) only after the stream has been synchronised: a DeviceBufs of that
-// function, or of its caller, frees after that and never under work in flight — as long as every exit past the first
-// enqueue goes through them.  The three .hip files that include this header #undef both at their end.
-#define STRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(e_); hipStreamSynchronize(ctx->stream); return ALN_E_HIP; } } while (0)
-#define RTRY(expr) do { int r_ = (expr); if (r_ != ALN_OK) { hipStreamSynchronize(ctx->stream); return r_; } } while (0)
-
-// Device buffers with an owner: freed, and the run's device state released, when it goes out of scope
-struct DeviceBufs {
-  ScoreRun& run;
-  std::vector<void*> owned;
-  explicit DeviceBufs(ScoreRun& r) : run(r) {}
-  DeviceBufs(const DeviceBufs&) = delete;
-  ~DeviceBufs() { for (void* p : owned) hipFree(p); run.release(); }
-  template <class T>
-  hipError_t get(T*& p, size_t count) {
-    const hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
-    if (e == hipSuccess) owned.push_back(p);
-    return e;
-  }
-};
-
+// (The error exits STRY / RTRY and the buffer owner DeviceBufs: score_common.h.)
 struct HitNeed { size_t strip, mask; int cap; };   // of one hit: strip bytes, words of a forbidden-cell plane (0: none), most list entries
 struct FusedChunk { size_t h0, n, strip, mask; int trav_stride; int cls_cnt[9]; };   // hits [h0, h0 + n) and what they need together
 inline void place(HitDesc& d, size_t strip, size_t) { d.strip_off = (int64_t)strip; }
@@ -531,23 +511,19 @@ struct FusedRoute {
   }
   int stage(const FusedChunk& c) { return stage(c, [] { return (int)ALN_OK; }); }
 
-  // The chunk's hits listed by class, then per class present kernel(side, k, hits of the class, their list, qch, tch): the
-  // caller's kernel<R = k, Side> over that list; the residue side never reads the pools and is passed nullptr.
+  // The chunk's hits listed by class, then (launch_classes) per class present kernel(side, k, hits of the class, their list,
+  // qch, tch): the caller's kernel<R = k, Side> over that list — k at run time, because the callers' class masks decide which
+  // R they instantiate; the residue side never reads the pools and is passed nullptr.
   template <class Launch>
   int launch(const FusedChunk& c, Launch&& kernel) {
     aln_ctx* ctx = run.ctx;
     const int n = (int)c.n;
-    ClassOff co = {};
-    for (int k = 1; k < 9; ++k) co.off[k] = co.off[k - 1] + c.cls_cnt[k - 1];
     const DescClass<Desc> dc = {ddesc};
-    hipLaunchKernelGGL(class_list_kernel<DescClass<Desc>>, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, dc, n, co, dfill, dlist);
+    hipLaunchKernelGGL(class_list_kernel<DescClass<Desc>>, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, dc, n, ClassOff::of(c.cls_cnt), dfill, dlist);
     STRY(hipGetLastError());
-    for (int k = 1; k <= 8; ++k) {
-      if (c.cls_cnt[k] == 0) continue;
-      if (run.prof) kernel(ProfileQuery(), k, c.cls_cnt[k], dlist + co.off[k], dqch, dtch);
-      else kernel(ResidueQuery(), k, c.cls_cnt[k], dlist + co.off[k], nullptr, nullptr);
-      STRY(hipGetLastError());
-    }
+    STRY(launch_classes(run.prof != nullptr, c.cls_cnt, [&](auto side, auto rc, int cnt, int off) {
+      kernel(side, (int)decltype(rc)::value, cnt, dlist + off, run.prof ? dqch : nullptr, run.prof ? dtch : nullptr);
+    }));
     return ALN_OK;
   }
 };

@@ -234,23 +234,23 @@ static int search_block(ScoreRun& run, int32_t K, float min_score, aln_hit* hits
   if (ctx->hints.search_slab_rows > 0) slab_rows = std::min(rows, ctx->hints.search_slab_rows);
   const bool debug = ctx->hints.search_debug != 0;
 
+  // Everything below leaves through STRY / RTRY (score_common.h): the stream is synchronised before `bufs` frees the slab,
+  // the hit buffers and the run's device state, and before the debug events go.
+  DeviceBufs bufs(run);
+  struct Events {                                  // search_debug's four timestamps
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    ~Events() { for (hipEvent_t e : ev) if (e) hipEventDestroy(e); }
+  } events;
+  hipEvent_t (&ev)[4] = events.ev;
   float *dslab = nullptr, *dfull = nullptr; aln_hit* dhits = nullptr; int32_t *dnh = nullptr, *dlist = nullptr, *dcnt = nullptr, *dfcols = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  auto cleanup = [&]() {
-    hipFree(dslab); hipFree(dfull); hipFree(dhits); hipFree(dnh); hipFree(dlist); hipFree(dcnt); hipFree(dfcols);
-    for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
-    run.release();
-  };
-#define STRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(e_); cleanup(); return ALN_E_HIP; } } while (0)
-#define RTRY(expr) do { int r_ = (expr); if (r_ != ALN_OK) { hipStreamSynchronize(ctx->stream); cleanup(); return r_; } } while (0)
   // profiles: the block's device rows (128 B each) stay below the slab budget too, else every slab brings its own
   run.rows_per_slab = prof && (size_t)(prof->offsets[run.q_end] - prof->offsets[q_begin]) * 128 > kSlabBudget;
   RTRY(all_full ? run.upload_offsets() : run.upload());
-  STRY(hipMalloc((void**)&dslab, (size_t)slab_rows * n_t * 4));
-  STRY(hipMalloc((void**)&dhits, (size_t)slab_rows * K * sizeof(aln_hit)));
-  STRY(hipMalloc((void**)&dnh, (size_t)slab_rows * 4));
-  STRY(hipMalloc((void**)&dcnt, 18 * 4));
-  if (local) STRY(hipMalloc((void**)&dlist, (size_t)slab_rows * K * 4));
+  STRY(bufs.get(dslab, (size_t)slab_rows * n_t));
+  STRY(bufs.get(dhits, (size_t)slab_rows * K));
+  STRY(bufs.get(dnh, (size_t)slab_rows));
+  STRY(bufs.get(dcnt, 18));
+  if (local) STRY(bufs.get(dlist, (size_t)slab_rows * K));
   std::vector<float> hfull;                      // the full-build route's scores of one slab: nr x n_full
   std::vector<int32_t> fcol;                     // template -> column of hfull
   std::vector<char> is_full((size_t)n_t, all_full ? 1 : 0);
@@ -259,8 +259,8 @@ static int search_block(ScoreRun& run, int32_t K, float min_score, aln_hit* hits
     if (!all_full) {
       fcol.assign((size_t)n_t, 0);
       for (int j = 0; j < n_full; ++j) { fcol[full_t[j]] = j; is_full[full_t[j]] = 1; }
-      STRY(hipMalloc((void**)&dfull, hfull.size() * 4));
-      STRY(hipMalloc((void**)&dfcols, (size_t)n_full * 4));
+      STRY(bufs.get(dfull, hfull.size()));
+      STRY(bufs.get(dfcols, (size_t)n_full));
       STRY(hipMemcpyAsync(dfcols, full_t.data(), (size_t)n_full * 4, hipMemcpyHostToDevice, ctx->stream));
     }
   }
@@ -291,15 +291,13 @@ static int search_block(ScoreRun& run, int32_t K, float min_score, aln_hit* hits
     sa.n_t = n_t; sa.K = K; sa.q_first = q_begin + r0; sa.min_score = min_score; sa.local = local; sa.all_full = all_full;
     hipLaunchKernelGGL(topk_select_kernel, dim3(nr), dim3(kSelThreads), 0, ctx->stream, sa);
     STRY(hipGetLastError());
-    int32_t cls_cnt[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    ClassOff co = {};
+    int cls_cnt[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (local) {
       STRY(hipMemcpyAsync(cls_cnt, dcnt, sizeof cls_cnt, hipMemcpyDeviceToHost, ctx->stream));
       STRY(hipStreamSynchronize(ctx->stream));
-      for (int c = 1; c < 9; ++c) co.off[c] = co.off[c - 1] + cls_cnt[c - 1];
       const int n_slots = nr * K;
       const HitClass hc = {dhits, run.dto, (int)all_full};
-      hipLaunchKernelGGL(class_list_kernel<HitClass>, dim3((n_slots + 255) / 256), dim3(256), 0, ctx->stream, hc, n_slots, co, dcnt + 9, dlist);
+      hipLaunchKernelGGL(class_list_kernel<HitClass>, dim3((n_slots + 255) / 256), dim3(256), 0, ctx->stream, hc, n_slots, ClassOff::of(cls_cnt), dcnt + 9, dlist);
       STRY(hipGetLastError());
     }
     if (debug) STRY(hipEventRecord(ev[2], ctx->stream));
@@ -307,16 +305,10 @@ static int search_block(ScoreRun& run, int32_t K, float min_score, aln_hit* hits
     if (local && !all_full) {
       ScoreArgs s = run.a;
       s.q_begin = q_begin + r0;
-      for (int c = 1; c <= 8; ++c) {
-        if (cls_cnt[c] == 0) continue;
-        dispatch_r<8>(c, [&](auto rc) {
-          constexpr int R = decltype(rc)::value;
-          if (prof) hipLaunchKernelGGL((score_local_end_kernel<R, ProfileQuery>), dim3(cls_cnt[c]), dim3(64), 0, ctx->stream, s, dlist + co.off[c], dhits, K);
-          else hipLaunchKernelGGL((score_local_end_kernel<R, ResidueQuery>), dim3(cls_cnt[c]), dim3(64), 0, ctx->stream, s, dlist + co.off[c], dhits, K);
-        });
-        STRY(hipGetLastError());
-        n_end += cls_cnt[c];
-      }
+      STRY(launch_classes(prof != nullptr, cls_cnt, [&](auto side, auto rc, int cnt, int off) {
+        hipLaunchKernelGGL((score_local_end_kernel<decltype(rc)::value, decltype(side)>), dim3(cnt), dim3(64), 0, ctx->stream, s, dlist + off, dhits, K);
+        n_end += cnt;
+      }));
     }
     if (debug) STRY(hipEventRecord(ev[3], ctx->stream));
     aln_hit* out = hits + (size_t)r0 * K;
@@ -343,9 +335,6 @@ static int search_block(ScoreRun& run, int32_t K, float min_score, aln_hit* hits
       ms_full_end += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
   }
-#undef STRY
-#undef RTRY
-  cleanup();
   if (debug)
     fprintf(stderr, "%s: rows %d n_t %d K %d slabs %d (%d rows each) score_ms %.3f select_ms %.3f end_ms %.3f (%lld hits) "
             "full_end_ms %.3f (%lld hits)\n", entry, rows, n_t, K, n_slabs, slab_rows, ms_score, ms_select, ms_end, n_end, ms_full_end, n_full_end);
@@ -374,3 +363,6 @@ extern "C" int aln_search_topk_profiles(aln_ctx* ctx, const aln_qprofiles* profi
   if (rc != ALN_OK) return rc;
   return search_block(run, K, min_score, hits, n_hits, "aln_search_topk_profiles");
 }
+
+#undef STRY
+#undef RTRY

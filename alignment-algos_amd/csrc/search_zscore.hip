@@ -257,22 +257,17 @@ static int zscores_block(ScoreRun& run, int32_t K, const aln_hit* hits, const in
   size_t max_pool = prof ? 16 : 1; int max_nr = 1;       // side: an order is fetched 16 bytes at a time
   for (const Chunk& c : chunks) { max_pool = std::max(max_pool, c.pool); max_nr = std::max(max_nr, c.nr); }
 
-  void* dpool = nullptr; int64_t* dpoff = nullptr; int32_t *dslot = nullptr, *dlist = nullptr, *dfill = nullptr;
+  DeviceBufs bufs(run);                                  // every exit below is STRY / RTRY (score_common.h), or the last line
+  uint8_t* dpool = nullptr; int64_t* dpoff = nullptr; int32_t *dslot = nullptr, *dlist = nullptr, *dfill = nullptr;
   unsigned long long* dacc = nullptr;
-  auto cleanup = [&]() {
-    hipFree(dpool); hipFree(dpoff); hipFree(dslot); hipFree(dlist); hipFree(dfill); hipFree(dacc);
-    run.release();
-  };
-#define STRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(e_); hipStreamSynchronize(ctx->stream); cleanup(); return ALN_E_HIP; } } while (0)
-#define RTRY(expr) do { int r_ = (expr); if (r_ != ALN_OK) { hipStreamSynchronize(ctx->stream); cleanup(); return r_; } } while (0)
   RTRY(run.upload());
   const size_t max_slots = (size_t)max_nr * K;
-  STRY(hipMalloc(&dpool, max_pool));
-  STRY(hipMalloc((void**)&dpoff, (size_t)(max_nr + 1) * 8));
-  STRY(hipMalloc((void**)&dslot, max_slots * 4));
-  STRY(hipMalloc((void**)&dlist, max_slots * 4));
-  STRY(hipMalloc((void**)&dfill, 9 * 4));
-  STRY(hipMalloc((void**)&dacc, max_slots * 16));
+  STRY(bufs.get(dpool, max_pool));
+  STRY(bufs.get(dpoff, (size_t)max_nr + 1));
+  STRY(bufs.get(dslot, max_slots));
+  STRY(bufs.get(dlist, max_slots));
+  STRY(bufs.get(dfill, 9));
+  STRY(bufs.get(dacc, max_slots * 2));
   std::vector<int64_t> poff((size_t)max_nr + 1);
   std::vector<int32_t> slot_t(max_slots);
   std::vector<long long> acc(max_slots * 2);
@@ -300,8 +295,7 @@ static int zscores_block(ScoreRun& run, int32_t K, const aln_hit* hits, const in
       }
     }
     int n_used = 0;
-    ClassOff co = {};
-    for (int k = 0; k < 9; ++k) { if (k) co.off[k] = co.off[k - 1] + cls_cnt[k - 1]; n_used += cls_cnt[k]; }
+    for (int k = 0; k < 9; ++k) n_used += cls_cnt[k];
     if (n_used > cls_cnt[0]) {
       if (run.rows_per_slab) RTRY(run.upload_profile_rows(q_begin + r0, q_begin + r0 + nr));
       STRY(hipMemcpyAsync(dpoff, poff.data(), (size_t)(nr + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -314,28 +308,20 @@ static int zscores_block(ScoreRun& run, int32_t K, const aln_hit* hits, const in
       else hipLaunchKernelGGL(shuffle_queries_kernel, sgrid, dim3(256), 0, ctx->stream, sh);
       STRY(hipGetLastError());
       const SlotClass sc = {dslot, run.dto};
-      hipLaunchKernelGGL(class_list_kernel<SlotClass>, dim3((n_slots + 255) / 256), dim3(256), 0, ctx->stream, sc, n_slots, co, dfill, dlist);
+      hipLaunchKernelGGL(class_list_kernel<SlotClass>, dim3((n_slots + 255) / 256), dim3(256), 0, ctx->stream, sc, n_slots, ClassOff::of(cls_cnt), dfill, dlist);
       STRY(hipGetLastError());
       ZScoreArgs z = {};
       z.a = run.a; z.a.q_begin = q_begin + r0;          // (after upload_profile_rows: it sets a.qcodes)
       z.slot_t = dslot; z.poff = dpoff; z.pool = dpool; z.acc = dacc; z.K = K; z.S = S; z.G = G;
       z.free_del = run.free_del; z.free_ins = run.free_ins;
-      for (int k = 1; k <= 8; ++k) {
-        if (cls_cnt[k] == 0) continue;
-        z.list = dlist + co.off[k];
-        const dim3 grid(cls_cnt[k], n_groups);
-        auto launch = [&](auto side) {
-          typedef decltype(side) Side;
-          dispatch_r<8>(k, [&](auto rc) {
-            constexpr int R = decltype(rc)::value;
-            if (run.local) hipLaunchKernelGGL((score_shuffled_kernel<R, true, Side>), grid, dim3(64), 0, ctx->stream, z);
-            else hipLaunchKernelGGL((score_shuffled_kernel<R, false, Side>), grid, dim3(64), 0, ctx->stream, z);
-          });
-        };
-        if (prof) launch(ProfileQuery());
-        else launch(ResidueQuery());
-        STRY(hipGetLastError());
-      }
+      STRY(launch_classes(prof != nullptr, cls_cnt, [&](auto side, auto rc, int cnt, int off) {
+        typedef decltype(side) Side;
+        constexpr int R = decltype(rc)::value;
+        z.list = dlist + off;
+        const dim3 grid(cnt, n_groups);
+        if (run.local) hipLaunchKernelGGL((score_shuffled_kernel<R, true, Side>), grid, dim3(64), 0, ctx->stream, z);
+        else hipLaunchKernelGGL((score_shuffled_kernel<R, false, Side>), grid, dim3(64), 0, ctx->stream, z);
+      }));
       STRY(hipMemcpyAsync(acc.data(), dacc, (size_t)n_slots * 16, hipMemcpyDeviceToHost, ctx->stream));
       STRY(hipStreamSynchronize(ctx->stream));
     } else std::fill(acc.begin(), acc.begin() + (size_t)n_slots * 2, 0LL);
@@ -399,9 +385,6 @@ static int zscores_block(ScoreRun& run, int32_t K, const aln_hit* hits, const in
       }
     write_chunk(r0, nr, acc.data());
   }
-#undef STRY
-#undef RTRY
-  cleanup();
   return ALN_OK;
 }
 
@@ -429,3 +412,6 @@ extern "C" int aln_hits_zscores_profiles(aln_ctx* ctx, const aln_qprofiles* prof
   if (rc != ALN_OK) return rc;
   return zscores_block(run, K, hits, n_hits, n_shuffles, seed, stats);
 }
+
+#undef STRY
+#undef RTRY

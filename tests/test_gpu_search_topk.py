@@ -305,7 +305,29 @@ def test_hits_align_to_themselves(K, blosum62):
     assert np.array_equal(s2.view(U32), blk.reshape(-1)["score"].view(U32))
 
 
-# ---- 7. argument checks -------------------------------------------------------------------------------------------------
+# ---- 7. the debug path ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", [aln_amd.LOCAL, aln_amd.SEMI_LOCAL])
+def test_search_debug_changes_no_result(mode, blosum62):
+    """search_debug = 1 (four events per slab, a line on stderr) over slabs of 2 rows: hits and n_hits byte-equal to the default's,
+    for residue queries and for their profiles; the template of 300 residues puts a second length class into every slab"""
+    alpha, table = blosum62
+    ctx = gpu_util.ctx()
+    qs = [residues(MT19937(98000 + n), ln) for n, ln in enumerate((3, 11, 24, 33, 40))]
+    ts = [residues(MT19937(98100 + n), ln) for n, ln in enumerate((3, 9, 17, 26, 35, 40, 300))]
+    ts[6] = ts[6][:200] + qs[4] + ts[6][240:]                # a hit in class 2
+    prof = aln_amd.profiles_from_sequences(qs, alpha, table)
+    searches = [lambda: aln_amd.search_topk(ctx, qs, ts, alpha, table, 11, 1, 3, align_type=mode),
+                lambda: aln_amd.search_topk_profiles(ctx, prof, ts, 11, 1, 3, align_type=mode)]
+    for search in searches:
+        hits, n_hits = search()
+        assert (n_hits == 3).all() and 6 in hits["t"][4]
+        with ctx.hints(search_debug=1, search_slab_rows=2):
+            dbg, n_dbg = search()
+        assert ctx.get_hint("search_debug") == 0
+        assert dbg.tobytes() == hits.tobytes() and n_dbg.tobytes() == n_hits.tobytes()
+
+
+# ---- 8. argument checks -------------------------------------------------------------------------------------------------
 def test_argument_checks(blosum62):
     alpha, table = blosum62
     ctx = gpu_util.ctx()
