@@ -110,7 +110,7 @@ struct aln_hints {
   int64_t enum_node_cap = 0; // trie nodes of aln_batch_enumerate (0 = default)
   int enum_keep_pools = 1;   // 1: aln_batch_enumerate_all keeps its device pools with the batch (freed with it); 0: frees them when it returns
   int enum_debug = 0;        // 1: aln_batch_enumerate_all reports every group of pairs it searches on stderr
-  int enum_waves = 0;        // cw / ucw search: waves per pair (enumerate_par.hip); 0 = by the number of pairs, 1 = the one-wave kernel
+  int enum_waves = 0;        // cw / ucw search: waves per pair (enumerate_par.hip); 0 = 16 where the kind and the LDS allow it, 1 = the one-wave kernel
   int enum_heavy_first = 1;  // aln_batch_enumerate_all: launch the pairs in the order of what the batch's previous search used, heaviest first
   int enum_pool_retries = 2; // aln_batch_enumerate_all: times a pair whose pools overflowed is searched again with 4 x the capacity
 };
@@ -185,12 +185,14 @@ struct aln_batch {
   long optimal_build = 0;                      // n_builds when Optimal's traceback was last launched on a full build (0 = never):
                                                // equal to n_builds <=> the CURRENT build has had it (aln_gather_resident_enqueue)
   float enum_search_ms = 0.f, enum_unroll_ms = 0.f;   // last aln_batch_enumerate_all
-  // device pools of aln_batch_enumerate_all, kept between calls (hint enum_keep_pools): a hipMalloc of tens of GB costs seconds
   uint8_t* h_stage_pin = nullptr; size_t h_stage_bytes = 0;   // pinned staging of residue codes + table (upload_submatrix)
   hipEvent_t stage_ev = nullptr;                              // ... behind the last upload's copies out of it
   bool pairs_dirty = false;                                   // d_pairs differs from the full-rectangle descriptors in h_pairs
+  // device pools of aln_batch_enumerate_all, kept between calls (hint enum_keep_pools): a hipMalloc of tens of GB costs seconds
   struct Scratch { void* p = nullptr; size_t bytes = 0; };
-  Scratch enum_scratch[9];
+  enum EnumSlot { kEnumNodePair, kEnumNodeNext, kEnumHead, kEnumScore, kEnumTask, kEnumSlotInfo, kEnumLists, kEnumPacked, kEnumNodeLen,
+                  kEnumSlots };
+  Scratch enum_scratch[kEnumSlots];
   std::vector<int32_t> enum_usage;                    // ... and what every pair's search used of its pools
   // aln_batch_optimal_enqueue / _collect: two pinned result slots
   aln::PairResult* h_slot[2] = {nullptr, nullptr};

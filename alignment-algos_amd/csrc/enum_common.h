@@ -54,6 +54,24 @@ struct EnumArgs {
   int cr_tpad;
 };
 
+// The search kernels outside enumerate.hip, which its host code launches: enumerate_ks.hip, enumerate_par.hip (with the
+// block maxima of its pruned scan) and enumerate_cr.hip
+__global__ void enumerate_ks_kernel(const PairDesc* __restrict__ pairs, int pair, EvalDev proto, const uint8_t* __restrict__ qcodes,
+                                    const uint8_t* __restrict__ tcodes, const float* __restrict__ tgi, const float* __restrict__ tge,
+                                    const float* __restrict__ Hbase, const uint32_t* __restrict__ Pbase,
+                                    const float* __restrict__ Sbase, EnumArgs a);
+__global__ void enumerate_par_kernel(const PairDesc* __restrict__ pairs, int pair, EvalDev proto, const uint8_t* __restrict__ qcodes,
+                                     const uint8_t* __restrict__ tcodes, const float* __restrict__ tgi, const float* __restrict__ tge,
+                                     const float* __restrict__ Hbase, const uint32_t* __restrict__ Pbase,
+                                     const float* __restrict__ Sbase, EnumArgs a);
+__global__ void enum_blockmax_kernel(const PairDesc* __restrict__ pairs, const int32_t* __restrict__ pair_list, int pair0,
+                                     const float* __restrict__ Hbase, int h_mode, float* __restrict__ rowmax, float* __restrict__ colmax,
+                                     int bm_rows, int bm_cols, int nbt, int nbq, int bm_pair0);
+__global__ void enumerate_cr_kernel(const PairDesc* __restrict__ pairs, int pair, EvalDev proto, const uint8_t* __restrict__ qcodes,
+                                    const uint8_t* __restrict__ tcodes, const float* __restrict__ tgi, const float* __restrict__ tge,
+                                    const float* __restrict__ Hbase, const uint32_t* __restrict__ Pbase,
+                                    const float* __restrict__ Sbase, EnumArgs a);
+
 constexpr uint32_t kNoNode = 0xFFFFFFFFu;
 
 // One alignment out of the trie, in list order (head -> end), by one wave: a node is one cell, or (node_len != nullptr) a run of

@@ -65,8 +65,9 @@ def _bits(x):
 
 
 # ---- aln_batch_enumerate through the ABI itself: the records as the library wrote them -------------------------------------------
-def _raw_enumerate(b, p, kind, nsub, delta, fl, user_limit, max_alignments, n_existing=-1, existing=None, **kw):
-    """-> rc, n_out, records (score, identity, uid, n_pairs, pair_off), pairs; everything sentinel-filled before the call"""
+def _raw_enumerate(b, p, kind, nsub, delta, fl, user_limit, max_alignments, n_existing=-1, existing=None, pairs_capacity=None, **kw):
+    """-> rc, n_out, records (score, identity, uid, n_pairs, pair_off), pairs; everything sentinel-filled before the call.
+    pairs_capacity: what the library is told of the pairs array (default: all of it)"""
     Q, T = b.dims(p)
     ex = None if existing is None else np.ascontiguousarray(existing, dtype=np.float32)
     noa = aln_amd.AlnNoa(aln_amd._ENUM[kind], int(nsub), float(np.float32(delta)), int(user_limit), int(n_existing),
@@ -78,7 +79,8 @@ def _raw_enumerate(b, p, kind, nsub, delta, fl, user_limit, max_alignments, n_ex
     n = C.c_int32(SENTINEL)
     flp = np.ascontiguousarray(fl, dtype=np.uint8)
     rc = aln_amd.lib().aln_batch_enumerate(b.h, p, C.byref(noa), flp.ctypes.data_as(C.POINTER(C.c_uint8)), out, max_alignments,
-                                           pairs.ctypes.data_as(C.POINTER(C.c_int32)), len(pairs), C.byref(n))
+                                           pairs.ctypes.data_as(C.POINTER(C.c_int32)), len(pairs) if pairs_capacity is None else pairs_capacity,
+                                           C.byref(n))
     recs = [(np.float32(a.score), np.float32(a.identity), a.uid, a.n_pairs, a.pair_off) for a in out]
     return rc, n.value, recs, pairs
 
@@ -403,6 +405,65 @@ def test_task_ring_wraps(knd, par_waves, pool_batch, capfd):
     print(knd, par_waves, "ali_cap", ali_cap, "tasks", tasks.tolist())
     assert b.last_enum_usage()[0].tolist() == created
     assert (tasks > ali_cap).sum() >= 2, (tasks.tolist(), ali_cap)
+
+
+# ---- 2b. the one-pair entry point's overflow exits ------------------------------------------------------------------------------
+def _one_pair(b, r, p, node_cap, **kw):
+    """pair p of the ragged batch under the run r through aln_batch_enumerate, with enum_node_cap = node_cap"""
+    rkw = ep.run_kw(r)
+    with gpu_util.ctx().hints(enum_node_cap=node_cap):
+        return _raw_enumerate(b, p, r.kind, r.nsub, r.delta, ep.flags(ep.POOL_PAIRS[p], ep.run_regions(r)[p]), rkw.pop("user_limit"),
+                              r.nsub + 2, **dict(rkw, **kw))
+
+
+@pytest.mark.parametrize("knd", list(ep.LARGE))
+def test_one_pair_node_pool_overflows_several_waves(knd, pool_batch, large_one_pair):
+    """aln_batch_enumerate has no retries: a pair that needs a second chunk of the several-wave kernel's node pool (taken from
+    the usage a batched call records) reports ALN_E_OVERFLOW under enum_node_cap = one chunk and writes nothing; the same call on
+    the same batch with 16 chunks returns the set the fixture's call with the default pool returned."""
+    b, r = pool_batch, ep.LARGE[knd]
+    want = large_one_pair(knd)
+    _check_all(_raw_all(b, r, node_cap=1 << 20, ali_cap=1 << 16), r)
+    nodes = b.last_enum_usage()[1]
+    p = [p for p in range(b.n) if nodes[p] > CHUNK][0]
+    print(knd, "pair", p, "nodes", int(nodes[p]))
+    rc, n, recs, pairs = _one_pair(b, r, p, CHUNK)
+    assert rc == aln_amd.E_OVERFLOW and n == SENTINEL and _untouched(recs, pairs), (knd, p, rc, n)
+    rc, n, recs, pairs = _one_pair(b, r, p, 1 << 20)
+    assert rc == 0 and n == len(want[p]), (knd, p, rc, n, len(want[p]))
+    for k, w in enumerate(want[p]):
+        score, identity, uid, n_pairs, pair_off = recs[k]
+        assert _bits(score) == _bits(w["score"]) and _bits(identity) == _bits(w["identity"]) and uid == w["uid"], (knd, p, k)
+        assert n_pairs == len(w["pairs"]) and np.array_equal(pairs[pair_off:pair_off + n_pairs], w["pairs"]), (knd, p, k)
+
+
+@pytest.mark.parametrize("knd", ep.KINDS)
+def test_one_pair_node_pool_overflows_one_wave(knd, pool_batch):
+    """The one-wave kernels, enum_node_cap between the smallest and the largest need of the batch (from the recorded usage, as
+    in test_node_pool_grows_in_the_one_wave_kernels): a pair above the cap reports ALN_E_OVERFLOW and writes nothing, a pair
+    below it is complete, and the overflowed pair is complete under a larger cap — the error exit leaves the batch usable."""
+    b, r = pool_batch, ep.SMALL[knd]
+    with gpu_util.ctx().hints(enum_waves=1):
+        _check_all(_raw_all(b, r), r)
+        nodes = b.last_enum_usage()[1]
+        cap = int(nodes.max()) // 8 + 64
+        below, above = [p for p in range(b.n) if nodes[p] <= cap][0], [p for p in range(b.n) if nodes[p] > cap][0]
+        print(knd, "nodes", nodes.tolist(), "node_cap", cap, "below", below, "above", above)
+        rc, n, recs, pairs = _one_pair(b, r, above, cap)
+        assert rc == aln_amd.E_OVERFLOW and n == SENTINEL and _untouched(recs, pairs), (knd, above, rc, n)
+        _check_records(*_one_pair(b, r, below, cap), ep.run_search(r, below).alis, (), (knd, "below", below))
+        _check_records(*_one_pair(b, r, above, 1 << 20), ep.run_search(r, above).alis, (), (knd, "above", above))
+
+
+def test_one_pair_pairs_capacity_one_short(pool_batch):
+    """Records enough, pairs_capacity one pair short of the kept lists: ALN_E_OVERFLOW from the host's assembly, behind the
+    release of the device pools; the same call with the full capacity gives the oracle's set."""
+    b, r, p = pool_batch, ep.SMALL["cw"], 0
+    want = ep.run_search(r, p).alis
+    total = sum(len(w["pairs"]) for w in want)
+    rc, n, recs, pairs = _one_pair(b, r, p, 1 << 20, pairs_capacity=total - 1)
+    assert rc == aln_amd.E_OVERFLOW and n == len(want), (rc, n, len(want))
+    _check_records(*_one_pair(b, r, p, 1 << 20, pairs_capacity=total), want, (), ("cw", "capacity", total))
 
 
 # ---- 3. kept pools and launch order ------------------------------------------------------------------------------------------------
