@@ -85,6 +85,13 @@ class AlnHitAlignment(C.Structure):
 
 HIT_ALIGNMENT_DTYPE = np.dtype([("n_pairs", np.int32), ("status", np.int32), ("score", np.float32), ("identity", np.float32)])
 
+
+class AlnHitSpan(C.Structure):
+    _fields_ = [("q_lo", C.c_int32), ("q_hi", C.c_int32), ("t_lo", C.c_int32), ("t_hi", C.c_int32)]
+
+
+HIT_SPAN_DTYPE = np.dtype([("q_lo", np.int32), ("q_hi", np.int32), ("t_lo", np.int32), ("t_hi", np.int32)])
+
 EXPORTS = [
     "aln_ctx_create", "aln_ctx_destroy", "aln_error_string", "aln_last_error", "aln_ctx_synchronize", "aln_has_gfx950",
     "aln_batch_create", "aln_batch_destroy", "aln_batch_n_pairs", "aln_batch_device_bytes", "aln_batch_dp",
@@ -97,6 +104,7 @@ EXPORTS = [
     "aln_hits_zscores", "aln_hits_align", "aln_hits_align_last_routes", "aln_score_profiles_vs_all", "aln_search_topk_profiles",
     "aln_hits_align_profiles", "aln_hits_zscores_profiles", "aln_hits_align_multi",
     "aln_hits_align_multi_profiles", "aln_hits_column_counts", "aln_hits_column_counts_profiles",
+    "aln_hits_pileup", "aln_hits_pileup_profiles",
 ]
 COMM_ID_BYTES = 128
 
@@ -192,6 +200,13 @@ def lib():
         L.aln_hits_column_counts_profiles.argtypes = [C.c_void_p, C.POINTER(AlnQProfiles), C.POINTER(AlnSeqs), C.POINTER(AlnSeqs),
                                                       C.POINTER(AlnGap), C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, _ip,
                                                       C.POINTER(AlnHitAlignment), _ip, _ip]
+        L.aln_hits_pileup.argtypes = [C.c_void_p, C.POINTER(AlnSeqs), C.POINTER(AlnSeqs), C.POINTER(AlnSubmatrix), C.POINTER(AlnGap),
+                                      C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.POINTER(AlnHitAlignment),
+                                      C.POINTER(AlnHitSpan), C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), C.c_int32]
+        L.aln_hits_pileup_profiles.argtypes = [C.c_void_p, C.POINTER(AlnQProfiles), C.POINTER(AlnSeqs), C.POINTER(AlnSeqs),
+                                               C.POINTER(AlnGap), C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip,
+                                               C.POINTER(AlnHitAlignment), C.POINTER(AlnHitSpan), C.POINTER(C.c_uint8),
+                                               C.POINTER(C.c_uint16), C.c_int32]
         L.aln_hits_align_last_routes.argtypes = [C.c_void_p, _lp]
         L.aln_hmap2_gap_arrays.argtypes = [_fp, C.c_int64, C.c_float, C.c_float, C.c_float, _fp, _fp]
         L.aln_batch_plane_bytes_per_cell.argtypes = [C.c_void_p]
@@ -700,6 +715,80 @@ def hits_column_counts_profiles(ctx, profiles, templates, hits, n_hits, gi, ge, 
     -> the 4-tuple of hits_column_counts."""
     return _counts(ctx, _ProfileSide("aln_hits_column_counts_profiles", profiles, templates, consensus), hits, n_hits, gi, ge, weights,
                    q_begin, align_type, want_covered)
+
+
+def _pileup(ctx, side, hits, n_hits, gi, ge, q_begin, align_type, want_letters, want_tpos, want_spans, line_stride):
+    hits, n_hits, rows, K = _hit_list(hits, n_hits)
+    if line_stride is None:
+        line_stride = max(int(np.diff(side.offsets[q_begin:q_begin + rows + 1]).max(initial=2)) - 2, 1)
+    stride = max(int(line_stride), 0)
+    rec = np.zeros((rows, K), dtype=HIT_ALIGNMENT_DTYPE)
+    spans = np.zeros((rows, K), dtype=HIT_SPAN_DTYPE) if want_spans else None
+    letters = np.zeros((rows, K, stride), dtype=np.uint8) if want_letters else None
+    tpos = np.zeros((rows, K, stride), dtype=np.uint16) if want_tpos else None
+    rc = side.call(ctx, _const_gap(align_type, gi, ge), q_begin, q_begin + rows, int(K), _as(hits, AlnHit), _i(n_hits),
+                   _as(rec, AlnHitAlignment), _as(spans, AlnHitSpan) if want_spans else None,
+                   letters.ctypes.data_as(C.POINTER(C.c_uint8)) if want_letters else None,
+                   tpos.ctypes.data_as(C.POINTER(C.c_uint16)) if want_tpos else None, int(line_stride))
+    if rc != 0 and not (rec["status"] == rc).any():
+        _check(rc, ctx.h)
+    return rec, spans, letters, tpos, rc
+
+
+def hits_pileup(ctx, queries, templates, hits, n_hits, alphabet, table, gi, ge, q_begin=0, align_type=LOCAL, want_letters=True,
+                want_tpos=True, want_spans=True, line_stride=None):
+    """aln_hits_pileup: the query-anchored stack of the alignments hits_align reports for the used slots of hits[rows, K], laid
+    out on the device — one row per slot whose index p is query position p + 1: the template's letter aligned to it, '-' where
+    the alignment passes the position opposite a gap, '.' outside the aligned range and in slots that do not contribute (status
+    != 0; local score <= 0), NUL beyond the query and in unused slots; tpos holds the template position (0: none).
+    line_stride: None = the longest query of the block (at least 1).  -> rec[rows, K] (hits_align's records without lists),
+    spans[rows, K] (fields q_lo, q_hi, t_lo, t_hi; zero where nothing is aligned; or None), letters uint8 [rows, K, stride] (or
+    None), tpos uint16 [rows, K, stride] (or None), rc (0, or the lowest per-slot status).  Raises only when the call wrote
+    nothing."""
+    return _pileup(ctx, _ResidueSide("aln_hits_pileup", queries, templates, alphabet, table), hits, n_hits, gi, ge, q_begin, align_type,
+                   want_letters, want_tpos, want_spans, line_stride)
+
+
+def hits_pileup_profiles(ctx, profiles, templates, hits, n_hits, gi, ge, consensus=None, q_begin=0, align_type=LOCAL,
+                         want_letters=True, want_tpos=True, want_spans=True, line_stride=None):
+    """aln_hits_pileup_profiles: hits_pileup for the hits of a profile search (profiles: a QueryProfiles; consensus as in
+    hits_align_profiles — it only enters the records' identity).  -> the 5-tuple of hits_pileup."""
+    return _pileup(ctx, _ProfileSide("aln_hits_pileup_profiles", profiles, templates, consensus), hits, n_hits, gi, ge, q_begin,
+                   align_type, want_letters, want_tpos, want_spans, line_stride)
+
+
+def counts_from_pileup(letters_row, alphabet, weights=None):
+    """The tally of hits_column_counts restated over a pileup, pure numpy.  letters_row: [K, L] letters of one query (one row of
+    hits_pileup's letters; L = its residues or more); weights: None (every slot 1) or K integers.
+    -> (counts int64 [L, n]: per position how often each letter of `alphabet` stands there, covered int64 [L]: the weighted
+    slots whose aligned range spans the position, aligned or '-')."""
+    rows = np.asarray(letters_row, dtype=np.uint8)
+    assert rows.ndim == 2
+    w = np.ones(rows.shape[0], np.int64) if weights is None else np.asarray(weights, np.int64).reshape(rows.shape[0])
+    counts = np.zeros((rows.shape[1], len(alphabet)), np.int64)
+    for a, ch in enumerate(alphabet):
+        counts[:, a] = ((rows == ord(ch)) * w[:, None]).sum(axis=0)
+    covered = (((rows != ord(".")) & (rows != 0)) * w[:, None]).sum(axis=0)
+    return counts, covered
+
+
+def a3m_from_pileup(template, letters_line, tpos_line):
+    """One a3m row of a slot, pure numpy.  template: the hit's residues WITHOUT sentinels (position j is template[j - 1]);
+    letters_line / tpos_line: the slot's L = Q - 2 entries of hits_pileup's letters and tpos.  Per query position the letter
+    ('.' written as '-'); after an aligned position (i, j) whose next aligned position is (i', j') with j' > j + 1 the template
+    residues j + 1 .. j' - 1 in lower case.  Template residues before t_lo and after t_hi do not appear.  -> str"""
+    letters = np.asarray(letters_line, dtype=np.uint8)
+    tpos = np.asarray(tpos_line, dtype=np.int64)
+    aligned = np.nonzero(tpos > 0)[0]
+    nxt = {int(p): int(tpos[n]) for p, n in zip(aligned[:-1], aligned[1:])}
+    out = []
+    for p in range(len(letters)):
+        ch = chr(int(letters[p]))
+        out.append("-" if ch == "." else ch)
+        j = int(tpos[p])
+        if p in nxt and nxt[p] > j + 1:
+            out.append(template[j:nxt[p] - 1].lower())
+    return "".join(out)
 
 
 def pssm_from_counts(counts, background, fallback_rows, pseudo=1.0, scale=2.0):

@@ -39,7 +39,7 @@ struct ScoreArgs {
 //                 its wave ends, and such a query has no letters of its own (the identity is counted over characters)
 //   letters()     of a pool's codes and its characters, the one an alignment's identity is counted over (search_align.hip)
 //   kFusedLocal / kFusedGlobal   bit R set: class R runs in hit_local_kernel<R> / hit_global_kernel<R> (search_align.h), under
-//                 ListJob (search_align.hip) and under CountJob (search_counts.hip)
+//                 ListJob (search_align.hip), CountJob (search_counts.hip) and PileupJob (search_pileup.hip)
 //   kFusedMulti   bit R set: class R runs in align_local_multi_kernel<R> (search_align_multi.hip)
 // The row arrays never leave the kernel and the sweeps' text does not change with the side.
 struct ResidueQuery {

@@ -1,7 +1,8 @@
 // search_align.h — what the fused hit-alignment entries share.  Device: how a hit is described to a kernel (HitDesc), the two
 // observers that turn a row sweep into the strip bytes and the final cell's pointer, strip_walk, the walk back through the
 // strip, and the ONE pair of kernels around them, hit_local_kernel / hit_global_kernel<R, Side, Job>: what becomes of a walk
-// entry is the job's — ListJob here (search_align.hip: the pair list), CountJob in search_counts.hip (the column counts).
+// entry is the job's — ListJob here (search_align.hip: the pair list), CountJob in search_counts.hip (the column counts),
+// PileupJob in search_pileup.hip (the query-anchored rows).
 // search_align_multi.hip (several rounds per hit) has a kernel of its own around the same walk.  Host: where a slot's record,
 // list and lines go (AlignOut, put_fused, pair_desc), the routing of slots (route_slots) and the fused route's driver that
 // the three entries run their chunks through (FusedRoute, over score_common.h's DeviceBufs, STRY / RTRY and launch_classes).

@@ -1,0 +1,335 @@
+// search_pileup.hip — the query-anchored pileup of search hits, on the device: aln_hits_pileup (gfx950).
+//
+// What is read off a search round — sequence weights, purging, gap statistics, a consensus, the MSA handed on — wants one
+// fixed-width row per hit whose column is the query position: the template residue aligned to it, or a gap.  The list of a hit
+// is 8 B per entry and has to be scattered on the host; the row is 1 B (letters) + 2 B (template positions) per query position
+// and needs nothing further.  So the two kernels of search_align.h are instantiated here with a third job behind the same sweep
+// and walk:
+//   hit_local_kernel<R, Side, PileupJob>    sweep_local + StripObserver<true> + the score check + strip_walk;
+//   hit_global_kernel<R, Side, PileupJob>   sweep_global + GlobalObserver + final_cell + strip_walk.
+// One wave per hit.  The job's sink counts `same` for the identity (the record is aln_hits_align's), and for an interior entry
+// (q, t) stores t as 2 bytes into the hit's tpos row and the template's CHARACTER as 1 byte into its letters row, both at index
+// q - 1, each only where that output is wanted, and keeps the lane's smallest and largest interior q with the t that belongs to
+// each.  After the walk the wave reduces the two bounds, writes the span, and turns every position of i_lo .. i_hi that no entry
+// wrote into '-', 64 positions per step.
+//
+// Where the bytes come from.  The rows of a chunk live in two device buffers of `stride` = the block's longest Q - 2 entries per
+// hit.  Before every launch the host memsets the chunk's letters to '.', its tpos and its spans to 0 — in the stream's order, so
+// a kernel never meets what an earlier chunk or call left — and the kernels only ever overwrite: a slot that is muted (below),
+// a local slot that is refused before the walk and every position outside i_lo .. i_hi keep '.' / 0 / {0,0,0,0} as the definition
+// wants them.  The host copies Q - 2 entries per slot into the caller's arrays, which it has zeroed in full: that is the padding.
+//
+// Ordering of the gap pass.  It reads letters bytes that OTHER lanes of the wave stored during the walk (a diagonal run is
+// stored by up to 64 lanes, a jump's entry by lane 0).  Between the last of those stores and the first of those loads stand
+// __threadfence(); __syncthreads(); — the pair the kernels place between the sweep's strip stores and the walk.  The fence is a
+// sequentially consistent fence at agent scope: every lane's stores have left for L2 before it completes and the vector L1 is
+// invalidated after it, so a line that another wave of the CU pulled in earlier (rows of two hits may share a cache line: the
+// stride is not padded) is not read stale; the barrier keeps any lane from loading before every lane has passed its fence.  The
+// block is one wave and finish() is called by every lane under wave-uniform conditions, so the barrier is reached by all 64.
+// The '.' the pass tests for was written by the memset, an earlier operation of the stream.  ('.' is taken not to be a letter of
+// the templates' alphabet: a pileup could not show it.)
+//
+// The character pool.  `Letters` of the residue side are codes, so the pool is not among the sink's constructor arguments: it
+// rides behind the job's Args (PileupRows; FusedRoute::upload_pools() puts the pool on the device for both sides) and the hit's
+// offset into it is toff[desc[hit].t], the offset of the codes.  The kernels' signatures are untouched.
+// A slot that must not contribute but needs its record — a local score <= 0, the seed cell's list — is muted by a per-hit flag
+// from the host (live == 0), as CountJob is muted by weight 0: its sink counts `same` and stores nothing.  A local slot whose
+// sweep score differs from .score returns before the walk.  Everything the kernels do not take goes through
+// align_through_batches (search_align.hip) with pair lists wanted, from which the host fills the same outputs.
+#include <algorithm>
+#include <climits>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "search_align.h"
+
+namespace aln {
+
+// Where the rows of a chunk's hits go: the same for every chunk of a call, so it lies on the device once and the kernels'
+// argument block carries one pointer to it — the sink reads it after the sweep, and nothing of it is held across the sweep.
+struct PileupRows {
+  const int32_t* live;      // per hit of the chunk; 0: the record only
+  const char* pool;         // the templates' characters (read only where letters are wanted)
+  char* letters;            // hit h's row at letters + h * stride, preset to '.' (nullptr: not wanted)
+  uint16_t* tpos;           // ... at tpos + h * stride, preset to 0 (nullptr: not wanted)
+  aln_hit_span* spans;      // one per hit of the chunk, preset to zero (nullptr: not wanted)
+  int64_t stride;
+};
+
+struct PileupArgs {
+  const int32_t* list;      // blockIdx.x -> hit of the chunk
+  const HitDesc* desc;
+  uint8_t* strip;
+  const PileupRows* rows;
+  PairResult* res;          // best = score, n_path, status
+  int32_t* same;
+};
+
+// The job that piles up.  What strip_walk's entries become: the identity's count, two stores, the lane's bounds.
+struct PileupJob {
+  typedef PileupArgs Args;
+  template <class Letters>
+  struct Sink {
+    Letters qs, ts;                         // what the identity is counted over
+    const char* tch;                        // the template's characters
+    char* lrow; uint16_t* prow;             // the hit's two rows (index q - 1)
+    aln_hit_span* span;
+    int Q, T, live;
+    int same = 0, lo = INT_MAX, lo_t = 0, hi = -1, hi_t = 0;
+    __device__ __forceinline__ Sink(const Args& g, const ScoreArgs& a, int hit, int, Letters qs_, Letters ts_, const uint8_t*, int Q_,
+                                    int T_)
+        : qs(qs_), ts(ts_), Q(Q_), T(T_) {
+      const PileupRows o = *g.rows;
+      tch = o.pool + a.toff[g.desc[hit].t];
+      lrow = o.letters ? o.letters + (size_t)hit * o.stride : nullptr;
+      prow = o.tpos ? o.tpos + (size_t)hit * o.stride : nullptr;
+      span = o.spans ? o.spans + hit : nullptr;
+      live = o.live[hit];
+    }
+    __device__ __forceinline__ void operator()(int, int q, int t) {
+      same += (qs[q] == ts[t]) ? 1 : 0;
+      if (live && q >= 1 && q <= Q - 2 && t >= 1 && t <= T - 2) {
+        if (q < lo) { lo = q; lo_t = t; }
+        if (q > hi) { hi = q; hi_t = t; }
+        if (prow) prow[q - 1] = (uint16_t)t;
+        if (lrow) lrow[q - 1] = tch[t];
+      }
+    }
+    // after the walk: same summed, the span, '-' over the unwritten positions of i_lo .. i_hi (every lane calls it)
+    __device__ __forceinline__ void finish() {
+      const int mylo = lo, myhi = hi;
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) {
+        same += __shfl_xor(same, off);
+        lo = min(lo, __shfl_xor(lo, off));
+        hi = max(hi, __shfl_xor(hi, off));
+      }
+      if (hi < 0) return;                   // muted, or no interior entry: '.', 0 and the zero span stand (wave-uniform)
+      // a query position occurs once in a list, so one lane owns each bound
+      lo_t = __shfl(lo_t, __builtin_ctzll(__ballot(mylo == lo)));
+      hi_t = __shfl(hi_t, __builtin_ctzll(__ballot(myhi == hi)));
+      if (span && threadIdx.x == 0) *span = aln_hit_span{lo, hi, lo_t, hi_t};
+      if (lrow) {
+        __threadfence();                    // the walk's stores of every lane are visible to every lane (head of the file)
+        __syncthreads();
+        for (int i = lo + (int)threadIdx.x; i <= hi; i += 64)
+          if (lrow[i - 1] == '.') lrow[i - 1] = '-';
+      }
+    }
+    __device__ __forceinline__ int status(int) const { return 0; }
+  };
+};
+
+// One slot's rows from its pair list, on the host: the definition of include/aln_hip.h restated (the batch route).  lrow / prow:
+// the slot's rows, already '.' / 0 over p < Q - 2; span: already zero.
+static void pileup_from_list(const int32_t* l, int n, int64_t Q, int64_t T, const char* tres, char* lrow, uint16_t* prow,
+                             aln_hit_span* span) {
+  int64_t lo = INT64_MAX, hi = -1, lo_t = 0, hi_t = 0;
+  for (int k = 0; k < n; ++k) {
+    const int64_t i = l[2 * k], j = l[2 * k + 1];
+    if (i < 1 || i > Q - 2 || j < 1 || j > T - 2) continue;
+    if (i < lo) { lo = i; lo_t = j; }
+    if (i > hi) { hi = i; hi_t = j; }
+    if (prow) prow[i - 1] = (uint16_t)j;
+    if (lrow) lrow[i - 1] = tres[j];
+  }
+  if (hi < 0) return;
+  if (span) *span = aln_hit_span{(int32_t)lo, (int32_t)hi, (int32_t)lo_t, (int32_t)hi_t};
+  if (lrow)
+    for (int64_t i = lo; i <= hi; ++i)
+      if (lrow[i - 1] == '.') lrow[i - 1] = '-';
+}
+
+// The shared body of aln_hits_pileup and aln_hits_pileup_profiles (run: prepared; `queries`: the pool the query lengths are
+// read from, as in count_block): the stride check, the slot checks, the routes, the chunks of fused hits, the batches.
+static int pileup_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const aln_hit* hits, const int32_t* n_hits,
+                        aln_hit_alignment* out, aln_hit_span* spans, char* letters, uint16_t* tpos, int32_t line_stride) {
+  aln_ctx* ctx = run.ctx;
+  const aln_seqs* templates = run.templates;
+  const aln_qprofiles* prof = run.prof;
+  const int rows = run.rows;
+  if (rows == 0) return ALN_OK;
+  const bool want_rows = letters || tpos;
+  int64_t maxw = 0;                                          // the longest Q - 2 of the block
+  for (int q = run.q_begin; q < run.q_end; ++q) maxw = std::max<int64_t>(maxw, queries->offsets[q + 1] - queries->offsets[q] - 2);
+  if (want_rows && line_stride < maxw) return ALN_E_ARG;
+  maxw = std::max<int64_t>(maxw, 1);                         // ... which is the device rows' stride
+
+  // align_block's walk (every used slot validated and described for its route); nothing written before
+  SlotRoutes sr;
+  int rc = route_slots(run, queries, K, hits, n_hits, hit_kernel_classes(run), run.local, sr);
+  if (rc != ALN_OK) return rc;
+  std::vector<HitDesc>& fast = sr.fast;
+  const std::vector<size_t>& fast_slot = sr.fast_slot;
+  const std::vector<int32_t>&bq = sr.bq, &bt = sr.bt;
+  const std::vector<size_t>& bslot = sr.bslot;
+  ctx->align_routes[0] = (int64_t)fast.size(); ctx->align_routes[1] = (int64_t)bq.size();
+
+  // the outputs in full: zero everywhere, then '.' over the Q - 2 positions of every used slot
+  const size_t n_slots = (size_t)rows * K, ls = want_rows ? (size_t)line_stride : 0;
+  if (letters) memset(letters, 0, n_slots * ls);
+  if (tpos) memset(tpos, 0, n_slots * ls * 2);
+  if (spans) memset(spans, 0, n_slots * sizeof(aln_hit_span));
+  for (int r = 0; r < rows; ++r) {
+    const int64_t w = queries->offsets[run.q_begin + r + 1] - queries->offsets[run.q_begin + r] - 2;
+    for (int k = 0; k < K; ++k) {
+      const size_t slot = (size_t)r * K + k;
+      if (k >= n_hits[r]) out[slot] = aln_hit_alignment{0, 0, 0.0f, 0.0f};
+      else if (letters && w > 0) memset(letters + slot * ls, '.', (size_t)w);
+    }
+  }
+  AlignOut ao = {out, nullptr, 0, nullptr, nullptr, 0, nullptr};
+
+  // chunks of fused hits.  cut() is asked for one "pair of lines" of maxw bytes per hit, which is the 2 maxw bytes of a tpos row
+  // (the letters row is half of that), and for lists of no entries: strips and each row buffer stay below the budget.
+  if (!fast.empty()) {
+    FusedRoute<HitDesc> fr(run, queries, fast);
+    std::vector<int32_t> fast_live(fast.size());
+    for (size_t h = 0; h < fast.size(); ++h) fast_live[h] = (run.local && !(fast[h].score > 0.f)) ? 0 : 1;
+    fr.cut(1, want_rows, (int)std::min<int64_t>(maxw, INT_MAX), [&](const HitDesc& d) {
+      const int srows = run.local ? d.q_end - 1 : (int)(queries->offsets[d.q + 1] - queries->offsets[d.q]) - 3;
+      return HitNeed{(size_t)std::max(srows, 1) * 256 * (size_t)d.cls, 0, 0};
+    });
+    const size_t max_n = fr.max_n, dw = (size_t)maxw;
+    int32_t *dlive = nullptr, *dsame = nullptr; PairResult* dres = nullptr;
+    char* dlet = nullptr; uint16_t* dpos = nullptr; aln_hit_span* dspan = nullptr; PileupRows* drows = nullptr;
+    RTRY(fr.begin());
+    STRY(fr.bufs.get(dlive, max_n));
+    STRY(fr.bufs.get(dsame, max_n));
+    STRY(fr.bufs.get(dres, max_n));
+    if (letters) STRY(fr.bufs.get(dlet, max_n * dw));
+    if (tpos) STRY(fr.bufs.get(dpos, max_n * dw));
+    if (spans) STRY(fr.bufs.get(dspan, max_n));
+    STRY(fr.bufs.get(drows, 1));
+    std::vector<PairResult> hres(max_n);
+    std::vector<int32_t> hsame(max_n);
+    std::vector<char> hlet(letters ? max_n * dw : 0);
+    std::vector<uint16_t> hpos(tpos ? max_n * dw : 0);
+    std::vector<aln_hit_span> hspan(spans ? max_n : 0);
+    RTRY(fr.upload_pools());                                   // the templates' characters, on both sides
+    const PileupRows where = {dlive, fr.dtch, dlet, dpos, dspan, (int64_t)dw};   // (alive until the first chunk's synchronisation)
+    STRY(hipMemcpyAsync(drows, &where, sizeof(where), hipMemcpyHostToDevice, ctx->stream));
+    for (const FusedChunk& c : fr.chunks) {
+      const size_t n = c.n;
+      RTRY(fr.stage(c, [&]() -> int {
+        STRY(hipMemcpyAsync(dlive, fast_live.data() + c.h0, n * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (dlet) STRY(hipMemsetAsync(dlet, '.', n * dw, ctx->stream));
+        if (dpos) STRY(hipMemsetAsync(dpos, 0, n * dw * 2, ctx->stream));
+        if (dspan) STRY(hipMemsetAsync(dspan, 0, n * sizeof(aln_hit_span), ctx->stream));
+        return ALN_OK;
+      }));
+      PileupArgs g = {};
+      g.desc = fr.ddesc; g.strip = fr.dstrip; g.rows = drows; g.res = dres; g.same = dsame;
+      RTRY(fr.launch(c, [&](auto side, int k, int cnt, const int32_t* list, const char* qch, const char* tch) {
+        typedef decltype(side) Side;
+        const dim3 grid(cnt), block(64);
+        g.list = list;
+        constexpr int kLocalMax = ((Side::kFusedLocal >> 8) & 1u) ? 8 : 7;   // a class the mask leaves out never gets here
+        if (run.local)
+          dispatch_r<kLocalMax>(k, [&](auto rc) {
+            hipLaunchKernelGGL((hit_local_kernel<decltype(rc)::value, Side, PileupJob>), grid, block, 0, ctx->stream, run.a, g, qch, tch);
+          });
+        else
+          dispatch_r<8>(k, [&](auto rc) {
+            hipLaunchKernelGGL((hit_global_kernel<decltype(rc)::value, Side, PileupJob>), grid, block, 0, ctx->stream, run.a, g, qch, tch,
+                               run.free_del, run.free_ins);
+          });
+      }));
+      STRY(hipMemcpyAsync(hres.data(), dres, n * sizeof(PairResult), hipMemcpyDeviceToHost, ctx->stream));
+      STRY(hipMemcpyAsync(hsame.data(), dsame, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+      if (dlet) STRY(hipMemcpyAsync(hlet.data(), dlet, n * dw, hipMemcpyDeviceToHost, ctx->stream));
+      if (dpos) STRY(hipMemcpyAsync(hpos.data(), dpos, n * dw * 2, hipMemcpyDeviceToHost, ctx->stream));
+      if (dspan) STRY(hipMemcpyAsync(hspan.data(), dspan, n * sizeof(aln_hit_span), hipMemcpyDeviceToHost, ctx->stream));
+      STRY(hipStreamSynchronize(ctx->stream));                 // the host vectors above are read by the copies until here
+      for (size_t h = 0; h < n; ++h) {
+        const HitDesc& d = fast[c.h0 + h];
+        const size_t slot = fast_slot[c.h0 + h];
+        const int64_t Q = queries->offsets[d.q + 1] - queries->offsets[d.q], T = templates->offsets[d.t + 1] - templates->offsets[d.t];
+        put_fused(ao, slot, hres[h], hsame[h], Q, T, nullptr, nullptr, nullptr, 0);
+        if (letters) memcpy(letters + slot * ls, hlet.data() + h * dw, (size_t)(Q - 2));
+        if (tpos) memcpy(tpos + slot * ls, hpos.data() + h * dw, (size_t)(Q - 2) * 2);
+        if (spans) spans[slot] = hspan[h];
+      }
+    }
+  }
+
+  // the batch route, a group of slots at a time: records and pair lists into buffers of the group, laid out here
+  if (!bq.empty()) {
+    constexpr size_t kGroupBytes = (size_t)256 << 20;        // of pair lists on the host at a time
+    std::vector<aln_hit_alignment> grec;
+    std::vector<int32_t> gpairs, gq, gt;
+    std::vector<size_t> gslot;
+    for (size_t b0 = 0; b0 < bq.size();) {
+      size_t b1 = b0; int64_t stride = 4;
+      while (b1 < bq.size()) {
+        const int64_t Q = queries->offsets[bq[b1] + 1] - queries->offsets[bq[b1]];
+        const int64_t T = templates->offsets[bt[b1] + 1] - templates->offsets[bt[b1]];
+        const int64_t s = std::max(stride, std::min(Q, T) + 3);
+        if (b1 > b0 && (b1 + 1 - b0) * (size_t)s * 8 > kGroupBytes) break;
+        stride = s; ++b1;
+      }
+      const size_t nb = b1 - b0;
+      grec.assign(nb, aln_hit_alignment{0, 0, 0.0f, 0.0f});
+      gpairs.assign(nb * (size_t)stride * 2, 0);
+      gq.assign(bq.begin() + b0, bq.begin() + b1); gt.assign(bt.begin() + b0, bt.begin() + b1);
+      gslot.resize(nb);
+      for (size_t p = 0; p < nb; ++p) gslot[p] = p;
+      AlignOut go = {grec.data(), gpairs.data(), (int32_t)stride, nullptr, nullptr, 0, nullptr};
+      rc = align_through_batches(ctx, queries, templates, run.sub, prof, run.gap, gq, gt, gslot, go);
+      if (rc != ALN_OK) return rc;
+      for (size_t p = 0; p < nb; ++p) {
+        const size_t slot = bslot[b0 + p];
+        const aln_hit_alignment& rec = grec[p];
+        out[slot] = rec;
+        ao.note(rec.status);
+        if (rec.status != 0 || (run.local && !(rec.score > 0.f))) continue;
+        const int64_t Q = queries->offsets[gq[p] + 1] - queries->offsets[gq[p]];
+        const int64_t to = templates->offsets[gt[p]], T = templates->offsets[gt[p] + 1] - to;
+        pileup_from_list(gpairs.data() + p * (size_t)stride * 2, rec.n_pairs, Q, T, templates->residues + to,
+                         letters ? letters + slot * ls : nullptr, tpos ? tpos + slot * ls : nullptr, spans ? spans + slot : nullptr);
+      }
+      b0 = b1;
+    }
+  }
+  return ao.worst;
+}
+
+static bool pileup_outputs_ok(int32_t K, const aln_hit* hits, const int32_t* n_hits, const aln_hit_alignment* out, const char* letters,
+                              const uint16_t* tpos, int32_t line_stride) {
+  if (!hits || !n_hits || !out || K < 1 || K > 1024) return false;
+  return !((letters || tpos) && line_stride < 1);
+}
+
+}  // namespace aln
+
+using namespace aln;
+
+extern "C" int aln_hits_pileup(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
+                               const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K, const aln_hit* hits,
+                               const int32_t* n_hits, aln_hit_alignment* out, aln_hit_span* spans, char* letters, uint16_t* tpos,
+                               int32_t line_stride) {
+  if (ctx) ctx->align_routes[0] = ctx->align_routes[1] = 0;
+  if (!pileup_outputs_ok(K, hits, n_hits, out, letters, tpos, line_stride)) return ALN_E_ARG;
+  ScoreRun run;
+  int rc = run.prepare(ctx, queries, templates, sub, gap, q_begin, q_end);
+  if (rc != ALN_OK) return rc;
+  return pileup_block(run, run.queries, K, hits, n_hits, out, spans, letters, tpos, line_stride);
+}
+
+extern "C" int aln_hits_pileup_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_seqs* consensus,
+                                        const aln_seqs* templates, const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K,
+                                        const aln_hit* hits, const int32_t* n_hits, aln_hit_alignment* out, aln_hit_span* spans,
+                                        char* letters, uint16_t* tpos, int32_t line_stride) {
+  if (ctx) ctx->align_routes[0] = ctx->align_routes[1] = 0;
+  if (!profiles || !templates || !gap) return ALN_E_ARG;
+  if (!pileup_outputs_ok(K, hits, n_hits, out, letters, tpos, line_stride)) return ALN_E_ARG;
+  ScoreRun run;
+  run.consensus = consensus;
+  int rc = run.prepare(ctx, nullptr, templates, nullptr, gap, q_begin, q_end, profiles);
+  if (rc != ALN_OK) return rc;
+  return pileup_block(run, consensus ? consensus : run.queries, K, hits, n_hits, out, spans, letters, tpos, line_stride);
+}
+
+#undef STRY
+#undef RTRY

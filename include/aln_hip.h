@@ -606,6 +606,62 @@ int aln_hits_column_counts_profiles(aln_ctx* ctx, const aln_qprofiles* profiles,
                                     const aln_seqs* templates, const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K,
                                     const aln_hit* hits, const int32_t* n_hits, const int32_t* weights,
                                     aln_hit_alignment* out, int32_t* counts /* ... x profiles->n */, int32_t* covered);
+/* ---- the query-anchored pileup of search hits: one fixed-width row per hit, column = query position -------------------- */
+/* The a3m / pileup form of a search round: for every used slot one row whose index is the query position and whose entry is
+ * the template residue aligned to that position, or a gap — what per-hit weights, purging of near-identical hits, gap
+ * statistics, a consensus and the MSA handed to another tool are read off — and the aligned range of every hit, without a pair
+ * list leaving the device.
+ * The hit layout and which slots are used are aln_hits_align's (duplicates allowed).  The alignment of a slot is the pair list
+ * aln_hits_align reports for it: ALN_LOCAL trusts the slot's end cell (a sweep score that differs from .score gives the slot
+ * ALN_E_ARG, n_pairs 0, and the call goes on), the four other align types start at (Q-1, T-1).  out[s] is, byte for byte, the
+ * record aln_hits_align writes for the slot when called with pairs == NULL and no line group; unused slots hold { 0, 0, 0, 0 };
+ * ALN_E_OVERFLOW cannot occur.
+ * A slot CONTRIBUTES when its status is 0 and, ALN_LOCAL, its score is > 0 (aln_hits_column_counts' rule without the weights).
+ * With Q the residues of the row's query and T those of the template (sentinels counted), query position i (1 <= i <= Q-2)
+ * stands at index p = i - 1 of the slot's line: letters[s * line_stride + p], tpos[s * line_stride + p].  An INTERIOR ENTRY is
+ * a list entry (i, j) with 1 <= i <= Q-2 and 1 <= j <= T-2; i_lo / i_hi are the smallest / largest i of the slot's interior
+ * entries.  Then
+ *   a contributing slot with interior entry (i, j):   tpos = j, letters = templates->residues[offsets[t] + j] — the pool's own
+ *                                                     character, on both routes;
+ *   a contributing slot, no entry at i, i_lo < i < i_hi:   tpos = 0, letters = '-';
+ *   every other position p < Q-2 of a used slot:      tpos = 0, letters = '.' — outside [i_lo, i_hi], and every position of a
+ *                                                     slot that does not contribute;
+ *   indices Q-2 <= p < line_stride of a used slot and every index of an unused slot:   '\0' / 0.
+ * ('.' and '-' are taken not to be letters of the templates.)  spans[s] = { i_lo, i_hi, the j of i_lo, the j of i_hi } for a
+ * contributing slot with at least one interior entry, { 0, 0, 0, 0 } for every other slot; under ALN_LOCAL (q_lo, t_lo) is the
+ * start cell of the hit whose end cell is (q_end, t_end).  j <= T-2 <= 65532, so uint16_t holds every position.
+ * spans, letters and tpos are independent and each may be NULL; with all three NULL the call is aln_hits_align without lists
+ * and lines.  line_stride is read only when letters or tpos is given.
+ * The outputs are written in full by every successful call and depend on neither the chunking (hints "align_chunk_hits",
+ * "align_rows_per_chunk"), the launch order, the route nor hint "align_fused_nonlocal".
+ * Routes: those of aln_hits_align — one wave per hit sweeps as there, writes the 1 B/cell strip, walks back through it and per
+ * list entry issues one 2-byte store into the hit's tpos row and one 1-byte store into its letters row on the device
+ * (csrc/search_pileup.hip), then writes the span and the '-' of its range; per hit the 16-byte record, the span and Q-2 <=
+ * stride entries of each row come down, no list.  What those kernels do not take (longer templates, fractional scoring, pairs
+ * without an interior, ALN_LOCAL templates of 1793 .. 2048 columns, the non-local types under "align_fused_nonlocal" = 0) goes
+ * through resident batches whose pair lists the host lays out into the same outputs.  aln_hits_align_last_routes reports
+ * this call's slots too.
+ * Checks, in this order, nothing written when one fails: NULL hits / n_hits / out, K outside 1..1024, line_stride < 1 when
+ * letters or tpos is given (ALN_E_ARG); aln_score_all_vs_all's, in its order; line_stride < Q-2 for any query of
+ * [q_begin, q_end) when letters or tpos is given (ALN_E_ARG); every n_hits[r] in 0..K, every used slot's t in
+ * [0, n_templates) and, local, its end cell in range (ALN_E_ARG).
+ * q_begin == q_end: ALN_OK, nothing written.  Returns the lowest per-slot status, ALN_OK when all are 0. */
+typedef struct { int32_t q_lo, q_hi, t_lo, t_hi; } aln_hit_span;   /* 16 bytes; {0,0,0,0}: nothing aligned */
+int aln_hits_pileup(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
+                    const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K,
+                    const aln_hit* hits, const int32_t* n_hits,
+                    aln_hit_alignment* out /* rows x K */, aln_hit_span* spans /* rows x K, may be NULL */,
+                    char* letters /* rows x K x line_stride, may be NULL */,
+                    uint16_t* tpos /* rows x K x line_stride, may be NULL */, int32_t line_stride);
+/* The same for the hits of a profile search: the slots, records, routes and consensus pool are aln_hits_align_profiles' — the
+ * consensus only enters the records' identity —, spans, letters and tpos are those above, and the checks are NULL profiles /
+ * templates / gap, then NULL hits / n_hits / out, K and line_stride < 1; aln_score_profiles_vs_all's, in its order, with the
+ * consensus pool where aln_hits_align_profiles checks it; line_stride < Q-2; n_hits, t and the end cells.  For profiles derived
+ * from residue queries under an integral table every output is byte-identical to aln_hits_pileup's on those residues. */
+int aln_hits_pileup_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_seqs* consensus /* may be NULL */,
+                             const aln_seqs* templates, const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K,
+                             const aln_hit* hits, const int32_t* n_hits, aln_hit_alignment* out, aln_hit_span* spans,
+                             char* letters, uint16_t* tpos, int32_t line_stride);
 /* Several NON-INTERSECTING local alignments per hit (the second, third .. HSP of a hit; Waterman-Eggert's declumping restated on
  * the reference's recurrence).  ALN_LOCAL only.  For one pair — query of Q residues, template of T, sentinels counted — under a
  * table and constant affine gaps:
@@ -676,7 +732,7 @@ int aln_hits_align_multi_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, c
                                   int32_t max_alignments /* N, 1..16 */, float min_score /* -INFINITY: none */,
                                   int32_t* n_found /* rows x K */, aln_hit_alignment* out /* rows x K x N */,
                                   int32_t* pairs, int32_t pair_stride, char* tlines, char* qlines, int32_t line_stride, int32_t* lengths);
-/* out[0]: the used slots the last aln_hits_align / aln_hits_align_profiles / aln_hits_align_multi / aln_hits_align_multi_profiles / aln_hits_column_counts(_profiles) call on this context sent through a fused kernel,
+/* out[0]: the used slots the last aln_hits_align / aln_hits_align_profiles / aln_hits_align_multi / aln_hits_align_multi_profiles / aln_hits_column_counts(_profiles) / aln_hits_pileup(_profiles) call on this context sent through a fused kernel,
  * out[1]: through resident batches; { 0, 0 } before any call and after a call that failed its checks.  NULL argument: ALN_E_ARG. */
 int aln_hits_align_last_routes(const aln_ctx* ctx, int64_t out[2]);
 
