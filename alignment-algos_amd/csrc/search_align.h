@@ -5,7 +5,10 @@
 // PileupJob in search_pileup.hip (the query-anchored rows).
 // search_align_multi.hip (several rounds per hit) has a kernel of its own around the same walk.  Host: where a slot's record,
 // list and lines go (AlignOut, put_fused, pair_desc), the routing of slots (route_slots) and the fused route's driver that
-// the three entries run their chunks through (FusedRoute, over score_common.h's DeviceBufs, STRY / RTRY and launch_classes).
+// the four entries run their chunks through (FusedRoute, over score_common.h's DeviceBufs, STRY / RTRY and launch_classes).
+// Around the driver, what the entries over HitDesc share: a hit's strip bytes (hit_strip_bytes), the launch of the kernel pair
+// over a job (launch_hit_job), the owner of the per-hit records (HitRecords), the batch route of the jobs that read pair lists
+// on the host (for_list_groups) and what an extern "C" entry does before its body (hit_list_ok, hit_entry).
 // The strip byte is defined at the head of search_align.hip.  DESIGN 4.8 found that a helper which takes a kernel's ROW ARRAYS by reference costs
 // registers; the walk and the jobs run after the sweep on scalar state only, and sharing them costs none.
 #pragma once
@@ -320,6 +323,17 @@ struct AlignOut {
   aln_hit_alignment* out; int32_t* pairs; int32_t pair_stride; char* tlines; char* qlines; int32_t line_stride; int32_t* lengths;
   int worst = ALN_OK;
   void note(int st) { if (st < worst) worst = st; }
+  // a slot nothing is reported for: the zero record, empty lines
+  void clear(size_t slot) {
+    out[slot] = aln_hit_alignment{0, 0, 0.0f, 0.0f};
+    if (tlines) { tlines[slot * (size_t)line_stride] = 0; qlines[slot * (size_t)line_stride] = 0; }
+    if (lengths) lengths[slot] = 0;
+  }
+  // ... which the unused slots of a hit list are (n_hits[r] in 0 .. K: route_slots has checked it)
+  void clear_unused(int rows, int32_t K, const int32_t* n_hits) {
+    for (int r = 0; r < rows; ++r)
+      for (int k = n_hits[r]; k < K; ++k) clear((size_t)r * K + k);
+  }
   // list: n entries, reversed when flip; line: the slot's two lines of `len` chars (nullptr: none)
   void put(size_t slot, int status, float score, float identity, int n, const int32_t* list, bool flip, int len, const char* tl,
            const char* ql) {
@@ -418,17 +432,22 @@ int align_through_batches(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs*
                           const aln_qprofiles* prof, const aln_gap* gap, const std::vector<int32_t>& qi_all,
                           const std::vector<int32_t>& ti_all, const std::vector<size_t>& slot_all, AlignOut& ao);
 
-// the checks both entries make before ScoreRun's: the hit list, the record array, K, and the two optional output groups
+// the check every entry makes before ScoreRun's: the hit list, the record array, K
+inline bool hit_list_ok(int32_t K, const aln_hit* hits, const int32_t* n_hits, const aln_hit_alignment* out) {
+  return hits && n_hits && out && K >= 1 && K <= 1024;
+}
+// ... and with it the two optional output groups of the entries that list
 inline bool align_outputs_ok(int32_t K, const aln_hit* hits, const int32_t* n_hits, const aln_hit_alignment* out, const int32_t* pairs,
                              int32_t pair_stride, const char* tlines, const char* qlines, int32_t line_stride, const int32_t* lengths) {
-  if (!hits || !n_hits || !out || K < 1 || K > 1024) return false;
+  if (!hit_list_ok(K, hits, n_hits, out)) return false;
   if (pairs ? pair_stride < 2 : false) return false;
   const bool want_lines = tlines || qlines;
   if (want_lines ? (!tlines || !qlines || line_stride < 1) : lengths != nullptr) return false;
   return true;
 }
 
-// ---- the fused route's driver: what aln_hits_align, aln_hits_align_multi and aln_hits_column_counts run their chunks through ----
+// ---- the fused route's driver: what aln_hits_align, aln_hits_align_multi, aln_hits_column_counts and aln_hits_pileup run their
+// chunks through ----
 constexpr size_t kFusedBudget = (size_t)1 << 30;   // bytes of strips (of masks, of lists, of lines) resident at a time
 
 // (The error exits STRY / RTRY and the buffer owner DeviceBufs: score_common.h.)
@@ -528,5 +547,130 @@ struct FusedRoute {
     return ALN_OK;
   }
 };
+
+// ---- what the entries over HitDesc — aln_hits_align, aln_hits_column_counts, aln_hits_pileup — share around the driver ----
+
+// The strip of a fused hit (HitDesc::strip_off), for cut(): rows 2 .. q_end of a local sweep, rows 2 .. Q-2 of the others
+inline size_t hit_strip_bytes(const ScoreRun& run, const aln_seqs* queries, const HitDesc& d) {
+  const int rows = run.local ? d.q_end - 1 : (int)(queries->offsets[d.q + 1] - queries->offsets[d.q]) - 3;
+  return (size_t)std::max(rows, 1) * 256 * (size_t)d.cls;
+}
+
+// One chunk through the kernel pair over a job: per class present hit_local_kernel or hit_global_kernel<R, Side, Job>, by the
+// run's align type, over the class's part of the list (g.list is set here; the caller fills the rest of g).  A template the
+// caller's .hip file instantiates with its own job, so every compile unit emits its own kernels and no others.  Leaves as
+// FusedRoute::launch does: an error exit has synchronized the stream.
+template <class Job>
+int launch_hit_job(FusedRoute<HitDesc>& fr, const FusedChunk& c, typename Job::Args& g) {
+  ScoreRun& run = fr.run;
+  const hipStream_t stream = run.ctx->stream;
+  return fr.launch(c, [&](auto side, int k, int cnt, const int32_t* list, const char* qch, const char* tch) {
+    typedef decltype(side) Side;
+    const dim3 grid(cnt), block(64);
+    g.list = list;
+    constexpr int kLocalMax = ((Side::kFusedLocal >> 8) & 1u) ? 8 : 7;   // a class the mask leaves out never gets here
+    if (run.local)
+      dispatch_r<kLocalMax>(k, [&](auto rc) {
+        hipLaunchKernelGGL((hit_local_kernel<decltype(rc)::value, Side, Job>), grid, block, 0, stream, run.a, g, qch, tch);
+      });
+    else
+      dispatch_r<8>(k, [&](auto rc) {
+        hipLaunchKernelGGL((hit_global_kernel<decltype(rc)::value, Side, Job>), grid, block, 0, stream, run.a, g, qch, tch,
+                           run.free_del, run.free_ins);
+      });
+  });
+}
+
+// The records the kernels leave per hit (per hit and round: aln_hits_align_multi) — res and same of a job's Args — and their
+// host images.  The caller enqueues the download where it stands in its chunk and reads the images after its synchronization.
+struct HitRecords {
+  PairResult* dres = nullptr; int32_t* dsame = nullptr;
+  std::vector<PairResult> hres; std::vector<int32_t> hsame;
+  int alloc(DeviceBufs& bufs, size_t n) {
+    aln_ctx* ctx = bufs.run.ctx;
+    STRY(bufs.get(dsame, n));
+    STRY(bufs.get(dres, n));
+    hres.resize(n); hsame.resize(n);
+    return ALN_OK;
+  }
+  int enqueue_download(aln_ctx* ctx, size_t n) {
+    STRY(hipMemcpyAsync(hres.data(), dres, n * sizeof(PairResult), hipMemcpyDeviceToHost, ctx->stream));
+    STRY(hipMemcpyAsync(hsame.data(), dsame, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    return ALN_OK;
+  }
+  // A chunk's records into their slots, for a job without lists and lines; also(h, slot, Q): what else the caller files for
+  // hit h of the chunk
+  template <class Also>
+  void put(AlignOut& ao, const FusedRoute<HitDesc>& fr, const FusedChunk& c, const std::vector<size_t>& fast_slot, Also&& also) const {
+    const aln_seqs* queries = fr.queries; const aln_seqs* templates = fr.run.templates;
+    for (size_t h = 0; h < c.n; ++h) {
+      const HitDesc& d = fr.fast[c.h0 + h];
+      const int64_t Q = queries->offsets[d.q + 1] - queries->offsets[d.q], T = templates->offsets[d.t + 1] - templates->offsets[d.t];
+      put_fused(ao, fast_slot[c.h0 + h], hres[h], hsame[h], Q, T, nullptr, nullptr, nullptr, 0);
+      also(h, fast_slot[c.h0 + h], Q);
+    }
+  }
+};
+
+// The batch route of a job that reads pair lists on the host: the slots of sr.bq / bt / bslot go through
+// align_through_batches a group at a time, records and lists into buffers of the group — at most kListGroupBytes of lists,
+// and hint align_list_group_slots only asks for fewer slots —, the record is filed (ao.out, ao.note) and, unless the slot
+// failed or is a local one whose score is not > 0 (the seed cell's list), per_slot(slot, q, t, list, n_pairs) reads the list.
+constexpr size_t kListGroupBytes = (size_t)256 << 20;
+template <class PerSlot>
+int for_list_groups(ScoreRun& run, const aln_seqs* queries, const SlotRoutes& sr, AlignOut& ao, PerSlot&& per_slot) {
+  const aln_seqs* templates = run.templates;
+  const std::vector<int32_t>&bq = sr.bq, &bt = sr.bt;
+  const int hint = run.ctx->hints.align_list_group_slots;
+  const size_t forced = hint > 0 ? (size_t)hint : (size_t)-1;
+  std::vector<aln_hit_alignment> grec;
+  std::vector<int32_t> gpairs, gq, gt;
+  std::vector<size_t> gslot;
+  for (size_t b0 = 0, b1; b0 < bq.size(); b0 = b1) {
+    int64_t stride = 4;
+    for (b1 = b0; b1 < bq.size(); ++b1) {
+      const int64_t Q = queries->offsets[bq[b1] + 1] - queries->offsets[bq[b1]];
+      const int64_t T = templates->offsets[bt[b1] + 1] - templates->offsets[bt[b1]];
+      const int64_t s = std::max(stride, std::min(Q, T) + 3);
+      if (b1 > b0 && (b1 - b0 >= forced || (b1 + 1 - b0) * (size_t)s * 8 > kListGroupBytes)) break;
+      stride = s;
+    }
+    const size_t nb = b1 - b0;
+    grec.assign(nb, aln_hit_alignment{0, 0, 0.0f, 0.0f});
+    gpairs.assign(nb * (size_t)stride * 2, 0);
+    gq.assign(bq.begin() + b0, bq.begin() + b1); gt.assign(bt.begin() + b0, bt.begin() + b1);
+    gslot.resize(nb);
+    for (size_t p = 0; p < nb; ++p) gslot[p] = p;
+    AlignOut go = {grec.data(), gpairs.data(), (int32_t)stride, nullptr, nullptr, 0, nullptr};
+    const int rc = align_through_batches(run.ctx, queries, templates, run.sub, run.prof, run.gap, gq, gt, gslot, go);
+    if (rc != ALN_OK) return rc;
+    for (size_t p = 0; p < nb; ++p) {
+      const aln_hit_alignment& rec = grec[p];
+      ao.out[sr.bslot[b0 + p]] = rec;
+      ao.note(rec.status);
+      if (rec.status != 0 || (run.local && !(rec.score > 0.f))) continue;
+      per_slot(sr.bslot[b0 + p], gq[p], gt[p], gpairs.data() + p * (size_t)stride * 2, rec.n_pairs);
+    }
+  }
+  return ALN_OK;
+}
+
+// What an extern "C" entry of the family does before its body: align_routes reset; `ok`, the entry's own argument checks
+// (they write nothing and come before ScoreRun's); profile_form: the three pointers prepare() would otherwise read; the run
+// prepared in the residue form (queries, sub) or the profile form (profiles, consensus).  body(run, pool): pool is what
+// query letters and lengths are read from — run.queries, or the consensus pool of a profile run.
+template <class Body>
+int hit_entry(aln_ctx* ctx, bool profile_form, const aln_seqs* queries, const aln_qprofiles* profiles, const aln_seqs* consensus,
+              const aln_seqs* templates, const aln_submatrix* sub, const aln_gap* gap, int32_t q_begin, int32_t q_end, bool ok,
+              Body&& body) {
+  if (ctx) ctx->align_routes[0] = ctx->align_routes[1] = 0;
+  if (!ok || (profile_form && (!profiles || !templates || !gap))) return ALN_E_ARG;
+  ScoreRun run;
+  run.consensus = consensus;
+  const int rc = profile_form ? run.prepare(ctx, nullptr, templates, nullptr, gap, q_begin, q_end, profiles)
+                              : run.prepare(ctx, queries, templates, sub, gap, q_begin, q_end);
+  if (rc != ALN_OK) return rc;
+  return body(run, consensus ? consensus : run.queries);
+}
 
 }  // namespace aln

@@ -30,7 +30,8 @@
 // without an interior, a length class an instantiation was not kept for — goes through resident batches inside the call.
 // aln_hits_align_profiles is the same call for the hits of a profile search: the same host driver (align_block), the same two
 // kernels instantiated for the profile side, and batches built from the profiles' planes for what those do not take.
-// The chunks of fused hits run through FusedRoute (search_align.h), which aln_hits_align_multi and aln_hits_column_counts share.
+// The chunks of fused hits run through FusedRoute (search_align.h), which aln_hits_align_multi, aln_hits_column_counts and
+// aln_hits_pileup share; the entries' prologue (hit_entry) and the launch of the kernel pair (launch_hit_job) stand there too.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -43,7 +44,8 @@ namespace aln {
 // The batch route over the listed slots: aln_batch_create + aln_batch_dp + aln_batch_optimal / _strings, in the groups
 // BatchGroup (score_common.h) cuts under the plane budget.  prof != nullptr: `queries` holds the query
 // letters (the consensus pool or the placeholder), `sub` is not read and every batch is built from the planes of its own pairs
-// (BatchSim), which its budget counts.  (Declared in search_align.h: search_counts.hip tallies the lists of this route.)
+// (BatchSim), which its budget counts.  (Declared in search_align.h: for_list_groups there runs it for the jobs that read
+// their lists on the host.)
 int align_through_batches(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
                           const aln_qprofiles* prof, const aln_gap* gap, const std::vector<int32_t>& qi_all,
                           const std::vector<int32_t>& ti_all, const std::vector<size_t>& slot_all, AlignOut& ao) {
@@ -90,10 +92,7 @@ static int align_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
   int rc;
   const int rows = run.rows;
   if (rows == 0) return ALN_OK;
-  // a fused hit's strip rows and the most entries its list can have
-  auto strip_rows = [&](const HitDesc& d) {
-    return run.local ? d.q_end - 1 : (int)(queries->offsets[d.q + 1] - queries->offsets[d.q]) - 3;
-  };
+  // the most entries a fused hit's list can have
   auto list_cap = [&](const HitDesc& d) {
     if (run.local) return std::min(d.q_end, d.t_end) + 3;
     return (int)std::min(queries->offsets[d.q + 1] - queries->offsets[d.q], templates->offsets[d.t + 1] - templates->offsets[d.t]) + 1;
@@ -108,29 +107,21 @@ static int align_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
   const std::vector<size_t>& bslot = sr.bslot;
   ctx->align_routes[0] = (int64_t)fast.size(); ctx->align_routes[1] = (int64_t)bq.size();
   AlignOut ao = {out, pairs, pair_stride, tlines, qlines, line_stride, lengths};
-  for (int r = 0; r < rows; ++r)
-    for (int k = std::max(n_hits[r], 0); k < K; ++k) {
-      const size_t slot = (size_t)r * K + k;
-      const aln_hit_alignment zero = {0, 0, 0.0f, 0.0f};
-      out[slot] = zero;
-      if (tlines) { tlines[slot * (size_t)line_stride] = 0; qlines[slot * (size_t)line_stride] = 0; }
-      if (lengths) lengths[slot] = 0;
-    }
+  ao.clear_unused(rows, K, n_hits);
 
   // chunks of fused hits: one list each, and the two lines where wanted
   if (!fast.empty()) {
     FusedRoute<HitDesc> fr(run, queries, fast);
     fr.cut(1, want_lines, line_stride, [&](const HitDesc& d) {
-      return HitNeed{(size_t)std::max(strip_rows(d), 1) * 256 * (size_t)d.cls, 0, list_cap(d)};
+      return HitNeed{hit_strip_bytes(run, queries, d), 0, list_cap(d)};
     });
     const size_t max_n = fr.max_n, max_trav = fr.max_trav;
-    int32_t *dtrav = nullptr, *dsame = nullptr; PairResult* dres = nullptr; PairDesc* dpd = nullptr; StrOut* dso = nullptr; char* dlines = nullptr;
+    int32_t* dtrav = nullptr; PairDesc* dpd = nullptr; StrOut* dso = nullptr; char* dlines = nullptr;
+    HitRecords rec;
     RTRY(fr.begin());
     STRY(fr.bufs.get(dtrav, max_trav));
-    STRY(fr.bufs.get(dsame, max_n));
-    STRY(fr.bufs.get(dres, max_n));
-    std::vector<PairResult> hres(max_n);
-    std::vector<int32_t> hsame(max_n), htrav(max_trav);
+    RTRY(rec.alloc(fr.bufs, max_n));
+    std::vector<int32_t> htrav(max_trav);
     std::vector<PairDesc> hpd;
     std::vector<StrOut> hso;
     std::vector<char> hlines;
@@ -145,38 +136,23 @@ static int align_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
       const int n = (int)c.n;
       RTRY(fr.stage(c));
       AlignArgs g = {};
-      g.desc = fr.ddesc; g.strip = fr.dstrip; g.trav = dtrav; g.trav_stride = c.trav_stride; g.res = dres; g.same = dsame;
-      RTRY(fr.launch(c, [&](auto side, int k, int cnt, const int32_t* list, const char* qch, const char* tch) {
-        typedef decltype(side) Side;
-        const dim3 grid(cnt), block(64);
-        g.list = list;
-        constexpr int kLocalMax = ((Side::kFusedLocal >> 8) & 1u) ? 8 : 7;   // a class the mask leaves out never gets here
-        if (run.local)
-          dispatch_r<kLocalMax>(k, [&](auto rc) {
-            hipLaunchKernelGGL((hit_local_kernel<decltype(rc)::value, Side, ListJob>), grid, block, 0, ctx->stream, run.a, g, qch, tch);
-          });
-        else
-          dispatch_r<8>(k, [&](auto rc) {
-            hipLaunchKernelGGL((hit_global_kernel<decltype(rc)::value, Side, ListJob>), grid, block, 0, ctx->stream, run.a, g, qch, tch,
-                               run.free_del, run.free_ins);
-          });
-      }));
+      g.desc = fr.ddesc; g.strip = fr.dstrip; g.trav = dtrav; g.trav_stride = c.trav_stride; g.res = rec.dres; g.same = rec.dsame;
+      RTRY(launch_hit_job<ListJob>(fr, c, g));
       if (want_lines) {
         for (int h = 0; h < n; ++h) hpd[h] = pair_desc(queries, templates, fast[c.h0 + h].q, fast[c.h0 + h].t);
         STRY(hipMemcpyAsync(dpd, hpd.data(), (size_t)n * sizeof(PairDesc), hipMemcpyHostToDevice, ctx->stream));
         StrParams prm = {c.trav_stride, 1, 0, line_stride};
-        RTRY(launch_gapped_strings(ctx, n, dpd, dres, dtrav, fr.dqch, fr.dtch, dlines, dso, prm));
+        RTRY(launch_gapped_strings(ctx, n, dpd, rec.dres, dtrav, fr.dqch, fr.dtch, dlines, dso, prm));
         STRY(hipMemcpyAsync(hso.data(), dso, (size_t)n * sizeof(StrOut), hipMemcpyDeviceToHost, ctx->stream));
         STRY(hipMemcpyAsync(hlines.data(), dlines, (size_t)n * 2 * (size_t)line_stride, hipMemcpyDeviceToHost, ctx->stream));
       }
-      STRY(hipMemcpyAsync(hres.data(), dres, (size_t)n * sizeof(PairResult), hipMemcpyDeviceToHost, ctx->stream));
-      STRY(hipMemcpyAsync(hsame.data(), dsame, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+      RTRY(rec.enqueue_download(ctx, c.n));
       if (pairs) STRY(hipMemcpyAsync(htrav.data(), dtrav, (size_t)n * c.trav_stride * 8, hipMemcpyDeviceToHost, ctx->stream));
       STRY(hipStreamSynchronize(ctx->stream));                 // the host vectors above are read by the copies until here
       for (int h = 0; h < n; ++h) {
         const HitDesc& d = fast[c.h0 + h];
         const int64_t Q = queries->offsets[d.q + 1] - queries->offsets[d.q], T = templates->offsets[d.t + 1] - templates->offsets[d.t];
-        put_fused(ao, fast_slot[c.h0 + h], hres[h], hsame[h], Q, T, htrav.data() + (size_t)h * c.trav_stride * 2,
+        put_fused(ao, fast_slot[c.h0 + h], rec.hres[h], rec.hsame[h], Q, T, htrav.data() + (size_t)h * c.trav_stride * 2,
                   want_lines ? &hso[h] : nullptr, want_lines ? hlines.data() + (size_t)h * 2 * line_stride : nullptr, line_stride);
       }
     }
@@ -196,12 +172,11 @@ extern "C" int aln_hits_align(aln_ctx* ctx, const aln_seqs* queries, const aln_s
                               const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K, const aln_hit* hits,
                               const int32_t* n_hits, aln_hit_alignment* out, int32_t* pairs, int32_t pair_stride, char* tlines,
                               char* qlines, int32_t line_stride, int32_t* lengths) {
-  if (ctx) ctx->align_routes[0] = ctx->align_routes[1] = 0;
-  if (!align_outputs_ok(K, hits, n_hits, out, pairs, pair_stride, tlines, qlines, line_stride, lengths)) return ALN_E_ARG;
-  ScoreRun run;
-  int rc = run.prepare(ctx, queries, templates, sub, gap, q_begin, q_end);
-  if (rc != ALN_OK) return rc;
-  return align_block(run, run.queries, K, hits, n_hits, out, pairs, pair_stride, tlines, qlines, line_stride, lengths);
+  return hit_entry(ctx, false, queries, nullptr, nullptr, templates, sub, gap, q_begin, q_end,
+                   align_outputs_ok(K, hits, n_hits, out, pairs, pair_stride, tlines, qlines, line_stride, lengths),
+                   [&](ScoreRun& run, const aln_seqs* pool) {
+                     return align_block(run, pool, K, hits, n_hits, out, pairs, pair_stride, tlines, qlines, line_stride, lengths);
+                   });
 }
 
 // The same for the hits of a profile search.  The query letters — the lines and the identity need them, the scores never do —
@@ -210,15 +185,11 @@ extern "C" int aln_hits_align_profiles(aln_ctx* ctx, const aln_qprofiles* profil
                                        const aln_seqs* templates, const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K,
                                        const aln_hit* hits, const int32_t* n_hits, aln_hit_alignment* out, int32_t* pairs,
                                        int32_t pair_stride, char* tlines, char* qlines, int32_t line_stride, int32_t* lengths) {
-  if (ctx) ctx->align_routes[0] = ctx->align_routes[1] = 0;
-  if (!profiles || !templates || !gap) return ALN_E_ARG;
-  if (!align_outputs_ok(K, hits, n_hits, out, pairs, pair_stride, tlines, qlines, line_stride, lengths)) return ALN_E_ARG;
-  ScoreRun run;
-  run.consensus = consensus;
-  int rc = run.prepare(ctx, nullptr, templates, nullptr, gap, q_begin, q_end, profiles);
-  if (rc != ALN_OK) return rc;
-  return align_block(run, consensus ? consensus : run.queries, K, hits, n_hits, out, pairs, pair_stride, tlines, qlines,
-                     line_stride, lengths);
+  return hit_entry(ctx, true, nullptr, profiles, consensus, templates, nullptr, gap, q_begin, q_end,
+                   align_outputs_ok(K, hits, n_hits, out, pairs, pair_stride, tlines, qlines, line_stride, lengths),
+                   [&](ScoreRun& run, const aln_seqs* pool) {
+                     return align_block(run, pool, K, hits, n_hits, out, pairs, pair_stride, tlines, qlines, line_stride, lengths);
+                   });
 }
 
 extern "C" int aln_hits_align_last_routes(const aln_ctx* ctx, int64_t out[2]) {

@@ -261,13 +261,7 @@ static int multi_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
   AlignOut ao = {out, pairs, pair_stride, tlines, qlines, line_stride, lengths};
   for (size_t s = 0; s < (size_t)rows * K; ++s) {              // every record starts as "not reported"
     n_found[s] = 0;
-    for (int a = 0; a < N; ++a) {
-      const size_t e = s * N + a;
-      const aln_hit_alignment zero = {0, 0, 0.0f, 0.0f};
-      out[e] = zero;
-      if (tlines) { tlines[e * (size_t)line_stride] = 0; qlines[e * (size_t)line_stride] = 0; }
-      if (lengths) lengths[e] = 0;
-    }
+    for (int a = 0; a < N; ++a) ao.clear(s * N + a);
   }
 
   // chunks of fused hits: a strip, a forbidden-cell plane, N lists and, where wanted, N pairs of lines each
@@ -278,16 +272,15 @@ static int multi_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
       return HitNeed{(size_t)std::max<int64_t>(Q - 3, 1) * 256 * (size_t)d.cls, (size_t)Q * 8 * (size_t)d.cls, (int)std::min(Q, T) + 1};
     });
     const size_t max_n = fr.max_n, max_trav = fr.max_trav, max_e = max_n * (size_t)N;
-    uint32_t* dmask = nullptr; int32_t *dtrav = nullptr, *dsame = nullptr, *dfound = nullptr;
-    PairResult* dres = nullptr; PairDesc* dpd = nullptr; StrOut* dso = nullptr; char* dlines = nullptr;
+    uint32_t* dmask = nullptr; int32_t *dtrav = nullptr, *dfound = nullptr;
+    PairDesc* dpd = nullptr; StrOut* dso = nullptr; char* dlines = nullptr;
+    HitRecords rec;                                            // N records per hit
     RTRY(fr.begin());
     STRY(fr.bufs.get(dmask, fr.max_mask));
     STRY(fr.bufs.get(dtrav, max_trav));
-    STRY(fr.bufs.get(dsame, max_e));
     STRY(fr.bufs.get(dfound, max_n));
-    STRY(fr.bufs.get(dres, max_e));
-    std::vector<PairResult> hres(max_e);
-    std::vector<int32_t> hsame(max_e), hfound(max_n), htrav(max_trav);
+    RTRY(rec.alloc(fr.bufs, max_e));
+    std::vector<int32_t> hfound(max_n), htrav(max_trav);
     std::vector<PairDesc> hpd;
     std::vector<StrOut> hso;
     std::vector<char> hlines;
@@ -303,11 +296,11 @@ static int multi_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
       const size_t ne = (size_t)n * N;
       RTRY(fr.stage(c));
       STRY(hipMemsetAsync(dmask, 0, c.mask * 4, ctx->stream));
-      STRY(hipMemsetAsync(dres, 0, ne * sizeof(PairResult), ctx->stream));   // rounds that are not reported: n_path 0, empty lines
-      STRY(hipMemsetAsync(dsame, 0, ne * 4, ctx->stream));
+      STRY(hipMemsetAsync(rec.dres, 0, ne * sizeof(PairResult), ctx->stream));   // rounds that are not reported: n_path 0, empty lines
+      STRY(hipMemsetAsync(rec.dsame, 0, ne * 4, ctx->stream));
       MultiArgs g = {};
       g.desc = fr.ddesc; g.strip = fr.dstrip; g.mask = dmask; g.trav = dtrav; g.trav_stride = c.trav_stride; g.n_rounds = N;
-      g.min_score = min_score; g.res = dres; g.same = dsame; g.n_found = dfound;
+      g.min_score = min_score; g.res = rec.dres; g.same = rec.dsame; g.n_found = dfound;
       RTRY(fr.launch(c, [&](auto side, int k, int cnt, const int32_t* list, const char* qch, const char* tch) {
         typedef decltype(side) Side;
         g.list = list;
@@ -321,12 +314,11 @@ static int multi_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
           std::fill_n(hpd.begin() + (size_t)h * N, N, pair_desc(queries, templates, fast[c.h0 + h].q, fast[c.h0 + h].t));
         STRY(hipMemcpyAsync(dpd, hpd.data(), ne * sizeof(PairDesc), hipMemcpyHostToDevice, ctx->stream));
         StrParams prm = {c.trav_stride, 1, 0, line_stride};
-        RTRY(launch_gapped_strings(ctx, (int)ne, dpd, dres, dtrav, fr.dqch, fr.dtch, dlines, dso, prm));
+        RTRY(launch_gapped_strings(ctx, (int)ne, dpd, rec.dres, dtrav, fr.dqch, fr.dtch, dlines, dso, prm));
         STRY(hipMemcpyAsync(hso.data(), dso, ne * sizeof(StrOut), hipMemcpyDeviceToHost, ctx->stream));
         STRY(hipMemcpyAsync(hlines.data(), dlines, ne * 2 * (size_t)line_stride, hipMemcpyDeviceToHost, ctx->stream));
       }
-      STRY(hipMemcpyAsync(hres.data(), dres, ne * sizeof(PairResult), hipMemcpyDeviceToHost, ctx->stream));
-      STRY(hipMemcpyAsync(hsame.data(), dsame, ne * 4, hipMemcpyDeviceToHost, ctx->stream));
+      RTRY(rec.enqueue_download(ctx, ne));
       STRY(hipMemcpyAsync(hfound.data(), dfound, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
       if (pairs) STRY(hipMemcpyAsync(htrav.data(), dtrav, ne * c.trav_stride * 8, hipMemcpyDeviceToHost, ctx->stream));
       STRY(hipStreamSynchronize(ctx->stream));                 // the host vectors above are read by the copies until here
@@ -337,7 +329,7 @@ static int multi_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
         n_found[slot] = hfound[h];
         for (int a = 0; a < hfound[h]; ++a) {
           const size_t e = (size_t)h * N + a;
-          put_fused(ao, slot * (size_t)N + a, hres[e], hsame[e], Q, T, htrav.data() + e * c.trav_stride * 2,
+          put_fused(ao, slot * (size_t)N + a, rec.hres[e], rec.hsame[e], Q, T, htrav.data() + e * c.trav_stride * 2,
                     want_lines ? &hso[e] : nullptr, want_lines ? hlines.data() + e * 2 * line_stride : nullptr, line_stride);
         }
       }
@@ -359,15 +351,13 @@ extern "C" int aln_hits_align_multi(aln_ctx* ctx, const aln_seqs* queries, const
                                     const int32_t* n_hits, int32_t max_alignments, float min_score, int32_t* n_found,
                                     aln_hit_alignment* out, int32_t* pairs, int32_t pair_stride, char* tlines, char* qlines,
                                     int32_t line_stride, int32_t* lengths) {
-  if (ctx) ctx->align_routes[0] = ctx->align_routes[1] = 0;
-  if (!n_found || max_alignments < 1 || max_alignments > 16) return ALN_E_ARG;
-  if (!align_outputs_ok(K, hits, n_hits, out, pairs, pair_stride, tlines, qlines, line_stride, lengths)) return ALN_E_ARG;
-  ScoreRun run;
-  int rc = run.prepare(ctx, queries, templates, sub, gap, q_begin, q_end);
-  if (rc != ALN_OK) return rc;
-  if (!run.local) return ALN_E_ARG;
-  return multi_block(run, run.queries, K, hits, n_hits, max_alignments, min_score, n_found, out, pairs, pair_stride, tlines, qlines,
-                     line_stride, lengths);
+  const bool ok = n_found && max_alignments >= 1 && max_alignments <= 16 &&
+                  align_outputs_ok(K, hits, n_hits, out, pairs, pair_stride, tlines, qlines, line_stride, lengths);
+  return hit_entry(ctx, false, queries, nullptr, nullptr, templates, sub, gap, q_begin, q_end, ok, [&](ScoreRun& run, const aln_seqs* pool) {
+    if (!run.local) return (int)ALN_E_ARG;
+    return multi_block(run, pool, K, hits, n_hits, max_alignments, min_score, n_found, out, pairs, pair_stride, tlines, qlines,
+                       line_stride, lengths);
+  });
 }
 
 // The same for the hits of a profile search.  The query letters — the lines and the identity need them, the scores never do —
@@ -377,17 +367,13 @@ extern "C" int aln_hits_align_multi_profiles(aln_ctx* ctx, const aln_qprofiles* 
                                              int32_t K, const aln_hit* hits, const int32_t* n_hits, int32_t max_alignments,
                                              float min_score, int32_t* n_found, aln_hit_alignment* out, int32_t* pairs,
                                              int32_t pair_stride, char* tlines, char* qlines, int32_t line_stride, int32_t* lengths) {
-  if (ctx) ctx->align_routes[0] = ctx->align_routes[1] = 0;
-  if (!n_found || max_alignments < 1 || max_alignments > 16) return ALN_E_ARG;
-  if (!profiles || !templates || !gap) return ALN_E_ARG;
-  if (!align_outputs_ok(K, hits, n_hits, out, pairs, pair_stride, tlines, qlines, line_stride, lengths)) return ALN_E_ARG;
-  ScoreRun run;
-  run.consensus = consensus;
-  int rc = run.prepare(ctx, nullptr, templates, nullptr, gap, q_begin, q_end, profiles);
-  if (rc != ALN_OK) return rc;
-  if (!run.local) return ALN_E_ARG;
-  return multi_block(run, consensus ? consensus : run.queries, K, hits, n_hits, max_alignments, min_score, n_found, out, pairs,
-                     pair_stride, tlines, qlines, line_stride, lengths);
+  const bool ok = n_found && max_alignments >= 1 && max_alignments <= 16 &&
+                  align_outputs_ok(K, hits, n_hits, out, pairs, pair_stride, tlines, qlines, line_stride, lengths);
+  return hit_entry(ctx, true, nullptr, profiles, consensus, templates, nullptr, gap, q_begin, q_end, ok, [&](ScoreRun& run, const aln_seqs* pool) {
+    if (!run.local) return (int)ALN_E_ARG;
+    return multi_block(run, pool, K, hits, n_hits, max_alignments, min_score, n_found, out, pairs, pair_stride, tlines, qlines,
+                       line_stride, lengths);
+  });
 }
 
 #undef STRY

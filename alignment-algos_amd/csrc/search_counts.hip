@@ -14,8 +14,8 @@
 // buffer and no gapped_strings_kernel; the rows are zeroed once per call and downloaded once at its end.
 // A slot that must not contribute — weight 0, a local score <= 0 (the seed cell's list) — still needs its record: the host
 // passes weight 0 for it and the kernel leaves the adds out.  A local slot whose sweep score differs from .score returns
-// before the walk.  Everything the kernels do not take goes through align_through_batches (search_align.hip) with pair lists
-// wanted, which the host tallies into the same outputs.
+// before the walk.  Everything the kernels do not take goes through for_list_groups (search_align.h) — align_through_batches
+// with pair lists wanted, a group of slots at a time —, whose lists the host tallies into the same outputs.
 #include <algorithm>
 #include <climits>
 #include <cstring>
@@ -76,7 +76,8 @@ struct CountJob {
 };
 
 // The shared body of aln_hits_column_counts and aln_hits_column_counts_profiles (run: prepared; `queries`: the pool the query
-// letters and lengths are read from, as in align_block): the slot checks, the routes, the chunks of fused hits, the batches.
+// letters and lengths are read from — hit_entry's pool, search_align.h): the slot checks, the routes, the chunks of fused
+// hits, the batches.
 static int count_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const aln_hit* hits, const int32_t* n_hits,
                        const int32_t* weights, aln_hit_alignment* out, int32_t* counts, int32_t* covered) {
   aln_ctx* ctx = run.ctx;
@@ -90,78 +91,49 @@ static int count_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
   const int64_t row0 = queries->offsets[q_begin];
   const size_t n_rows = (size_t)(queries->offsets[run.q_end] - row0);
 
-  // align_block's walk (every used slot validated and described for its route), then the weights; nothing written before
+  // route_slots' walk (every used slot validated and described for its route), then the weights; nothing written before
   SlotRoutes sr;
   int rc = route_slots(run, queries, K, hits, n_hits, hit_kernel_classes(run), run.local, sr);
   if (rc != ALN_OK) return rc;
   std::vector<HitDesc>& fast = sr.fast;
   const std::vector<size_t>& fast_slot = sr.fast_slot;
-  const std::vector<int32_t>&bq = sr.bq, &bt = sr.bt;
-  const std::vector<size_t>& bslot = sr.bslot;
   if (weights)
     for (int r = 0; r < rows; ++r)
       for (int k = 0; k < n_hits[r]; ++k)
         if (weights[(size_t)r * K + k] < 0 || weights[(size_t)r * K + k] > 65535) return ALN_E_ARG;
   auto weight_of = [&](size_t slot) { return weights ? weights[slot] : 1; };
-  ctx->align_routes[0] = (int64_t)fast.size(); ctx->align_routes[1] = (int64_t)bq.size();
+  ctx->align_routes[0] = (int64_t)fast.size(); ctx->align_routes[1] = (int64_t)sr.bq.size();
 
   memset(counts, 0, n_rows * (size_t)n_alpha * 4);
   if (covered) memset(covered, 0, n_rows * 4);
-  for (int r = 0; r < rows; ++r)
-    for (int k = n_hits[r]; k < K; ++k) out[(size_t)r * K + k] = aln_hit_alignment{0, 0, 0.0f, 0.0f};
   AlignOut ao = {out, nullptr, 0, nullptr, nullptr, 0, nullptr};
+  ao.clear_unused(rows, K, n_hits);
 
   // chunks of fused hits: no lists and no lines, so only the strips count against the budget
   if (!fast.empty()) {
     FusedRoute<HitDesc> fr(run, queries, fast);
     std::vector<int32_t> fast_w(fast.size());
     for (size_t h = 0; h < fast.size(); ++h) fast_w[h] = (run.local && !(fast[h].score > 0.f)) ? 0 : weight_of(fast_slot[h]);
-    fr.cut(0, false, 0, [&](const HitDesc& d) {
-      const int srows = run.local ? d.q_end - 1 : (int)(queries->offsets[d.q + 1] - queries->offsets[d.q]) - 3;
-      return HitNeed{(size_t)std::max(srows, 1) * 256 * (size_t)d.cls, 0, 0};
-    });
-    const size_t max_n = fr.max_n;
-    int32_t *dw = nullptr, *dsame = nullptr, *drows = nullptr; PairResult* dres = nullptr;
+    fr.cut(0, false, 0, [&](const HitDesc& d) { return HitNeed{hit_strip_bytes(run, queries, d), 0, 0}; });
+    int32_t *dw = nullptr, *drows = nullptr;
+    HitRecords rec;
     RTRY(fr.begin());
-    STRY(fr.bufs.get(dw, max_n));
-    STRY(fr.bufs.get(dsame, max_n));
-    STRY(fr.bufs.get(dres, max_n));
+    STRY(fr.bufs.get(dw, fr.max_n));
+    RTRY(rec.alloc(fr.bufs, fr.max_n));
     STRY(fr.bufs.get(drows, std::max<size_t>(n_rows, 1) * 32));
     STRY(hipMemsetAsync(drows, 0, std::max<size_t>(n_rows, 1) * 128, ctx->stream));      // once per call, not per chunk
-    std::vector<PairResult> hres(max_n);
-    std::vector<int32_t> hsame(max_n);
     if (prof) RTRY(fr.upload_pools());
     for (const FusedChunk& c : fr.chunks) {
-      const int n = (int)c.n;
       RTRY(fr.stage(c, [&]() -> int {
-        STRY(hipMemcpyAsync(dw, fast_w.data() + c.h0, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+        STRY(hipMemcpyAsync(dw, fast_w.data() + c.h0, c.n * 4, hipMemcpyHostToDevice, ctx->stream));
         return ALN_OK;
       }));
       CountArgs g = {};
-      g.desc = fr.ddesc; g.strip = fr.dstrip; g.weight = dw; g.rows = drows; g.row0 = row0; g.res = dres; g.same = dsame;
-      RTRY(fr.launch(c, [&](auto side, int k, int cnt, const int32_t* list, const char* qch, const char* tch) {
-        typedef decltype(side) Side;
-        const dim3 grid(cnt), block(64);
-        g.list = list;
-        constexpr int kLocalMax = ((Side::kFusedLocal >> 8) & 1u) ? 8 : 7;   // a class the mask leaves out never gets here
-        if (run.local)
-          dispatch_r<kLocalMax>(k, [&](auto rc) {
-            hipLaunchKernelGGL((hit_local_kernel<decltype(rc)::value, Side, CountJob>), grid, block, 0, ctx->stream, run.a, g, qch, tch);
-          });
-        else
-          dispatch_r<8>(k, [&](auto rc) {
-            hipLaunchKernelGGL((hit_global_kernel<decltype(rc)::value, Side, CountJob>), grid, block, 0, ctx->stream, run.a, g, qch, tch,
-                               run.free_del, run.free_ins);
-          });
-      }));
-      STRY(hipMemcpyAsync(hres.data(), dres, (size_t)n * sizeof(PairResult), hipMemcpyDeviceToHost, ctx->stream));
-      STRY(hipMemcpyAsync(hsame.data(), dsame, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-      STRY(hipStreamSynchronize(ctx->stream));                 // the host vectors above are read by the copies until here
-      for (int h = 0; h < n; ++h) {
-        const HitDesc& d = fast[c.h0 + h];
-        const int64_t Q = queries->offsets[d.q + 1] - queries->offsets[d.q], T = templates->offsets[d.t + 1] - templates->offsets[d.t];
-        put_fused(ao, fast_slot[c.h0 + h], hres[h], hsame[h], Q, T, nullptr, nullptr, nullptr, 0);
-      }
+      g.desc = fr.ddesc; g.strip = fr.dstrip; g.weight = dw; g.rows = drows; g.row0 = row0; g.res = rec.dres; g.same = rec.dsame;
+      RTRY(launch_hit_job<CountJob>(fr, c, g));
+      RTRY(rec.enqueue_download(ctx, c.n));
+      STRY(hipStreamSynchronize(ctx->stream));                 // the records' host images are read by the copies until here
+      rec.put(ao, fr, c, fast_slot, [](size_t, size_t, int64_t) {});
     }
     std::vector<int32_t> hrows(n_rows * 32);
     STRY(hipMemcpyAsync(hrows.data(), drows, n_rows * 128, hipMemcpyDeviceToHost, ctx->stream));
@@ -172,56 +144,28 @@ static int count_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
     }
   }
 
-  // the batch route, a group of slots at a time: records and pair lists into buffers of the group, tallied here
-  if (!bq.empty()) {
+  // the batch route (for_list_groups, search_align.h): every surviving slot's pair list tallied here
+  if (!sr.bq.empty()) {
     int idx[256];
     for (int i = 0; i < 256; ++i) idx[i] = -1;
     for (int i = 0; i < n_alpha; ++i) idx[(unsigned char)alphabet[i]] = i;
-    constexpr size_t kGroupBytes = (size_t)256 << 20;        // of pair lists on the host at a time
-    std::vector<aln_hit_alignment> grec;
-    std::vector<int32_t> gpairs, gq, gt;
-    std::vector<size_t> gslot;
-    for (size_t b0 = 0; b0 < bq.size();) {
-      size_t b1 = b0; int64_t stride = 4;
-      while (b1 < bq.size()) {
-        const int64_t Q = queries->offsets[bq[b1] + 1] - queries->offsets[bq[b1]];
-        const int64_t T = templates->offsets[bt[b1] + 1] - templates->offsets[bt[b1]];
-        const int64_t s = std::max(stride, std::min(Q, T) + 3);
-        if (b1 > b0 && (b1 + 1 - b0) * (size_t)s * 8 > kGroupBytes) break;
-        stride = s; ++b1;
+    rc = for_list_groups(run, queries, sr, ao, [&](size_t slot, int32_t q, int32_t t, const int32_t* l, int n_pairs) {
+      const int w = weight_of(slot);
+      if (w <= 0) return;
+      const int64_t qo = queries->offsets[q], Q = queries->offsets[q + 1] - qo;
+      const int64_t to = templates->offsets[t], T = templates->offsets[t + 1] - to;
+      int64_t lo = INT64_MAX, hi = -1;
+      for (int k = 0; k < n_pairs; ++k) {
+        const int64_t i = l[2 * k], j = l[2 * k + 1];
+        if (i < 1 || i > Q - 2 || j < 1 || j > T - 2) continue;
+        const int a = idx[(unsigned char)templates->residues[to + j]];
+        if (a >= 0) counts[(size_t)(qo - row0 + i) * n_alpha + a] += w;
+        lo = std::min(lo, i); hi = std::max(hi, i);
       }
-      const size_t nb = b1 - b0;
-      grec.assign(nb, aln_hit_alignment{0, 0, 0.0f, 0.0f});
-      gpairs.assign(nb * (size_t)stride * 2, 0);
-      gq.assign(bq.begin() + b0, bq.begin() + b1); gt.assign(bt.begin() + b0, bt.begin() + b1);
-      gslot.resize(nb);
-      for (size_t p = 0; p < nb; ++p) gslot[p] = p;
-      AlignOut go = {grec.data(), gpairs.data(), (int32_t)stride, nullptr, nullptr, 0, nullptr};
-      rc = align_through_batches(ctx, queries, templates, run.sub, prof, run.gap, gq, gt, gslot, go);
-      if (rc != ALN_OK) return rc;
-      for (size_t p = 0; p < nb; ++p) {
-        const size_t slot = bslot[b0 + p];
-        const aln_hit_alignment& rec = grec[p];
-        out[slot] = rec;
-        ao.note(rec.status);
-        const int w = weight_of(slot);
-        if (rec.status != 0 || w <= 0 || (run.local && !(rec.score > 0.f))) continue;
-        const int64_t qo = queries->offsets[gq[p]], Q = queries->offsets[gq[p] + 1] - qo;
-        const int64_t to = templates->offsets[gt[p]], T = templates->offsets[gt[p] + 1] - to;
-        const int32_t* l = gpairs.data() + p * (size_t)stride * 2;
-        int64_t lo = INT64_MAX, hi = -1;
-        for (int k = 0; k < rec.n_pairs; ++k) {
-          const int64_t i = l[2 * k], j = l[2 * k + 1];
-          if (i < 1 || i > Q - 2 || j < 1 || j > T - 2) continue;
-          const int a = idx[(unsigned char)templates->residues[to + j]];
-          if (a >= 0) counts[(size_t)(qo - row0 + i) * n_alpha + a] += w;
-          lo = std::min(lo, i); hi = std::max(hi, i);
-        }
-        if (covered)
-          for (int64_t i = lo; i <= hi; ++i) covered[qo - row0 + i] += w;
-      }
-      b0 = b1;
-    }
+      if (covered)
+        for (int64_t i = lo; i <= hi; ++i) covered[qo - row0 + i] += w;
+    });
+    if (rc != ALN_OK) return rc;
   }
   return ao.worst;
 }
@@ -234,26 +178,20 @@ extern "C" int aln_hits_column_counts(aln_ctx* ctx, const aln_seqs* queries, con
                                       const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K, const aln_hit* hits,
                                       const int32_t* n_hits, const int32_t* weights, aln_hit_alignment* out, int32_t* counts,
                                       int32_t* covered) {
-  if (ctx) ctx->align_routes[0] = ctx->align_routes[1] = 0;
-  if (!hits || !n_hits || !out || !counts || K < 1 || K > 1024) return ALN_E_ARG;
-  ScoreRun run;
-  int rc = run.prepare(ctx, queries, templates, sub, gap, q_begin, q_end);
-  if (rc != ALN_OK) return rc;
-  return count_block(run, run.queries, K, hits, n_hits, weights, out, counts, covered);
+  return hit_entry(ctx, false, queries, nullptr, nullptr, templates, sub, gap, q_begin, q_end, hit_list_ok(K, hits, n_hits, out) && counts,
+                   [&](ScoreRun& run, const aln_seqs* pool) {
+                     return count_block(run, pool, K, hits, n_hits, weights, out, counts, covered);
+                   });
 }
 
 extern "C" int aln_hits_column_counts_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_seqs* consensus,
                                                const aln_seqs* templates, const aln_gap* gap, int32_t q_begin, int32_t q_end,
                                                int32_t K, const aln_hit* hits, const int32_t* n_hits, const int32_t* weights,
                                                aln_hit_alignment* out, int32_t* counts, int32_t* covered) {
-  if (ctx) ctx->align_routes[0] = ctx->align_routes[1] = 0;
-  if (!profiles || !templates || !gap) return ALN_E_ARG;
-  if (!hits || !n_hits || !out || !counts || K < 1 || K > 1024) return ALN_E_ARG;
-  ScoreRun run;
-  run.consensus = consensus;
-  int rc = run.prepare(ctx, nullptr, templates, nullptr, gap, q_begin, q_end, profiles);
-  if (rc != ALN_OK) return rc;
-  return count_block(run, consensus ? consensus : run.queries, K, hits, n_hits, weights, out, counts, covered);
+  return hit_entry(ctx, true, nullptr, profiles, consensus, templates, nullptr, gap, q_begin, q_end, hit_list_ok(K, hits, n_hits, out) && counts,
+                   [&](ScoreRun& run, const aln_seqs* pool) {
+                     return count_block(run, pool, K, hits, n_hits, weights, out, counts, covered);
+                   });
 }
 
 #undef STRY

@@ -34,8 +34,8 @@
 // offset into it is toff[desc[hit].t], the offset of the codes.  The kernels' signatures are untouched.
 // A slot that must not contribute but needs its record — a local score <= 0, the seed cell's list — is muted by a per-hit flag
 // from the host (live == 0), as CountJob is muted by weight 0: its sink counts `same` and stores nothing.  A local slot whose
-// sweep score differs from .score returns before the walk.  Everything the kernels do not take goes through
-// align_through_batches (search_align.hip) with pair lists wanted, from which the host fills the same outputs.
+// sweep score differs from .score returns before the walk.  Everything the kernels do not take goes through for_list_groups
+// (search_align.h) — align_through_batches with pair lists wanted —, from whose lists the host fills the same outputs.
 #include <algorithm>
 #include <climits>
 #include <cstring>
@@ -142,12 +142,12 @@ static void pileup_from_list(const int32_t* l, int n, int64_t Q, int64_t T, cons
 }
 
 // The shared body of aln_hits_pileup and aln_hits_pileup_profiles (run: prepared; `queries`: the pool the query lengths are
-// read from, as in count_block): the stride check, the slot checks, the routes, the chunks of fused hits, the batches.
+// read from — hit_entry's pool, search_align.h): the stride check, the slot checks, the routes, the chunks of fused hits,
+// the batches.
 static int pileup_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const aln_hit* hits, const int32_t* n_hits,
                         aln_hit_alignment* out, aln_hit_span* spans, char* letters, uint16_t* tpos, int32_t line_stride) {
   aln_ctx* ctx = run.ctx;
   const aln_seqs* templates = run.templates;
-  const aln_qprofiles* prof = run.prof;
   const int rows = run.rows;
   if (rows == 0) return ALN_OK;
   const bool want_rows = letters || tpos;
@@ -156,30 +156,26 @@ static int pileup_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const
   if (want_rows && line_stride < maxw) return ALN_E_ARG;
   maxw = std::max<int64_t>(maxw, 1);                         // ... which is the device rows' stride
 
-  // align_block's walk (every used slot validated and described for its route); nothing written before
+  // route_slots' walk (every used slot validated and described for its route); nothing written before
   SlotRoutes sr;
   int rc = route_slots(run, queries, K, hits, n_hits, hit_kernel_classes(run), run.local, sr);
   if (rc != ALN_OK) return rc;
   std::vector<HitDesc>& fast = sr.fast;
   const std::vector<size_t>& fast_slot = sr.fast_slot;
-  const std::vector<int32_t>&bq = sr.bq, &bt = sr.bt;
-  const std::vector<size_t>& bslot = sr.bslot;
-  ctx->align_routes[0] = (int64_t)fast.size(); ctx->align_routes[1] = (int64_t)bq.size();
+  ctx->align_routes[0] = (int64_t)fast.size(); ctx->align_routes[1] = (int64_t)sr.bq.size();
 
   // the outputs in full: zero everywhere, then '.' over the Q - 2 positions of every used slot
   const size_t n_slots = (size_t)rows * K, ls = want_rows ? (size_t)line_stride : 0;
   if (letters) memset(letters, 0, n_slots * ls);
   if (tpos) memset(tpos, 0, n_slots * ls * 2);
   if (spans) memset(spans, 0, n_slots * sizeof(aln_hit_span));
+  AlignOut ao = {out, nullptr, 0, nullptr, nullptr, 0, nullptr};
+  ao.clear_unused(rows, K, n_hits);
   for (int r = 0; r < rows; ++r) {
     const int64_t w = queries->offsets[run.q_begin + r + 1] - queries->offsets[run.q_begin + r] - 2;
-    for (int k = 0; k < K; ++k) {
-      const size_t slot = (size_t)r * K + k;
-      if (k >= n_hits[r]) out[slot] = aln_hit_alignment{0, 0, 0.0f, 0.0f};
-      else if (letters && w > 0) memset(letters + slot * ls, '.', (size_t)w);
-    }
+    if (letters && w > 0)
+      for (int k = 0; k < n_hits[r]; ++k) memset(letters + ((size_t)r * K + k) * ls, '.', (size_t)w);
   }
-  AlignOut ao = {out, nullptr, 0, nullptr, nullptr, 0, nullptr};
 
   // chunks of fused hits.  cut() is asked for one "pair of lines" of maxw bytes per hit, which is the 2 maxw bytes of a tpos row
   // (the letters row is half of that), and for lists of no entries: strips and each row buffer stay below the budget.
@@ -187,23 +183,18 @@ static int pileup_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const
     FusedRoute<HitDesc> fr(run, queries, fast);
     std::vector<int32_t> fast_live(fast.size());
     for (size_t h = 0; h < fast.size(); ++h) fast_live[h] = (run.local && !(fast[h].score > 0.f)) ? 0 : 1;
-    fr.cut(1, want_rows, (int)std::min<int64_t>(maxw, INT_MAX), [&](const HitDesc& d) {
-      const int srows = run.local ? d.q_end - 1 : (int)(queries->offsets[d.q + 1] - queries->offsets[d.q]) - 3;
-      return HitNeed{(size_t)std::max(srows, 1) * 256 * (size_t)d.cls, 0, 0};
-    });
+    fr.cut(1, want_rows, (int)std::min<int64_t>(maxw, INT_MAX),
+           [&](const HitDesc& d) { return HitNeed{hit_strip_bytes(run, queries, d), 0, 0}; });
     const size_t max_n = fr.max_n, dw = (size_t)maxw;
-    int32_t *dlive = nullptr, *dsame = nullptr; PairResult* dres = nullptr;
-    char* dlet = nullptr; uint16_t* dpos = nullptr; aln_hit_span* dspan = nullptr; PileupRows* drows = nullptr;
+    int32_t* dlive = nullptr; char* dlet = nullptr; uint16_t* dpos = nullptr; aln_hit_span* dspan = nullptr; PileupRows* drows = nullptr;
+    HitRecords rec;
     RTRY(fr.begin());
     STRY(fr.bufs.get(dlive, max_n));
-    STRY(fr.bufs.get(dsame, max_n));
-    STRY(fr.bufs.get(dres, max_n));
+    RTRY(rec.alloc(fr.bufs, max_n));
     if (letters) STRY(fr.bufs.get(dlet, max_n * dw));
     if (tpos) STRY(fr.bufs.get(dpos, max_n * dw));
     if (spans) STRY(fr.bufs.get(dspan, max_n));
     STRY(fr.bufs.get(drows, 1));
-    std::vector<PairResult> hres(max_n);
-    std::vector<int32_t> hsame(max_n);
     std::vector<char> hlet(letters ? max_n * dw : 0);
     std::vector<uint16_t> hpos(tpos ? max_n * dw : 0);
     std::vector<aln_hit_span> hspan(spans ? max_n : 0);
@@ -220,85 +211,37 @@ static int pileup_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const
         return ALN_OK;
       }));
       PileupArgs g = {};
-      g.desc = fr.ddesc; g.strip = fr.dstrip; g.rows = drows; g.res = dres; g.same = dsame;
-      RTRY(fr.launch(c, [&](auto side, int k, int cnt, const int32_t* list, const char* qch, const char* tch) {
-        typedef decltype(side) Side;
-        const dim3 grid(cnt), block(64);
-        g.list = list;
-        constexpr int kLocalMax = ((Side::kFusedLocal >> 8) & 1u) ? 8 : 7;   // a class the mask leaves out never gets here
-        if (run.local)
-          dispatch_r<kLocalMax>(k, [&](auto rc) {
-            hipLaunchKernelGGL((hit_local_kernel<decltype(rc)::value, Side, PileupJob>), grid, block, 0, ctx->stream, run.a, g, qch, tch);
-          });
-        else
-          dispatch_r<8>(k, [&](auto rc) {
-            hipLaunchKernelGGL((hit_global_kernel<decltype(rc)::value, Side, PileupJob>), grid, block, 0, ctx->stream, run.a, g, qch, tch,
-                               run.free_del, run.free_ins);
-          });
-      }));
-      STRY(hipMemcpyAsync(hres.data(), dres, n * sizeof(PairResult), hipMemcpyDeviceToHost, ctx->stream));
-      STRY(hipMemcpyAsync(hsame.data(), dsame, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+      g.desc = fr.ddesc; g.strip = fr.dstrip; g.rows = drows; g.res = rec.dres; g.same = rec.dsame;
+      RTRY(launch_hit_job<PileupJob>(fr, c, g));
+      RTRY(rec.enqueue_download(ctx, n));
       if (dlet) STRY(hipMemcpyAsync(hlet.data(), dlet, n * dw, hipMemcpyDeviceToHost, ctx->stream));
       if (dpos) STRY(hipMemcpyAsync(hpos.data(), dpos, n * dw * 2, hipMemcpyDeviceToHost, ctx->stream));
       if (dspan) STRY(hipMemcpyAsync(hspan.data(), dspan, n * sizeof(aln_hit_span), hipMemcpyDeviceToHost, ctx->stream));
       STRY(hipStreamSynchronize(ctx->stream));                 // the host vectors above are read by the copies until here
-      for (size_t h = 0; h < n; ++h) {
-        const HitDesc& d = fast[c.h0 + h];
-        const size_t slot = fast_slot[c.h0 + h];
-        const int64_t Q = queries->offsets[d.q + 1] - queries->offsets[d.q], T = templates->offsets[d.t + 1] - templates->offsets[d.t];
-        put_fused(ao, slot, hres[h], hsame[h], Q, T, nullptr, nullptr, nullptr, 0);
+      rec.put(ao, fr, c, fast_slot, [&](size_t h, size_t slot, int64_t Q) {
         if (letters) memcpy(letters + slot * ls, hlet.data() + h * dw, (size_t)(Q - 2));
         if (tpos) memcpy(tpos + slot * ls, hpos.data() + h * dw, (size_t)(Q - 2) * 2);
         if (spans) spans[slot] = hspan[h];
-      }
+      });
     }
   }
 
-  // the batch route, a group of slots at a time: records and pair lists into buffers of the group, laid out here
-  if (!bq.empty()) {
-    constexpr size_t kGroupBytes = (size_t)256 << 20;        // of pair lists on the host at a time
-    std::vector<aln_hit_alignment> grec;
-    std::vector<int32_t> gpairs, gq, gt;
-    std::vector<size_t> gslot;
-    for (size_t b0 = 0; b0 < bq.size();) {
-      size_t b1 = b0; int64_t stride = 4;
-      while (b1 < bq.size()) {
-        const int64_t Q = queries->offsets[bq[b1] + 1] - queries->offsets[bq[b1]];
-        const int64_t T = templates->offsets[bt[b1] + 1] - templates->offsets[bt[b1]];
-        const int64_t s = std::max(stride, std::min(Q, T) + 3);
-        if (b1 > b0 && (b1 + 1 - b0) * (size_t)s * 8 > kGroupBytes) break;
-        stride = s; ++b1;
-      }
-      const size_t nb = b1 - b0;
-      grec.assign(nb, aln_hit_alignment{0, 0, 0.0f, 0.0f});
-      gpairs.assign(nb * (size_t)stride * 2, 0);
-      gq.assign(bq.begin() + b0, bq.begin() + b1); gt.assign(bt.begin() + b0, bt.begin() + b1);
-      gslot.resize(nb);
-      for (size_t p = 0; p < nb; ++p) gslot[p] = p;
-      AlignOut go = {grec.data(), gpairs.data(), (int32_t)stride, nullptr, nullptr, 0, nullptr};
-      rc = align_through_batches(ctx, queries, templates, run.sub, prof, run.gap, gq, gt, gslot, go);
-      if (rc != ALN_OK) return rc;
-      for (size_t p = 0; p < nb; ++p) {
-        const size_t slot = bslot[b0 + p];
-        const aln_hit_alignment& rec = grec[p];
-        out[slot] = rec;
-        ao.note(rec.status);
-        if (rec.status != 0 || (run.local && !(rec.score > 0.f))) continue;
-        const int64_t Q = queries->offsets[gq[p] + 1] - queries->offsets[gq[p]];
-        const int64_t to = templates->offsets[gt[p]], T = templates->offsets[gt[p] + 1] - to;
-        pileup_from_list(gpairs.data() + p * (size_t)stride * 2, rec.n_pairs, Q, T, templates->residues + to,
-                         letters ? letters + slot * ls : nullptr, tpos ? tpos + slot * ls : nullptr, spans ? spans + slot : nullptr);
-      }
-      b0 = b1;
-    }
+  // the batch route (for_list_groups, search_align.h): every surviving slot's pair list laid out here
+  if (!sr.bq.empty()) {
+    rc = for_list_groups(run, queries, sr, ao, [&](size_t slot, int32_t q, int32_t t, const int32_t* l, int n_pairs) {
+      const int64_t Q = queries->offsets[q + 1] - queries->offsets[q];
+      const int64_t to = templates->offsets[t], T = templates->offsets[t + 1] - to;
+      pileup_from_list(l, n_pairs, Q, T, templates->residues + to, letters ? letters + slot * ls : nullptr,
+                       tpos ? tpos + slot * ls : nullptr, spans ? spans + slot : nullptr);
+    });
+    if (rc != ALN_OK) return rc;
   }
   return ao.worst;
 }
 
 static bool pileup_outputs_ok(int32_t K, const aln_hit* hits, const int32_t* n_hits, const aln_hit_alignment* out, const char* letters,
                               const uint16_t* tpos, int32_t line_stride) {
-  if (!hits || !n_hits || !out || K < 1 || K > 1024) return false;
-  return !((letters || tpos) && line_stride < 1);
+  return hit_list_ok(K, hits, n_hits, out) && !((letters || tpos) && line_stride < 1);
 }
 
 }  // namespace aln
@@ -309,26 +252,20 @@ extern "C" int aln_hits_pileup(aln_ctx* ctx, const aln_seqs* queries, const aln_
                                const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K, const aln_hit* hits,
                                const int32_t* n_hits, aln_hit_alignment* out, aln_hit_span* spans, char* letters, uint16_t* tpos,
                                int32_t line_stride) {
-  if (ctx) ctx->align_routes[0] = ctx->align_routes[1] = 0;
-  if (!pileup_outputs_ok(K, hits, n_hits, out, letters, tpos, line_stride)) return ALN_E_ARG;
-  ScoreRun run;
-  int rc = run.prepare(ctx, queries, templates, sub, gap, q_begin, q_end);
-  if (rc != ALN_OK) return rc;
-  return pileup_block(run, run.queries, K, hits, n_hits, out, spans, letters, tpos, line_stride);
+  return hit_entry(ctx, false, queries, nullptr, nullptr, templates, sub, gap, q_begin, q_end,
+                   pileup_outputs_ok(K, hits, n_hits, out, letters, tpos, line_stride), [&](ScoreRun& run, const aln_seqs* pool) {
+                     return pileup_block(run, pool, K, hits, n_hits, out, spans, letters, tpos, line_stride);
+                   });
 }
 
 extern "C" int aln_hits_pileup_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_seqs* consensus,
                                         const aln_seqs* templates, const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K,
                                         const aln_hit* hits, const int32_t* n_hits, aln_hit_alignment* out, aln_hit_span* spans,
                                         char* letters, uint16_t* tpos, int32_t line_stride) {
-  if (ctx) ctx->align_routes[0] = ctx->align_routes[1] = 0;
-  if (!profiles || !templates || !gap) return ALN_E_ARG;
-  if (!pileup_outputs_ok(K, hits, n_hits, out, letters, tpos, line_stride)) return ALN_E_ARG;
-  ScoreRun run;
-  run.consensus = consensus;
-  int rc = run.prepare(ctx, nullptr, templates, nullptr, gap, q_begin, q_end, profiles);
-  if (rc != ALN_OK) return rc;
-  return pileup_block(run, consensus ? consensus : run.queries, K, hits, n_hits, out, spans, letters, tpos, line_stride);
+  return hit_entry(ctx, true, nullptr, profiles, consensus, templates, nullptr, gap, q_begin, q_end,
+                   pileup_outputs_ok(K, hits, n_hits, out, letters, tpos, line_stride), [&](ScoreRun& run, const aln_seqs* pool) {
+                     return pileup_block(run, pool, K, hits, n_hits, out, spans, letters, tpos, line_stride);
+                   });
 }
 
 #undef STRY

@@ -221,6 +221,9 @@ int aln_has_gfx950(void);
  *                                   the rows of its own profiles (environment default ALN_ZSCORE_ROWS_PER_CHUNK).  Same results.
  *   "align_chunk_hits"              aln_hits_align: hit slots whose 1 B/cell strips are resident on the device at a time; 0 (default) = as
  *                                   many as keep the strips, the lists and the lines below 1 GiB each; a value never lifts that budget
+ *   "align_list_group_slots"        aln_hits_column_counts, aln_hits_pileup: batch-route slots whose pair lists are held on the host at a
+ *                                   time; 0 (default) = as many as keep the lists below 256 MiB; a value never lifts that bound
+ *                                   (environment default ALN_ALIGN_LIST_GROUP_SLOTS).  Same results.
  *   "align_fused_nonlocal"          aln_hits_align: 1 (default) = hits of the four non-local align types are aligned by the fused
  *                                   kernel where it applies; 0 = they all go through resident batches (environment default
  *                                   ALN_ALIGN_FUSED_NONLOCAL).  Same results.

@@ -9,10 +9,12 @@ tolerance anywhere.  aln_amd's library is not imported (aln_amd.synth is pure nu
   tally            include/aln_hip.h, aln_hits_column_counts, restated: counts per row and covered
   class_set        queries of 130 .. 1 interior residues against templates of every fused length class and one beyond
   homolog_set      homolog_pair queries and templates: lists with deletion and insertion jumps
+  hit_array, gap   the GPU tests' hit slots as aln_hit, and SYSTEM's gap descriptor
   check_sets       the assertions on the reference alone; the test modules call it before they use a set
 """
 import numpy as np
 
+import aln_amd
 import orc
 import profile_align_cases as pac
 import profile_cases as pc
@@ -143,6 +145,30 @@ def homolog_set():
 
 def all_slots(n_q, n_t):
     return [(r, t) for r in range(n_q) for t in range(n_t)]
+
+
+def used_slots(n_hits, K):
+    return [(r, k) for r in range(len(n_hits)) for k in range(K) if k < n_hits[r]]
+
+
+def hit_array(t_idx, n_hits, lists, local):
+    """the slots t_idx[rows, K] as aln_hit: local slots carry the oracle's score and the cell its list starts from (the entry
+    before (Q-1, T-1)); non-local slots carry values that must not be read; unused slots hold a template that must not be"""
+    hits = np.zeros(t_idx.shape, dtype=aln_amd.HIT_DTYPE)
+    hits["t"] = t_idx
+    hits["q_end"], hits["t_end"], hits["score"] = -7, 1 << 20, -1e30
+    for (r, k), (score, pl) in zip(used_slots(n_hits, t_idx.shape[1]), lists):
+        if local:
+            hits["score"][r, k] = score
+            hits["q_end"][r, k], hits["t_end"][r, k] = pl[-2]
+    return hits
+
+
+def gap(model=aln_amd.GAP_AFFINE_CONST, align_type=aln_amd.LOCAL):
+    """SYSTEM's gap costs as the C ABI's descriptor"""
+    g = aln_amd.AlnGap()
+    g.model, g.align_type, g.gap_init, g.gap_extn = model, align_type, float(SYSTEM[1]), float(SYSTEM[2])
+    return g
 
 
 _CHECKED = {}

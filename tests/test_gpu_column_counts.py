@@ -3,7 +3,7 @@
 equality: counts and covered against the numpy tally over the oracle's pair lists (column_count_cases), the records byte for
 byte against aln_hits_align called without lists and lines.
 
-  1  every fused length class and the batch route into the same rows, a duplicated slot, weights, chunks, covered == NULL
+  1  every fused length class and the batch route into the same rows, a duplicated slot, weights, chunks, covered == NULL, list groups
   2  a row block with q_begin > 0
   3  a falsified local score, local pairs whose best score is 0, pairs without an interior
   4  the argument checks, in their order
@@ -30,21 +30,8 @@ _, GI, GE = cc.SYSTEM
 K5 = 5
 
 
-def used_slots(n_hits, K):
-    return [(r, k) for r in range(len(n_hits)) for k in range(K) if k < n_hits[r]]
-
-
-def hit_array(t_idx, n_hits, lists, local):
-    """the slots t_idx[rows, K] as aln_hit: local slots carry the oracle's score and the cell its list starts from (the entry
-    before (Q-1, T-1)); non-local slots carry values that must not be read; unused slots hold a template that must not be"""
-    hits = np.zeros(t_idx.shape, dtype=aln_amd.HIT_DTYPE)
-    hits["t"] = t_idx
-    hits["q_end"], hits["t_end"], hits["score"] = -7, 1 << 20, -1e30
-    for (r, k), (score, pl) in zip(used_slots(n_hits, t_idx.shape[1]), lists):
-        if local:
-            hits["score"][r, k] = score
-            hits["q_end"][r, k], hits["t_end"][r, k] = pl[-2]
-    return hits
+used_slots = cc.used_slots
+hit_array = cc.hit_array
 
 
 def slot_weights(weights, n_hits, K):
@@ -139,10 +126,34 @@ def test_every_class_and_both_routes(mode):
     bare = call(weights=weights, want_covered=False)
     assert bare[2] is None
     same_counts((bare[0], bare[1], heavy[2], bare[3]), heavy)
+    # the batch route's slots in groups (align_list_group_slots): local, its two or more slots one per group
+    if local:
+        with ctx.hints(align_list_group_slots=1):
+            same_counts(call(weights=weights), heavy)
+            assert aln_amd.hits_align_routes(ctx) == (fused, batched)
     if not local:
         with ctx.hints(align_fused_nonlocal=0):                        # every slot through batches: the route does not show
             same_counts(call(weights=weights), heavy)
             assert aln_amd.hits_align_routes(ctx) == (0, n_used)
+        group = 3 if n_used % 3 else 4
+        assert n_used > group and 0 < n_used % group                   # several groups, the last one shorter
+        with ctx.hints(align_fused_nonlocal=0, align_list_group_slots=group):
+            same_counts(call(weights=weights), heavy)
+            assert aln_amd.hits_align_routes(ctx) == (0, n_used)
+
+
+def test_align_list_group_slots_is_off_on_a_fresh_context_and_round_trips():
+    """the hint alone, on the host: no call is made"""
+    ctx = aln_amd.Context(0)
+    try:
+        assert ctx.get_hint("align_list_group_slots") == 0
+        ctx.set_hint("align_list_group_slots", 7)
+        assert ctx.get_hint("align_list_group_slots") == 7
+        with ctx.hints(align_list_group_slots=2):
+            assert ctx.get_hint("align_list_group_slots") == 2
+        assert ctx.get_hint("align_list_group_slots") == 7
+    finally:
+        ctx.close()
 
 
 # ---- 2. row blocks -----------------------------------------------------------------------------------------------------------------
@@ -274,10 +285,7 @@ class Raw:
                                                     a["counts"], a["covered"])
 
 
-def gap(model=aln_amd.GAP_AFFINE_CONST, align_type=aln_amd.LOCAL):
-    g = aln_amd.AlnGap()
-    g.model, g.align_type, g.gap_init, g.gap_extn = model, align_type, float(GI), float(GE)
-    return g
+gap = cc.gap
 
 
 ARG_QS = ["PAWHEAE", "HEAGAWGHEE"]

@@ -146,6 +146,8 @@ def test_equals_the_batch_route(K, blosum62):
             again = aln_amd.hits_align(ctx, qs, ts, hits, n_hits, alpha, table, 11, 1)
         same_results(again, res)
     assert ctx.get_hint("align_chunk_hits") == 0
+    with ctx.hints(align_list_group_slots=1):                          # groups lists read on the host: nothing here
+        same_results(aln_amd.hits_align(ctx, qs, ts, hits, n_hits, alpha, table, 11, 1), res)
 
 
 def test_every_length_class_equals_the_batch_route(blosum62):

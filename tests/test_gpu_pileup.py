@@ -3,7 +3,7 @@
 comparison is equality: letters, tpos and spans against the numpy restatement over the oracle's pair lists (pileup_cases), the
 records byte for byte against aln_hits_align called without lists and lines.
 
-  1  every fused length class and the batch route in one row, a duplicated slot, chunks, align_fused_nonlocal = 0
+  1  every fused length class and the batch route in one row, a duplicated slot, chunks, align_fused_nonlocal = 0, list groups
   2  the outputs singly, line_stride at the longest query and beyond
   3  the pileup rebuilt from hits_align's lists; counts_from_pileup against hits_column_counts
   4  a row block with q_begin > 0
@@ -33,17 +33,7 @@ K5 = 5
 used_slots = pu.used_slots
 
 
-def hit_array(t_idx, n_hits, lists, local):
-    """the slots t_idx[rows, K] as aln_hit: local slots carry the oracle's score and the cell its list starts from (the entry
-    before (Q-1, T-1)); non-local slots carry values that must not be read; unused slots hold a template that must not be"""
-    hits = np.zeros(t_idx.shape, dtype=aln_amd.HIT_DTYPE)
-    hits["t"] = t_idx
-    hits["q_end"], hits["t_end"], hits["score"] = -7, 1 << 20, -1e30
-    for (r, k), (score, pl) in zip(used_slots(n_hits, t_idx.shape[1]), lists):
-        if local:
-            hits["score"][r, k] = score
-            hits["q_end"][r, k], hits["t_end"][r, k] = pl[-2]
-    return hits
+hit_array = cc.hit_array
 
 
 def spans_array(spans):
@@ -117,8 +107,18 @@ def test_every_class_and_both_routes(mode):
         with ctx.hints(align_chunk_hits=chunk):
             same_pileup(call(), whole)
             assert aln_amd.hits_align_routes(ctx) == (fused, batched)
+    # the batch route's slots in groups (align_list_group_slots): local, its two or more slots one per group
+    if local:
+        with ctx.hints(align_list_group_slots=1):
+            same_pileup(call(), whole)
+            assert aln_amd.hits_align_routes(ctx) == (fused, batched)
     if not local:
         with ctx.hints(align_fused_nonlocal=0):
+            same_pileup(call(), whole)
+            assert aln_amd.hits_align_routes(ctx) == (0, n_used)
+        group = 3 if n_used % 3 else 4
+        assert n_used > group and 0 < n_used % group                   # several groups, the last one shorter
+        with ctx.hints(align_fused_nonlocal=0, align_list_group_slots=group):
             same_pileup(call(), whole)
             assert aln_amd.hits_align_routes(ctx) == (0, n_used)
 
@@ -316,10 +316,7 @@ class Raw:
         return aln_amd.lib().aln_hits_pileup(gpu_util.ctx().h, ref(a["q"]), ref(a["templ"]), ref(a["sub"]), ref(a["g"]), *tail)
 
 
-def gap(model=aln_amd.GAP_AFFINE_CONST, align_type=aln_amd.LOCAL):
-    g = aln_amd.AlnGap()
-    g.model, g.align_type, g.gap_init, g.gap_extn = model, align_type, float(GI), float(GE)
-    return g
+gap = cc.gap
 
 
 def stride_and_slot_checks(raw, hits, n_hits, refused, bad_t):
