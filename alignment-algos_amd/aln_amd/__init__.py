@@ -104,7 +104,7 @@ EXPORTS = [
     "aln_hits_zscores", "aln_hits_align", "aln_hits_align_last_routes", "aln_score_profiles_vs_all", "aln_search_topk_profiles",
     "aln_hits_align_profiles", "aln_hits_zscores_profiles", "aln_hits_align_multi",
     "aln_hits_align_multi_profiles", "aln_hits_column_counts", "aln_hits_column_counts_profiles",
-    "aln_hits_pileup", "aln_hits_pileup_profiles",
+    "aln_hits_pileup", "aln_hits_pileup_profiles", "aln_hits_weights", "aln_hits_weights_profiles",
 ]
 COMM_ID_BYTES = 128
 
@@ -207,6 +207,12 @@ def lib():
                                                C.POINTER(AlnGap), C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip,
                                                C.POINTER(AlnHitAlignment), C.POINTER(AlnHitSpan), C.POINTER(C.c_uint8),
                                                C.POINTER(C.c_uint16), C.c_int32]
+        L.aln_hits_weights.argtypes = [C.c_void_p, C.POINTER(AlnSeqs), C.POINTER(AlnSeqs), C.POINTER(AlnSubmatrix), C.POINTER(AlnGap),
+                                       C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.c_int32, C.POINTER(AlnHitAlignment),
+                                       _ip, _lp, _ip, _ip]
+        L.aln_hits_weights_profiles.argtypes = [C.c_void_p, C.POINTER(AlnQProfiles), C.POINTER(AlnSeqs), C.POINTER(AlnSeqs),
+                                                C.POINTER(AlnGap), C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.c_int32,
+                                                C.POINTER(AlnHitAlignment), _ip, _lp, _ip, _ip]
         L.aln_hits_align_last_routes.argtypes = [C.c_void_p, _lp]
         L.aln_hmap2_gap_arrays.argtypes = [_fp, C.c_int64, C.c_float, C.c_float, C.c_float, _fp, _fp]
         L.aln_batch_plane_bytes_per_cell.argtypes = [C.c_void_p]
@@ -755,6 +761,61 @@ def hits_pileup_profiles(ctx, profiles, templates, hits, n_hits, gi, ge, consens
     hits_align_profiles — it only enters the records' identity).  -> the 5-tuple of hits_pileup."""
     return _pileup(ctx, _ProfileSide("aln_hits_pileup_profiles", profiles, templates, consensus), hits, n_hits, gi, ge, q_begin,
                    align_type, want_letters, want_tpos, want_spans, line_stride)
+
+
+def _weights(ctx, side, hits, n_hits, gi, ge, w_max, q_begin, align_type, want_raw, want_counts, want_covered):
+    hits, n_hits, rows, K = _hit_list(hits, n_hits)
+    cut = [int(side.offsets[q_begin + r] - side.offsets[q_begin]) for r in range(rows + 1)]
+    rec = np.zeros((rows, K), dtype=HIT_ALIGNMENT_DTYPE)
+    weights = np.zeros((rows, K), dtype=np.int32)
+    raw = np.zeros((rows, K), dtype=np.int64) if want_raw else None
+    counts = np.zeros((cut[rows], side.n_letters), dtype=np.int32) if want_counts else None
+    covered = np.zeros(cut[rows], dtype=np.int32) if want_covered else None
+    rc = side.call(ctx, _const_gap(align_type, gi, ge), q_begin, q_begin + rows, int(K), _as(hits, AlnHit), _i(n_hits), int(w_max),
+                   _as(rec, AlnHitAlignment), _i(weights), raw.ctypes.data_as(_lp) if want_raw else None,
+                   _i(counts) if want_counts else None, _i(covered) if want_covered else None)
+    if rc != 0 and not (rec["status"] == rc).any():
+        _check(rc, ctx.h)
+    return rec, weights, raw, ([counts[cut[r]:cut[r + 1]] for r in range(rows)] if want_counts else None), covered, rc
+
+
+def hits_weights(ctx, queries, templates, hits, n_hits, alphabet, table, gi, ge, w_max=1000, q_begin=0, align_type=LOCAL, want_raw=True,
+                 want_counts=True, want_covered=True):
+    """aln_hits_weights: Henikoff position-based weights of the used slots of hits[rows, K], read off the query-anchored pileup
+    (hits_pileup's letters) on the device, and the column counts under those weights — no pileup is downloaded and every hit is
+    swept once.  Per query position p: n_p[a] slots show letter a, k_p letters occur; raw[k] = sum over the slot's letters of
+    floor(2^24 / (k_p n_p[a])); weight[k] = 0 where raw[k] == 0, else max(1, floor(w_max raw[k] / max raw of the row)), w_max in
+    1..65535.  -> rec[rows, K] (hits_align's records without lists), weights int32 [rows, K], raw int64 [rows, K] (or None),
+    counts and covered as hits_column_counts(..., weights=weights) returns them (or None), rc (0, or the lowest per-slot status).
+    Raises only when the call wrote nothing."""
+    return _weights(ctx, _ResidueSide("aln_hits_weights", queries, templates, alphabet, table), hits, n_hits, gi, ge, w_max, q_begin,
+                    align_type, want_raw, want_counts, want_covered)
+
+
+def hits_weights_profiles(ctx, profiles, templates, hits, n_hits, gi, ge, consensus=None, w_max=1000, q_begin=0, align_type=LOCAL,
+                          want_raw=True, want_counts=True, want_covered=True):
+    """aln_hits_weights_profiles: hits_weights for the hits of a profile search (profiles: a QueryProfiles, whose alphabet the
+    letters are counted in; consensus as in hits_align_profiles — it only enters the records' identity).
+    -> the 6-tuple of hits_weights."""
+    return _weights(ctx, _ProfileSide("aln_hits_weights_profiles", profiles, templates, consensus), hits, n_hits, gi, ge, w_max,
+                    q_begin, align_type, want_raw, want_counts, want_covered)
+
+
+def weights_from_pileup(letters_row, alphabet, w_max):
+    """The weights of hits_weights restated over a pileup, pure numpy, int64 throughout.  letters_row: [K, L] letters of one
+    query (one row of hits_pileup's letters; L = its residues or more); w_max: 1..65535.  -> (weights int64 [K], raw int64 [K])."""
+    rows = np.asarray(letters_row, dtype=np.uint8)
+    assert rows.ndim == 2 and 1 <= int(w_max) <= 65535
+    is_a = np.stack([rows == ord(ch) for ch in alphabet], axis=0) if len(alphabet) else np.zeros((0,) + rows.shape, bool)
+    n = is_a.sum(axis=1, dtype=np.int64)                              # [n letters, L]
+    k = (n > 0).sum(axis=0, dtype=np.int64)                           # [L]
+    term = np.int64(1 << 24) // np.maximum(k[None, :] * n, 1)         # [n letters, L]; read only where n > 0
+    raw = (is_a * term[:, None, :]).sum(axis=(0, 2), dtype=np.int64)
+    M = int(raw.max(initial=0))
+    weights = np.zeros(rows.shape[0], np.int64)
+    if M > 0:
+        weights = np.where(raw > 0, np.maximum(np.int64(w_max) * raw // np.int64(M), 1), 0).astype(np.int64)
+    return weights, raw
 
 
 def counts_from_pileup(letters_row, alphabet, weights=None):

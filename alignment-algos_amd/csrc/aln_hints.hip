@@ -45,6 +45,7 @@ const HintDef kDefs[] = {
     {"zscore_rows_per_chunk", "ALN_ZSCORE_ROWS_PER_CHUNK", false, &aln_hints::zscore_rows_per_chunk},
     {"align_chunk_hits", "ALN_ALIGN_CHUNK_HITS", false, &aln_hints::align_chunk_hits},
     {"align_list_group_slots", "ALN_ALIGN_LIST_GROUP_SLOTS", false, &aln_hints::align_list_group_slots},
+    {"weights_group_rows", "ALN_WEIGHTS_GROUP_ROWS", false, &aln_hints::weights_group_rows},
     {"align_fused_nonlocal", "ALN_ALIGN_FUSED_NONLOCAL", false, &aln_hints::align_fused_nonlocal},
     {"align_rows_per_chunk", "ALN_ALIGN_ROWS_PER_CHUNK", false, &aln_hints::align_rows_per_chunk},
     {"enum_heavy_first", "ALN_ENUM_HEAVY_FIRST", false, &aln_hints::enum_heavy_first},

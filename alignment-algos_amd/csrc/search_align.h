@@ -2,7 +2,7 @@
 // observers that turn a row sweep into the strip bytes and the final cell's pointer, strip_walk, the walk back through the
 // strip, and the ONE pair of kernels around them, hit_local_kernel / hit_global_kernel<R, Side, Job>: what becomes of a walk
 // entry is the job's — ListJob here (search_align.hip: the pair list), CountJob in search_counts.hip (the column counts),
-// PileupJob in search_pileup.hip (the query-anchored rows).
+// PileupJob in search_pileup.h (the query-anchored rows: search_pileup.hip downloads them, search_weights.hip keeps them).
 // search_align_multi.hip (several rounds per hit) has a kernel of its own around the same walk.  Host: where a slot's record,
 // list and lines go (AlignOut, put_fused, pair_desc), the routing of slots (route_slots) and the fused route's driver that
 // the four entries run their chunks through (FusedRoute, over score_common.h's DeviceBufs, STRY / RTRY and launch_classes).

@@ -224,6 +224,9 @@ int aln_has_gfx950(void);
  *   "align_list_group_slots"        aln_hits_column_counts, aln_hits_pileup: batch-route slots whose pair lists are held on the host at a
  *                                   time; 0 (default) = as many as keep the lists below 256 MiB; a value never lifts that bound
  *                                   (environment default ALN_ALIGN_LIST_GROUP_SLOTS).  Same results.
+ *   "weights_group_rows"            aln_hits_weights, aln_hits_weights_profiles: query rows whose letters rows (K x the block's longest
+ *                                   Q-2 bytes per row) are resident on the device at a time; 0 (default) = as many as keep them below
+ *                                   1 GiB; a value never lifts that budget (environment default ALN_WEIGHTS_GROUP_ROWS).  Same results.
  *   "align_fused_nonlocal"          aln_hits_align: 1 (default) = hits of the four non-local align types are aligned by the fused
  *                                   kernel where it applies; 0 = they all go through resident batches (environment default
  *                                   ALN_ALIGN_FUSED_NONLOCAL).  Same results.
@@ -665,6 +668,56 @@ int aln_hits_pileup_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, const 
                              const aln_seqs* templates, const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K,
                              const aln_hit* hits, const int32_t* n_hits, aln_hit_alignment* out, aln_hit_span* spans,
                              char* letters, uint16_t* tpos, int32_t line_stride);
+/* ---- position-based sequence weights of search hits: from a round's hits to weights and weighted counts, on the device ---- */
+/* Before the hits of a round become the next round's profile, redundant hits are weighted down: forty near-copies of one
+ * homolog must not out-vote five distant ones.  These are Henikoff's position-based weights, read off the pileup above without
+ * the pileup leaving the device, and — when wanted — the column counts under those weights, every hit swept once.
+ * Everything is exact integer arithmetic: the result depends on neither the launch order, the chunking nor the route.
+ * For a query row r of the block take the pileup aln_hits_pileup defines for its slots k < n_hits[r]: the letters rows
+ * L[k][p], p = 0 .. Q-3.  A slot CONTRIBUTES exactly when it does there: status 0 and, ALN_LOCAL, score > 0.  Only letters of
+ * the call's alphabet count; '-', '.' and NUL never do.  Per position p:
+ *   n_p[a]     the number of contributing slots with L[k][p] == alphabet[a];
+ *   k_p        the number of letters a with n_p[a] > 0.
+ * Per slot:
+ *   raw[k]     the sum, over the positions p where L[k][p] is a letter a, of floor(2^24 / (k_p * n_p[a])), an int64; 0 for a
+ *              slot that does not contribute or has no aligned letter;
+ *   M          max_k raw[k] over the row;
+ *   weight[k]  0 where raw[k] == 0, otherwise max(1, floor(w_max * raw[k] / M)) in 64-bit integers: the row's heaviest slot
+ *              gets exactly w_max.
+ * w_max is in 1..65535, the weights aln_hits_column_counts accepts.  (The denominator is at most 30 * 1024, raw is below 2^40
+ * and w_max * raw below 2^56.)  The query itself is not a member of the stack: a caller who wants it counted lists it as a hit.
+ * Slots, records, routes and statuses are aln_hits_pileup's: out[s] is, byte for byte, the record aln_hits_align writes for the
+ * slot when called with pairs == NULL and no line group; a slot that fails (a falsified local score: ALN_E_ARG) does not
+ * contribute and the call goes on.  weights (required) and raw (may be NULL) are rows x K; unused slots hold 0.
+ * counts and covered (each may be NULL, independently) are, byte for byte, what aln_hits_column_counts returns for the same
+ * hits with `weights` set to this call's weights, in its layout.
+ * Device side (csrc/search_weights.hip): the letters rows of a group of consecutive queries stay on the device in slot order
+ * (rows x K x the block's longest Q-2 bytes, at most 1 GiB per group; hint "weights_group_rows"); fused hits write them
+ * through aln_hits_pileup's kernels, the slots of the batch route are laid out on the host and uploaded; then a column tally
+ * (one wave per query and 64 positions, a 32-counter histogram per position in LDS), one wave per slot for raw, one wave per
+ * query for the weights, and the tally once more under the weights.  Only weights, raw, the records and the count rows come down.
+ * aln_hits_align_last_routes reports this call's slots too.
+ * Checks, in this order, nothing written when one fails: NULL hits / n_hits / out, K outside 1..1024 (ALN_E_ARG);
+ * aln_score_all_vs_all's, in its order; NULL weights, w_max outside 1..65535 (ALN_E_ARG); every n_hits[r] in 0..K, every used
+ * slot's t in [0, n_templates) and, local, its end cell in range (ALN_E_ARG); last, an alphabet that holds '.' or '-'
+ * (ALN_E_ARG: the pileup cannot show them as letters).
+ * q_begin == q_end: ALN_OK, nothing written.  Returns the lowest per-slot status, ALN_OK when all are 0. */
+int aln_hits_weights(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
+                     const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K,
+                     const aln_hit* hits, const int32_t* n_hits, int32_t w_max,
+                     aln_hit_alignment* out /* rows x K */, int32_t* weights /* rows x K */,
+                     int64_t* raw /* rows x K, may be NULL */,
+                     int32_t* counts /* (offsets[q_end] - offsets[q_begin]) x sub->n, may be NULL */,
+                     int32_t* covered /* offsets[q_end] - offsets[q_begin], may be NULL */);
+/* The same for the hits of a profile search: the slots, records, routes and consensus pool are aln_hits_pileup_profiles', the
+ * alphabet is profiles->alphabet, and the checks are NULL profiles / templates / gap, then NULL hits / n_hits / out and K;
+ * aln_score_profiles_vs_all's, in its order, with the consensus pool where aln_hits_align_profiles checks it; weights and
+ * w_max; n_hits, t and the end cells; the alphabet.  For profiles derived from residue queries under an integral table every
+ * output is byte-identical to aln_hits_weights' on those residues. */
+int aln_hits_weights_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_seqs* consensus /* may be NULL */,
+                              const aln_seqs* templates, const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K,
+                              const aln_hit* hits, const int32_t* n_hits, int32_t w_max, aln_hit_alignment* out,
+                              int32_t* weights, int64_t* raw, int32_t* counts, int32_t* covered);
 /* Several NON-INTERSECTING local alignments per hit (the second, third .. HSP of a hit; Waterman-Eggert's declumping restated on
  * the reference's recurrence).  ALN_LOCAL only.  For one pair — query of Q residues, template of T, sentinels counted — under a
  * table and constant affine gaps:
@@ -735,7 +788,7 @@ int aln_hits_align_multi_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, c
                                   int32_t max_alignments /* N, 1..16 */, float min_score /* -INFINITY: none */,
                                   int32_t* n_found /* rows x K */, aln_hit_alignment* out /* rows x K x N */,
                                   int32_t* pairs, int32_t pair_stride, char* tlines, char* qlines, int32_t line_stride, int32_t* lengths);
-/* out[0]: the used slots the last aln_hits_align / aln_hits_align_profiles / aln_hits_align_multi / aln_hits_align_multi_profiles / aln_hits_column_counts(_profiles) / aln_hits_pileup(_profiles) call on this context sent through a fused kernel,
+/* out[0]: the used slots the last aln_hits_align / aln_hits_align_profiles / aln_hits_align_multi / aln_hits_align_multi_profiles / aln_hits_column_counts(_profiles) / aln_hits_weights(_profiles) / aln_hits_pileup(_profiles) call on this context sent through a fused kernel,
  * out[1]: through resident batches; { 0, 0 } before any call and after a call that failed its checks.  NULL argument: ALN_E_ARG. */
 int aln_hits_align_last_routes(const aln_ctx* ctx, int64_t out[2]);
 
