@@ -92,6 +92,13 @@ class AlnHitSpan(C.Structure):
 
 HIT_SPAN_DTYPE = np.dtype([("q_lo", np.int32), ("q_hi", np.int32), ("t_lo", np.int32), ("t_hi", np.int32)])
 
+
+class AlnHitPurge(C.Structure):
+    _fields_ = [("keeper", C.c_int32), ("same", C.c_int32), ("overlap", C.c_int32), ("letters", C.c_int32)]
+
+
+HIT_PURGE_DTYPE = np.dtype([("keeper", np.int32), ("same", np.int32), ("overlap", np.int32), ("letters", np.int32)])
+
 EXPORTS = [
     "aln_ctx_create", "aln_ctx_destroy", "aln_error_string", "aln_last_error", "aln_ctx_synchronize", "aln_has_gfx950",
     "aln_batch_create", "aln_batch_destroy", "aln_batch_n_pairs", "aln_batch_device_bytes", "aln_batch_dp",
@@ -105,6 +112,7 @@ EXPORTS = [
     "aln_hits_align_profiles", "aln_hits_zscores_profiles", "aln_hits_align_multi",
     "aln_hits_align_multi_profiles", "aln_hits_column_counts", "aln_hits_column_counts_profiles",
     "aln_hits_pileup", "aln_hits_pileup_profiles", "aln_hits_weights", "aln_hits_weights_profiles",
+    "aln_hits_purge", "aln_hits_purge_profiles",
 ]
 COMM_ID_BYTES = 128
 
@@ -213,6 +221,13 @@ def lib():
         L.aln_hits_weights_profiles.argtypes = [C.c_void_p, C.POINTER(AlnQProfiles), C.POINTER(AlnSeqs), C.POINTER(AlnSeqs),
                                                 C.POINTER(AlnGap), C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.c_int32,
                                                 C.POINTER(AlnHitAlignment), _ip, _lp, _ip, _ip]
+        L.aln_hits_purge.argtypes = [C.c_void_p, C.POINTER(AlnSeqs), C.POINTER(AlnSeqs), C.POINTER(AlnSubmatrix), C.POINTER(AlnGap),
+                                     C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.c_int32, C.c_int32, C.c_int32,
+                                     C.POINTER(AlnHitAlignment), C.POINTER(AlnHitPurge), _ip, _lp, _ip, _ip]
+        L.aln_hits_purge_profiles.argtypes = [C.c_void_p, C.POINTER(AlnQProfiles), C.POINTER(AlnSeqs), C.POINTER(AlnSeqs),
+                                              C.POINTER(AlnGap), C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.c_int32,
+                                              C.c_int32, C.c_int32, C.POINTER(AlnHitAlignment), C.POINTER(AlnHitPurge), _ip, _lp, _ip,
+                                              _ip]
         L.aln_hits_align_last_routes.argtypes = [C.c_void_p, _lp]
         L.aln_hmap2_gap_arrays.argtypes = [_fp, C.c_int64, C.c_float, C.c_float, C.c_float, _fp, _fp]
         L.aln_batch_plane_bytes_per_cell.argtypes = [C.c_void_p]
@@ -816,6 +831,80 @@ def weights_from_pileup(letters_row, alphabet, w_max):
     if M > 0:
         weights = np.where(raw > 0, np.maximum(np.int64(w_max) * raw // np.int64(M), 1), 0).astype(np.int64)
     return weights, raw
+
+
+def _purge(ctx, side, hits, n_hits, gi, ge, max_identity, min_overlap, w_max, q_begin, align_type, want_weights, want_raw, want_counts,
+           want_covered):
+    hits, n_hits, rows, K = _hit_list(hits, n_hits)
+    cut = [int(side.offsets[q_begin + r] - side.offsets[q_begin]) for r in range(rows + 1)]
+    rec = np.zeros((rows, K), dtype=HIT_ALIGNMENT_DTYPE)
+    purge = np.zeros((rows, K), dtype=HIT_PURGE_DTYPE)
+    weights = np.zeros((rows, K), dtype=np.int32) if want_weights else None
+    raw = np.zeros((rows, K), dtype=np.int64) if want_weights and want_raw else None
+    counts = np.zeros((cut[rows], side.n_letters), dtype=np.int32) if want_weights and want_counts else None
+    covered = np.zeros(cut[rows], dtype=np.int32) if want_weights and want_covered else None
+    rc = side.call(ctx, _const_gap(align_type, gi, ge), q_begin, q_begin + rows, int(K), _as(hits, AlnHit), _i(n_hits),
+                   int(max_identity), int(min_overlap), int(w_max), _as(rec, AlnHitAlignment), _as(purge, AlnHitPurge),
+                   _i(weights) if weights is not None else None, raw.ctypes.data_as(_lp) if raw is not None else None,
+                   _i(counts) if counts is not None else None, _i(covered) if covered is not None else None)
+    if rc != 0 and not (rec["status"] == rc).any():
+        _check(rc, ctx.h)
+    return (rec, purge, weights, raw, ([counts[cut[r]:cut[r + 1]] for r in range(rows)] if counts is not None else None), covered, rc)
+
+
+def hits_purge(ctx, queries, templates, hits, n_hits, alphabet, table, gi, ge, max_identity=90, min_overlap=50, w_max=1000, q_begin=0,
+               align_type=LOCAL, want_weights=True, want_raw=True, want_counts=True, want_covered=True):
+    """aln_hits_purge: near-identical hits purged on the device, and the weights of the survivors.  Over the query-anchored
+    pileup of the used slots of hits[rows, K] (hits_pileup's letters, which stay on the device): slot k is NEAR an earlier slot
+    j when their rows overlap in at least one letter position, 100 overlap >= min_overlap letters(k) and 100 same >=
+    max_identity overlap; in ascending order a slot with a letter is kept unless it is near a KEPT earlier slot, whose smallest
+    is then its keeper.  max_identity: 1..101 (101: nothing is purged); min_overlap: 0..100.  The weights, raw, counts and
+    covered are hits_weights' over the pileup whose slots that are not kept show '.' everywhere (want_weights=False: purge only).
+    -> rec[rows, K] (hits_align's records without lists), purge[rows, K] (fields keeper, same, overlap, letters: kept
+    {k, 0, 0, letters}; purged by j {j, same, overlap, letters}; every other slot {-1, 0, 0, 0}), weights, raw, counts, covered
+    (as hits_weights returns them; None for what was not asked), rc (0, or the lowest per-slot status).  Raises only when the
+    call wrote nothing."""
+    return _purge(ctx, _ResidueSide("aln_hits_purge", queries, templates, alphabet, table), hits, n_hits, gi, ge, max_identity,
+                  min_overlap, w_max, q_begin, align_type, want_weights, want_raw, want_counts, want_covered)
+
+
+def hits_purge_profiles(ctx, profiles, templates, hits, n_hits, gi, ge, consensus=None, max_identity=90, min_overlap=50, w_max=1000,
+                        q_begin=0, align_type=LOCAL, want_weights=True, want_raw=True, want_counts=True, want_covered=True):
+    """aln_hits_purge_profiles: hits_purge for the hits of a profile search (profiles: a QueryProfiles, whose alphabet the
+    letters are; consensus as in hits_align_profiles — it only enters the records' identity).  -> the 7-tuple of hits_purge."""
+    return _purge(ctx, _ProfileSide("aln_hits_purge_profiles", profiles, templates, consensus), hits, n_hits, gi, ge, max_identity,
+                  min_overlap, w_max, q_begin, align_type, want_weights, want_raw, want_counts, want_covered)
+
+
+def purge_from_pileup(letters_row, alphabet, max_identity, min_overlap):
+    """The purge of hits_purge restated over a pileup, pure numpy, int64 throughout.  letters_row: [K, L] letters of one query
+    (one row of hits_pileup's letters; L = its residues or more); max_identity: 1..101; min_overlap: 0..100.
+    -> (keeper, same, overlap, letters), four int64 [K] arrays: hits_purge's record per slot."""
+    rows = np.asarray(letters_row, dtype=np.uint8)
+    assert rows.ndim == 2 and 1 <= int(max_identity) <= 101 and 0 <= int(min_overlap) <= 100
+    K = rows.shape[0]
+    is_letter = np.isin(rows, np.frombuffer(alphabet.encode(), np.uint8))
+    letters = is_letter.sum(axis=1, dtype=np.int64)
+    keeper = np.full(K, -1, np.int64)
+    same = np.zeros(K, np.int64)
+    overlap = np.zeros(K, np.int64)
+    kept = []
+    for k in range(K):
+        if letters[k] == 0:
+            continue
+        keeper[k] = k
+        if kept:
+            both = is_letter[kept] & is_letter[k][None, :]
+            ov = both.sum(axis=1, dtype=np.int64)
+            sm = (both & (rows[kept] == rows[k][None, :])).sum(axis=1, dtype=np.int64)
+            near = (ov >= 1) & (100 * ov >= np.int64(min_overlap) * letters[k]) & (100 * sm >= np.int64(max_identity) * ov)
+            if near.any():
+                first = int(np.argmax(near))
+                keeper[k], same[k], overlap[k] = kept[first], sm[first], ov[first]
+                continue
+        kept.append(k)
+    letters = np.where(keeper >= 0, letters, 0)
+    return keeper, same, overlap, letters
 
 
 def counts_from_pileup(letters_row, alphabet, weights=None):

@@ -105,7 +105,7 @@ struct aln_hints {
   int zscore_rows_per_chunk = 0;  // aln_hits_zscores_profiles: 1 = every chunk uploads the profile rows of its own query rows; 0 = by the 1 GiB budget
   int align_chunk_hits = 0;  // aln_hits_align: hit slots whose strips are resident at a time; 0 = by the 1 GiB budget (never lifts it)
   int align_list_group_slots = 0;  // aln_hits_column_counts, aln_hits_pileup: batch-route slots whose pair lists the host holds at a time; 0 = by the 256 MiB bound (never lifts it)
-  int weights_group_rows = 0;     // aln_hits_weights: query rows whose letters rows are resident on the device at a time; 0 = by the 1 GiB budget (never lifts it)
+  int weights_group_rows = 0;     // aln_hits_weights, aln_hits_purge: query rows whose letters rows are resident on the device at a time; 0 = by the 1 GiB budget (never lifts it)
   int align_fused_nonlocal = 1;   // 0: aln_hits_align sends hits of the four non-local align types through resident batches
   int align_rows_per_chunk = 0;   // aln_hits_align_profiles: 1 = every chunk uploads the profile rows of its own hits; 0 = by the 1 GiB budget
   int plane_row_align = 8;   // cells a plane row is padded to when a batch is created (8, 16, 32 or 64)

@@ -2,7 +2,8 @@
 // hit_local_kernel / hit_global_kernel<R, Side, PileupJob> (search_align.h), its argument blocks, the host's restatement of
 // one row from a pair list (the batch route) and the launch of the kernel pair.  aln_hits_pileup (search_pileup.hip, whose
 // head tells where the bytes come from and how the gap pass is ordered) downloads the rows; aln_hits_weights
-// (search_weights.hip) keeps the letters rows of a group of queries on the device and reads the weights off them.  The
+// (search_weights.hip) keeps the letters rows of a group of queries on the device and reads the weights off them, and
+// aln_hits_purge (search_purge.hip) the purge decision before that (both through search_stack.h's HitStack).  The
 // kernels are instantiated ONCE, in search_pileup.hip: launch_pileup_job is an ordinary function defined there.
 #pragma once
 #include <climits>

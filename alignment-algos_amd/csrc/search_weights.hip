@@ -21,26 +21,20 @@
 //                    `covered` in column 31: the weight of every slot whose letter is neither '.' nor NUL).
 // Only weights, raw, the hits' records and the count rows come down.  A block whose stack would exceed kStackBudget is cut into
 // groups of consecutive queries (hint weights_group_rows asks for fewer rows); a group runs the fused route (FusedRoute), the
-// batch route (for_list_groups) and the four kernels over its own queries.
+// batch route (for_list_groups) and the four kernels over its own queries.  The stack's construction is search_stack.h's
+// HitStack, which aln_hits_purge (search_purge.hip) builds the same stack with; the kernels of this file reach it through
+// launch_scatter_rows and launch_weight_kernels.
 #include <algorithm>
 #include <climits>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#include "search_pileup.h"
+#include "search_stack.h"
 
 namespace aln {
 
-constexpr size_t kStackBudget = (size_t)1 << 30;        // bytes of letters rows resident at a time
-constexpr int kSpareCol = 31;                           // the alphabet has at most 30 letters: k_p, or covered
 constexpr int kHistStride = 33;                         // words between the histograms of neighbouring lanes
-
-struct WeightQuery {        // one query row of the group
-  int64_t row;              // the count row of its position 0 (query row 1), relative to the group's first count row
-  int32_t len;              // Q - 2
-  int32_t pad;
-};
 
 // a chunk's letters rows into their slots of the stack: one wave per hit
 __global__ __launch_bounds__(64) void scatter_rows_kernel(const char* __restrict__ src, char* __restrict__ stack,
@@ -128,178 +122,47 @@ __global__ __launch_bounds__(64) void normalise_kernel(const int64_t* __restrict
   }
 }
 
+// scatter_rows_kernel and the four launches over a complete group behind ordinary functions (search_stack.h): the kernels are
+// instantiated in this file alone
+int launch_scatter_rows(aln_ctx* ctx, const char* src, char* stack, const int32_t* slot, int64_t stride, size_t n) {
+  hipLaunchKernelGGL(scatter_rows_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, src, stack, slot, stride);
+  STRY(hipGetLastError());
+  return ALN_OK;
+}
+
+int launch_weight_kernels(aln_ctx* ctx, const WeightLaunch& w) {
+  const dim3 tiles((unsigned)((w.stride + 63) / 64), (unsigned)w.gn), wave(64);
+  hipLaunchKernelGGL(column_tally_kernel<false>, tiles, wave, 0, ctx->stream, w.stack, w.stride, w.K, w.qr, w.idx, w.wt, w.np);
+  STRY(hipGetLastError());
+  hipLaunchKernelGGL(slot_raw_kernel, dim3((unsigned)(w.gn * w.K)), wave, 0, ctx->stream, w.stack, w.stride, w.K, w.qr, w.idx, w.np, w.raw);
+  STRY(hipGetLastError());
+  hipLaunchKernelGGL(normalise_kernel, dim3((unsigned)w.gn), wave, 0, ctx->stream, w.raw, w.K, w.w_max, w.wt);
+  STRY(hipGetLastError());
+  if (w.cnt) {
+    STRY(hipMemsetAsync(w.cnt, 0, w.g_rows * 128, ctx->stream));                          // the sentinel rows stay zero
+    hipLaunchKernelGGL(column_tally_kernel<true>, tiles, wave, 0, ctx->stream, w.stack, w.stride, w.K, w.qr, w.idx, w.wt, w.cnt);
+    STRY(hipGetLastError());
+  }
+  return ALN_OK;
+}
+
 // The shared body of aln_hits_weights and aln_hits_weights_profiles (run: prepared; `queries`: the pool the query lengths are
-// read from — hit_entry's pool, search_align.h).
+// read from — hit_entry's pool, search_align.h).  The stack's construction and the weights' buffers: search_stack.h.
 static int weights_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const aln_hit* hits, const int32_t* n_hits, int32_t w_max,
                          aln_hit_alignment* out, int32_t* weights, int64_t* raw, int32_t* counts, int32_t* covered) {
   aln_ctx* ctx = run.ctx;
-  const aln_seqs* templates = run.templates;
   if (!weights || w_max < 1 || w_max > 65535) return ALN_E_ARG;
-  const int rows = run.rows;
-  if (rows == 0) return ALN_OK;
-  const int n_alpha = run.prof ? run.prof->n : run.sub->n;
-  const char* alphabet = run.prof ? run.prof->alphabet : run.sub->alphabet;
-  const int64_t row0 = queries->offsets[run.q_begin];
-  const size_t n_rows = (size_t)(queries->offsets[run.q_end] - row0);
-  int64_t maxw = 1;                                          // the stack's stride: the longest Q - 2 of the block
-  for (int q = run.q_begin; q < run.q_end; ++q) maxw = std::max<int64_t>(maxw, queries->offsets[q + 1] - queries->offsets[q] - 2);
-
-  // route_slots' walk (every used slot validated and described for its route), then the alphabet; nothing written before
-  SlotRoutes sr;
-  int rc = route_slots(run, queries, K, hits, n_hits, hit_kernel_classes(run), run.local, sr);
+  if (run.rows == 0) return ALN_OK;
+  HitStack st(run, queries, K, out);
+  const int rc = st.route(hits, n_hits);                     // nothing written before
   if (rc != ALN_OK) return rc;
-  int8_t idx[256];
-  memset(idx, -1, sizeof idx);
-  for (int i = 0; i < n_alpha; ++i) {
-    if (alphabet[i] == '.' || alphabet[i] == '-') return ALN_E_ARG;      // the pileup could not show them as letters
-    idx[(unsigned char)alphabet[i]] = (int8_t)i;
-  }
-  ctx->align_routes[0] = (int64_t)sr.fast.size(); ctx->align_routes[1] = (int64_t)sr.bq.size();
-
-  const size_t n_slots = (size_t)rows * K;
-  const bool want_counts = counts || covered;
-  memset(weights, 0, n_slots * 4);
-  if (raw) memset(raw, 0, n_slots * 8);
-  if (counts) memset(counts, 0, n_rows * (size_t)n_alpha * 4);
-  if (covered) memset(covered, 0, n_rows * 4);
-  AlignOut ao = {out, nullptr, 0, nullptr, nullptr, 0, nullptr};
-  ao.clear_unused(rows, K, n_hits);
-
-  // groups of consecutive queries: as many rows as keep the stack below the budget; the hint only asks for fewer
-  const size_t dw = (size_t)maxw;
-  size_t group = std::max<size_t>(kStackBudget / ((size_t)K * dw), 1);
-  if (ctx->hints.weights_group_rows > 0) group = std::min(group, (size_t)ctx->hints.weights_group_rows);
-  group = std::min(std::min(group, (size_t)rows), (size_t)32768);   // (a group's rows are a launch's blockIdx.y)
-  size_t max_grows = 1;                                      // the most count rows of a group
-  for (size_t g0 = 0; g0 < (size_t)rows; g0 += group) {
-    const size_t g1 = std::min(g0 + group, (size_t)rows);
-    max_grows = std::max(max_grows, (size_t)(queries->offsets[run.q_begin + g1] - queries->offsets[run.q_begin + g0]));
-  }
-
-  DeviceBufs own(run);
-  char* dstack = nullptr; int8_t* didx = nullptr; WeightQuery* dqr = nullptr;
-  int32_t *dnp = nullptr, *dcnt = nullptr, *dwt = nullptr; int64_t* draw = nullptr;
-  STRY(own.get(dstack, group * K * dw));
-  STRY(own.get(didx, 256));
-  STRY(own.get(dqr, group));
-  STRY(own.get(dnp, max_grows * 32));
-  if (want_counts) STRY(own.get(dcnt, max_grows * 32));
-  STRY(own.get(dwt, group * K));
-  STRY(own.get(draw, group * K));
-  STRY(hipMemcpyAsync(didx, idx, sizeof idx, hipMemcpyHostToDevice, ctx->stream));        // (alive until the first synchronisation)
-  std::vector<WeightQuery> hqr(group);
-  std::vector<int32_t> hcnt(want_counts ? max_grows * 32 : 0);
-  std::vector<char> hrow(dw);
-
-  size_t f0 = 0, b0 = 0;                                     // the group's first fused hit and first batch slot (both row-major)
-  for (size_t g0 = 0; g0 < (size_t)rows; g0 += group) {
-    const size_t g1 = std::min(g0 + group, (size_t)rows), gn = g1 - g0;
-    const size_t slot0 = g0 * K, slot1 = g1 * K;
-    const int64_t grow0 = queries->offsets[run.q_begin + g0];
-    const size_t g_rows = (size_t)(queries->offsets[run.q_begin + g1] - grow0);
-    size_t f1 = f0, b1 = b0;
-    while (f1 < sr.fast.size() && sr.fast_slot[f1] < slot1) ++f1;
-    while (b1 < sr.bq.size() && sr.bslot[b1] < slot1) ++b1;
-    for (size_t r = 0; r < gn; ++r) {
-      const int64_t o = queries->offsets[run.q_begin + g0 + r];
-      hqr[r] = WeightQuery{o - grow0 + 1, (int32_t)(queries->offsets[run.q_begin + g0 + r + 1] - o - 2), 0};
-    }
-    STRY(hipMemcpyAsync(dqr, hqr.data(), gn * sizeof(WeightQuery), hipMemcpyHostToDevice, ctx->stream));
-    STRY(hipMemsetAsync(dstack, '.', gn * K * dw, ctx->stream));
-
-    // the group's fused hits, chunk by chunk: the rows of a chunk, then their move into the stack
-    if (f1 > f0) {
-      std::vector<HitDesc> fast(sr.fast.begin() + f0, sr.fast.begin() + f1);
-      const std::vector<size_t> fast_slot(sr.fast_slot.begin() + f0, sr.fast_slot.begin() + f1);
-      FusedRoute<HitDesc> fr(run, queries, fast);
-      std::vector<int32_t> fast_live(fast.size()), fast_at(fast.size());
-      for (size_t h = 0; h < fast.size(); ++h) {
-        fast_live[h] = (run.local && !(fast[h].score > 0.f)) ? 0 : 1;
-        fast_at[h] = (int32_t)(fast_slot[h] - slot0);
-      }
-      fr.cut(1, true, (int)std::min<int64_t>(maxw, INT_MAX),
-             [&](const HitDesc& d) { return HitNeed{hit_strip_bytes(run, queries, d), 0, 0}; });
-      const size_t max_n = fr.max_n;
-      int32_t *dlive = nullptr, *dat = nullptr; char* dlet = nullptr; PileupRows* drows = nullptr;
-      HitRecords rec;
-      RTRY(fr.begin());
-      STRY(fr.bufs.get(dlive, max_n));
-      STRY(fr.bufs.get(dat, max_n));
-      RTRY(rec.alloc(fr.bufs, max_n));
-      STRY(fr.bufs.get(dlet, max_n * dw));
-      STRY(fr.bufs.get(drows, 1));
-      RTRY(fr.upload_pools());                                 // the templates' characters, on both sides
-      const PileupRows where = {dlive, fr.dtch, dlet, nullptr, nullptr, (int64_t)dw};   // (alive until the first chunk's synchronisation)
-      STRY(hipMemcpyAsync(drows, &where, sizeof(where), hipMemcpyHostToDevice, ctx->stream));
-      for (const FusedChunk& c : fr.chunks) {
-        const size_t n = c.n;
-        RTRY(fr.stage(c, [&]() -> int {
-          STRY(hipMemcpyAsync(dlive, fast_live.data() + c.h0, n * 4, hipMemcpyHostToDevice, ctx->stream));
-          STRY(hipMemcpyAsync(dat, fast_at.data() + c.h0, n * 4, hipMemcpyHostToDevice, ctx->stream));
-          STRY(hipMemsetAsync(dlet, '.', n * dw, ctx->stream));
-          return ALN_OK;
-        }));
-        PileupArgs g = {};
-        g.desc = fr.ddesc; g.strip = fr.dstrip; g.rows = drows; g.res = rec.dres; g.same = rec.dsame;
-        RTRY(launch_pileup_job(fr, c, g));
-        hipLaunchKernelGGL(scatter_rows_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, dlet, dstack, dat, (int64_t)dw);
-        STRY(hipGetLastError());
-        RTRY(rec.enqueue_download(ctx, n));
-        STRY(hipStreamSynchronize(ctx->stream));               // the records' host images are read by the copies until here
-        rec.put(ao, fr, c, fast_slot, [](size_t, size_t, int64_t) {});
-      }
-    }
-
-    // the group's batch slots (for_list_groups, search_align.h): every surviving slot's row laid out here and uploaded
-    if (b1 > b0) {
-      SlotRoutes gs;
-      gs.bq.assign(sr.bq.begin() + b0, sr.bq.begin() + b1);
-      gs.bt.assign(sr.bt.begin() + b0, sr.bt.begin() + b1);
-      gs.bslot.assign(sr.bslot.begin() + b0, sr.bslot.begin() + b1);
-      int up = ALN_OK;
-      rc = for_list_groups(run, queries, gs, ao, [&](size_t slot, int32_t q, int32_t t, const int32_t* l, int n_pairs) {
-        const int64_t Q = queries->offsets[q + 1] - queries->offsets[q];
-        const int64_t to = templates->offsets[t], T = templates->offsets[t + 1] - to;
-        if (Q < 3 || up != ALN_OK) return;
-        memset(hrow.data(), '.', (size_t)(Q - 2));
-        pileup_from_list(l, n_pairs, Q, T, templates->residues + to, hrow.data(), nullptr, nullptr);
-        if (hipMemcpyAsync(dstack + (slot - slot0) * dw, hrow.data(), (size_t)(Q - 2), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-            hipStreamSynchronize(ctx->stream) != hipSuccess) {   // hrow is written again for the next slot
-          ctx->last_error = "aln_hits_weights: upload of a batch slot's row failed";
-          up = ALN_E_HIP;
-        }
-      });
-      RTRY(rc);
-      RTRY(up);
-    }
-
-    // the stack is complete: the tally, the slots' sums, the weights, the weighted tally
-    const dim3 tiles((unsigned)((dw + 63) / 64), (unsigned)gn), wave(64);
-    hipLaunchKernelGGL(column_tally_kernel<false>, tiles, wave, 0, ctx->stream, dstack, (int64_t)dw, (int)K, dqr, didx, dwt, dnp);
-    STRY(hipGetLastError());
-    hipLaunchKernelGGL(slot_raw_kernel, dim3((unsigned)(gn * K)), wave, 0, ctx->stream, dstack, (int64_t)dw, (int)K, dqr, didx, dnp, draw);
-    STRY(hipGetLastError());
-    hipLaunchKernelGGL(normalise_kernel, dim3((unsigned)gn), wave, 0, ctx->stream, draw, (int)K, (int)w_max, dwt);
-    STRY(hipGetLastError());
-    if (want_counts) {
-      STRY(hipMemsetAsync(dcnt, 0, g_rows * 128, ctx->stream));                           // the sentinel rows stay zero
-      hipLaunchKernelGGL(column_tally_kernel<true>, tiles, wave, 0, ctx->stream, dstack, (int64_t)dw, (int)K, dqr, didx, dwt, dcnt);
-      STRY(hipGetLastError());
-      STRY(hipMemcpyAsync(hcnt.data(), dcnt, g_rows * 128, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    STRY(hipMemcpyAsync(weights + slot0, dwt, gn * K * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (raw) STRY(hipMemcpyAsync(raw + slot0, draw, gn * K * 8, hipMemcpyDeviceToHost, ctx->stream));
-    STRY(hipStreamSynchronize(ctx->stream));
-    if (want_counts) {
-      const size_t base = (size_t)(grow0 - row0);
-      for (size_t r = 0; r < g_rows; ++r) {
-        if (counts) memcpy(counts + (base + r) * (size_t)n_alpha, hcnt.data() + r * 32, (size_t)n_alpha * 4);
-        if (covered) covered[base + r] = hcnt[r * 32 + kSpareCol];
-      }
-    }
-    f0 = f1; b0 = b1;
-  }
-  return ao.worst;
+  StackWeights sw(st, w_max, weights, raw, counts, covered);
+  sw.clear();
+  st.ao.clear_unused(run.rows, K, n_hits);
+  RTRY(st.alloc(1, 0));                                      // the stride: the block's longest Q - 2
+  RTRY(sw.alloc());
+  RTRY(st.build("aln_hits_weights", [&](const StackGroup& g) { return sw.group(g); }));
+  return st.ao.worst;
 }
 
 }  // namespace aln

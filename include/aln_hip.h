@@ -227,6 +227,7 @@ int aln_has_gfx950(void);
  *   "weights_group_rows"            aln_hits_weights, aln_hits_weights_profiles: query rows whose letters rows (K x the block's longest
  *                                   Q-2 bytes per row) are resident on the device at a time; 0 (default) = as many as keep them below
  *                                   1 GiB; a value never lifts that budget (environment default ALN_WEIGHTS_GROUP_ROWS).  Same results.
+ *                                   aln_hits_purge(_profiles) builds the same stack and reads the same hint.
  *   "align_fused_nonlocal"          aln_hits_align: 1 (default) = hits of the four non-local align types are aligned by the fused
  *                                   kernel where it applies; 0 = they all go through resident batches (environment default
  *                                   ALN_ALIGN_FUSED_NONLOCAL).  Same results.
@@ -718,6 +719,64 @@ int aln_hits_weights_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, const
                               const aln_seqs* templates, const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K,
                               const aln_hit* hits, const int32_t* n_hits, int32_t w_max, aln_hit_alignment* out,
                               int32_t* weights, int64_t* raw, int32_t* counts, int32_t* covered);
+/* ---- purging of near-identical search hits: the purge decision and the survivors' weights, on the device ---------------- */
+/* Before the weights of a round are made, near-identical hits are purged (PSI-BLAST at 94 % identity, hhfilter -id 90): weights
+ * damp redundancy, they do not remove it.  These entries go from a round's hits to the purge decision and, when wanted, to the
+ * weights and weighted counts of the survivors in one call: every hit is swept once and no pileup is downloaded.
+ * All of it is exact integer arithmetic: the result depends on neither the chunking, the grouping, the route nor the launch order.
+ * For a query row r of the block take the pileup aln_hits_pileup defines for its slots k < n_hits[r]: the letters rows
+ * L[k][p], p = 0 .. Q-3.  A slot CONTRIBUTES exactly when it does there: status 0 and, ALN_LOCAL, score > 0.  A LETTER is a
+ * character of the call's alphabet (sub->alphabet, or profiles->alphabet); '-', '.' and NUL never are letters, and the row of
+ * a slot that does not contribute shows no letter.
+ *   letters(k)     the number of positions where L[k][p] is a letter;
+ *   overlap(j,k)   for j < k, the number of positions where both rows show a letter;
+ *   same(j,k)      the number of those positions where the letters are equal.
+ * Slot k is NEAR slot j (j < k) when overlap(j,k) >= 1, 100 * overlap(j,k) >= min_overlap * letters(k) and
+ * 100 * same(j,k) >= max_identity * overlap(j,k).  (The products are at most 100 * 65532: int32 holds them.)
+ * The greedy rule, slots in ascending order (the search's order: best score first): slot k is KEPT when letters(k) > 0 and it
+ * is near no KEPT slot j < k; otherwise, if letters(k) > 0, it is PURGED and its keeper is the smallest kept j it is near.  A
+ * purged slot purges nobody.
+ * max_identity is in 1..101; 101 can never be met: then nothing is purged and every weight output is byte-identical to
+ * aln_hits_weights'.  min_overlap is in 0..100; with 0 only overlap >= 1 is asked.
+ * purge[s], per slot:   kept { k, 0, 0, letters(k) };   purged by j { j, same(j,k), overlap(j,k), letters(k) };
+ *                       unused, not contributing, or without a letter { -1, 0, 0, 0 }.
+ * weights may be NULL (purge only): then raw, counts and covered must be NULL too and w_max is not read.  With weights given,
+ * w_max is in 1..65535, and weights, raw, counts and covered are exactly aln_hits_weights' definition applied to the pileup in
+ * which every slot that is not kept shows '.' at every position: purged slots get weight 0 and raw 0, and counts and covered
+ * are, byte for byte, what aln_hits_column_counts returns for the same hits under the returned weights.
+ * out[s] is, byte for byte, the record aln_hits_align writes for the slot when called with pairs == NULL and no line group; a
+ * slot with a falsified local score gets ALN_E_ARG, does not contribute, and the call goes on.
+ * Device side (csrc/search_purge.hip): the stack is aln_hits_weights' (hint "weights_group_rows"; a group also keeps the pair
+ * bits, K x ceil(K/64) x 8 bytes per query row, below 1 GiB); over a complete group a pair kernel (per query, tiles of 64 slots
+ * k on the lanes x 32 slots j, rows staged through LDS and translated to letter codes, four positions per dword, one near bit
+ * per pair), a greedy kernel (one wave per query), one wave per purged slot for its record, the rows of the slots that are not
+ * kept rewritten to '.', then aln_hits_weights' four launches.  aln_hits_align_last_routes reports this call's slots too.
+ * Checks, in this order, nothing written when one fails: NULL hits / n_hits / out, K outside 1..1024 (ALN_E_ARG);
+ * aln_score_all_vs_all's, in its order; NULL purge; max_identity outside 1..101; min_overlap outside 0..100; weights == NULL
+ * with any of raw / counts / covered given; w_max outside 1..65535 when weights is given (ALN_E_ARG); every n_hits[r] in 0..K,
+ * every used slot's t in [0, n_templates) and, local, its end cell in range (ALN_E_ARG); last, an alphabet that holds '.' or
+ * '-' (ALN_E_ARG).
+ * q_begin == q_end: ALN_OK, nothing written.  Returns the lowest per-slot status, ALN_OK when all are 0. */
+typedef struct { int32_t keeper, same, overlap, letters; } aln_hit_purge;   /* 16 bytes */
+int aln_hits_purge(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
+                   const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K,
+                   const aln_hit* hits, const int32_t* n_hits,
+                   int32_t max_identity, int32_t min_overlap, int32_t w_max,
+                   aln_hit_alignment* out /* rows x K */, aln_hit_purge* purge /* rows x K */,
+                   int32_t* weights /* rows x K, may be NULL = purge only */,
+                   int64_t* raw /* rows x K, may be NULL */,
+                   int32_t* counts /* (offsets[q_end] - offsets[q_begin]) x sub->n, may be NULL */,
+                   int32_t* covered /* offsets[q_end] - offsets[q_begin], may be NULL */);
+/* The same for the hits of a profile search: the slots, records, routes and consensus pool are aln_hits_pileup_profiles', the
+ * alphabet is profiles->alphabet, and the checks are NULL profiles / templates / gap, then NULL hits / n_hits / out and K;
+ * aln_score_profiles_vs_all's, in its order, with the consensus pool where aln_hits_align_profiles checks it; then purge,
+ * max_identity, min_overlap, weights and w_max; n_hits, t and the end cells; the alphabet.  For profiles derived from residue
+ * queries under an integral table every output is byte-identical to aln_hits_purge's on those residues. */
+int aln_hits_purge_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_seqs* consensus /* may be NULL */,
+                            const aln_seqs* templates, const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K,
+                            const aln_hit* hits, const int32_t* n_hits, int32_t max_identity, int32_t min_overlap,
+                            int32_t w_max, aln_hit_alignment* out, aln_hit_purge* purge, int32_t* weights, int64_t* raw,
+                            int32_t* counts, int32_t* covered);
 /* Several NON-INTERSECTING local alignments per hit (the second, third .. HSP of a hit; Waterman-Eggert's declumping restated on
  * the reference's recurrence).  ALN_LOCAL only.  For one pair — query of Q residues, template of T, sentinels counted — under a
  * table and constant affine gaps:
@@ -788,7 +847,7 @@ int aln_hits_align_multi_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, c
                                   int32_t max_alignments /* N, 1..16 */, float min_score /* -INFINITY: none */,
                                   int32_t* n_found /* rows x K */, aln_hit_alignment* out /* rows x K x N */,
                                   int32_t* pairs, int32_t pair_stride, char* tlines, char* qlines, int32_t line_stride, int32_t* lengths);
-/* out[0]: the used slots the last aln_hits_align / aln_hits_align_profiles / aln_hits_align_multi / aln_hits_align_multi_profiles / aln_hits_column_counts(_profiles) / aln_hits_weights(_profiles) / aln_hits_pileup(_profiles) call on this context sent through a fused kernel,
+/* out[0]: the used slots the last aln_hits_align / aln_hits_align_profiles / aln_hits_align_multi / aln_hits_align_multi_profiles / aln_hits_column_counts(_profiles) / aln_hits_purge(_profiles) / aln_hits_weights(_profiles) / aln_hits_pileup(_profiles) call on this context sent through a fused kernel,
  * out[1]: through resident batches; { 0, 0 } before any call and after a call that failed its checks.  NULL argument: ALN_E_ARG. */
 int aln_hits_align_last_routes(const aln_ctx* ctx, int64_t out[2]);
 
