@@ -99,6 +99,25 @@ class AlnHitPurge(C.Structure):
 
 HIT_PURGE_DTYPE = np.dtype([("keeper", np.int32), ("same", np.int32), ("overlap", np.int32), ("letters", np.int32)])
 
+
+class AlnPssmParams(C.Structure):
+    """aln_pssm_params.  make() builds one from Python values and keeps the arrays its pointers were made from."""
+    _fields_ = [("scale", C.c_int32), ("beta", C.c_int32), ("bg", _ip), ("mix", _ip)]
+
+    @classmethod
+    def make(cls, bg, beta, scale=2, mix=None):
+        """bg: n integer background weights (1..1024 each, sum B <= 1024); beta: 1..2^26; scale: 1, 2, 4 or 8; mix: None
+        (background pseudo-counts) or n x n integers >= 1 whose rows sum to B"""
+        p = cls()
+        p.scale, p.beta = int(scale), int(beta)
+        p.bg_array = np.ascontiguousarray(bg, dtype=np.int32).reshape(-1)
+        p.bg = p.bg_array.ctypes.data_as(_ip)
+        p.mix_array = None
+        if mix is not None:
+            p.mix_array = np.ascontiguousarray(mix, dtype=np.int32).reshape(len(p.bg_array), len(p.bg_array))
+            p.mix = p.mix_array.ctypes.data_as(_ip)
+        return p
+
 EXPORTS = [
     "aln_ctx_create", "aln_ctx_destroy", "aln_error_string", "aln_last_error", "aln_ctx_synchronize", "aln_has_gfx950",
     "aln_batch_create", "aln_batch_destroy", "aln_batch_n_pairs", "aln_batch_device_bytes", "aln_batch_dp",
@@ -112,7 +131,7 @@ EXPORTS = [
     "aln_hits_align_profiles", "aln_hits_zscores_profiles", "aln_hits_align_multi",
     "aln_hits_align_multi_profiles", "aln_hits_column_counts", "aln_hits_column_counts_profiles",
     "aln_hits_pileup", "aln_hits_pileup_profiles", "aln_hits_weights", "aln_hits_weights_profiles",
-    "aln_hits_purge", "aln_hits_purge_profiles",
+    "aln_hits_purge", "aln_hits_purge_profiles", "aln_hits_pssm", "aln_hits_pssm_profiles", "aln_pssm_entry",
 ]
 COMM_ID_BYTES = 128
 
@@ -228,6 +247,16 @@ def lib():
                                               C.POINTER(AlnGap), C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.c_int32,
                                               C.c_int32, C.c_int32, C.POINTER(AlnHitAlignment), C.POINTER(AlnHitPurge), _ip, _lp, _ip,
                                               _ip]
+        L.aln_hits_pssm.argtypes = [C.c_void_p, C.POINTER(AlnSeqs), C.POINTER(AlnSeqs), C.POINTER(AlnSubmatrix), C.POINTER(AlnGap),
+                                    C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.c_int32, C.c_int32, C.c_int32,
+                                    C.POINTER(AlnPssmParams), C.POINTER(AlnHitAlignment), _fp, C.POINTER(AlnHitPurge), _ip, _lp, _ip,
+                                    _ip]
+        L.aln_hits_pssm_profiles.argtypes = [C.c_void_p, C.POINTER(AlnQProfiles), C.POINTER(AlnSeqs), C.POINTER(AlnSeqs),
+                                             C.POINTER(AlnGap), C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.c_int32,
+                                             C.c_int32, C.c_int32, C.POINTER(AlnPssmParams), C.POINTER(AlnHitAlignment), _fp,
+                                             C.POINTER(AlnHitPurge), _ip, _lp, _ip, _ip]
+        L.aln_pssm_entry.argtypes = [C.c_uint64, C.c_uint64, C.c_int32]
+        L.aln_pssm_entry.restype = C.c_int32
         L.aln_hits_align_last_routes.argtypes = [C.c_void_p, _lp]
         L.aln_hmap2_gap_arrays.argtypes = [_fp, C.c_int64, C.c_float, C.c_float, C.c_float, _fp, _fp]
         L.aln_batch_plane_bytes_per_cell.argtypes = [C.c_void_p]
@@ -958,6 +987,135 @@ def pssm_from_counts(counts, background, fallback_rows, pseudo=1.0, scale=2.0):
     N = c.sum(axis=1, keepdims=True)
     odds = (c + pseudo * bg) / ((N + pseudo) * bg)
     return np.where(N > 0, np.rint(scale * np.log2(odds)), fb).astype(np.float32)
+
+
+# T[m] = floor(2^(32 + m/16)), m = 1 .. 15 (include/aln_hip.h): four nested integer square roots of 2^(512 + m)
+PSSM_T = (0x10b5586cf, 0x1172b83c7, 0x12387a6e7, 0x1306fe0a3, 0x13dea64c1, 0x14bfdad53, 0x15ab07dd4, 0x16a09e667, 0x17a11473e,
+          0x18ace5422, 0x19c49182a, 0x1ae89f995, 0x1c199bdd8, 0x1d5818dcf, 0x1ea4afa2a)
+
+
+def _lg16(x, y):
+    """lg16 of include/aln_hip.h for Python integers x >= y >= 1: floor(16 log2(x / y)) read off a 33-bit mantissa"""
+    e = x.bit_length() - y.bit_length()
+    if (y << e) > x:
+        e -= 1
+    mant = (x << 32) // (y << e)
+    return 16 * e + sum(1 for t in PSSM_T if t <= mant)
+
+
+def pssm_score(num, den, scale):
+    """The score of aln_hits_pssm's rule for Python integers num, den >= 1 (any size) and scale in 1, 2, 4, 8, no float anywhere:
+    floor((lg16(num, den) scale + 8) / 16), or minus that of (den, num) when num < den."""
+    num, den, scale = int(num), int(den), int(scale)
+    assert num >= 1 and den >= 1 and scale in (1, 2, 4, 8)
+    return (_lg16(num, den) * scale + 8) // 16 if num >= den else -((_lg16(den, num) * scale + 8) // 16)
+
+
+def pssm_entry(num, den, scale):
+    """aln_pssm_entry: the same score from the library's host helper (no GPU); 0 for num or den of 0 or >= 2^63 or a scale other
+    than 1, 2, 4, 8."""
+    return int(lib().aln_pssm_entry(int(num), int(den), int(scale)))
+
+
+def pssm_rows_from_counts(counts, bg, beta, scale, fallback_rows, mix=None):
+    """The rule of hits_pssm restated with Python integers (arbitrary precision, no floats).  counts: (L, n) integers — the
+    INTERIOR rows of one entry of hits_purge's counts (entry[1:-1]); bg: n integers >= 1, B their sum; beta: the pseudo-count
+    mass in the units of the weights; scale: 1, 2, 4 or 8; fallback_rows: (L, n), what a row without counts keeps, bit for bit;
+    mix: None (mix[b][a] = bg[a]) or n x n integers, mix[b][a] the pseudo-count mass letter a receives per observation of b.
+    With N = sum_a c[a] > 0:  g[a] = sum_b c[b] mix[b][a],  num = c[a] N B + beta g[a],  den = (N + beta) N bg[a],  entry =
+    pssm_score(num, den, scale).  -> float32 (L, n)"""
+    fb = np.asarray(fallback_rows, dtype=np.float32)
+    rows = [[int(v) for v in row] for row in np.asarray(counts).reshape(fb.shape).tolist()]
+    bg = [int(v) for v in np.asarray(bg).reshape(-1).tolist()]
+    n, B, beta = len(bg), sum(bg), int(beta)
+    assert fb.ndim == 2 and fb.shape[1] == n
+    mix = [bg] * n if mix is None else [[int(v) for v in row] for row in np.asarray(mix).reshape(n, n).tolist()]
+    out = fb.copy()
+    for i, c in enumerate(rows):
+        N = sum(c)
+        if N == 0:
+            continue
+        for a in range(n):
+            g = sum(c[b] * mix[b][a] for b in range(n))
+            out[i, a] = pssm_score(c[a] * N * B + beta * g, (N + beta) * N * bg[a], scale)
+    return out
+
+
+def _pssm(ctx, side, hits, n_hits, gi, ge, params, max_identity, min_overlap, w_max, q_begin, align_type, want_purge, want_weights,
+          want_raw, want_counts, want_covered):
+    hits, n_hits, rows, K = _hit_list(hits, n_hits)
+    cut = [int(side.offsets[q_begin + r] - side.offsets[q_begin]) for r in range(rows + 1)]
+    rec = np.zeros((rows, K), dtype=HIT_ALIGNMENT_DTYPE)
+    prows = np.zeros((cut[rows], side.n_letters), dtype=np.float32)
+    purge = np.zeros((rows, K), dtype=HIT_PURGE_DTYPE) if want_purge else None
+    weights = np.zeros((rows, K), dtype=np.int32) if want_weights else None
+    raw = np.zeros((rows, K), dtype=np.int64) if want_raw else None
+    counts = np.zeros((cut[rows], side.n_letters), dtype=np.int32) if want_counts else None
+    covered = np.zeros(cut[rows], dtype=np.int32) if want_covered else None
+    rc = side.call(ctx, _const_gap(align_type, gi, ge), q_begin, q_begin + rows, int(K), _as(hits, AlnHit), _i(n_hits),
+                   int(max_identity), int(min_overlap), int(w_max), C.byref(params) if params is not None else None,
+                   _as(rec, AlnHitAlignment), _f(prows), _as(purge, AlnHitPurge) if want_purge else None,
+                   _i(weights) if want_weights else None, raw.ctypes.data_as(_lp) if want_raw else None,
+                   _i(counts) if want_counts else None, _i(covered) if want_covered else None)
+    if rc != 0 and not (rec["status"] == rc).any():
+        _check(rc, ctx.h)
+    per_query = lambda x: [x[cut[r]:cut[r + 1]] for r in range(rows)]
+    return rec, per_query(prows), purge, weights, raw, (per_query(counts) if want_counts else None), covered, rc
+
+
+def hits_pssm(ctx, queries, templates, hits, n_hits, alphabet, table, gi, ge, params, max_identity=90, min_overlap=50, w_max=1000,
+              q_begin=0, align_type=LOCAL, want_purge=True, want_weights=True, want_raw=True, want_counts=True, want_covered=True):
+    """aln_hits_pssm: from a round's hits to the next round's profile rows in one call, on the device — hits_purge's purge,
+    weights and weighted counts, then per count row with N = sum of its counts > 0 the integer log-odds
+    pssm_rows_from_counts restates (params: an AlnPssmParams, e.g. AlnPssmParams.make(bg, beta, scale, mix)); a row without
+    counts keeps the table row of the query's residue, bit for bit.  No count row is downloaded unless asked for.
+    -> rec[rows, K] (hits_align's records without lists), rows (per query a float32 (Q, n) array, the sentinel rows included
+    and zero; views of one block — entry[1:-1] is an entry of QueryProfiles), then purge, weights, raw, counts, covered exactly
+    as hits_purge returns them for the same arguments (None for what was not asked), rc (0, or the lowest per-slot status).
+    Raises only when the call wrote nothing."""
+    return _pssm(ctx, _ResidueSide("aln_hits_pssm", queries, templates, alphabet, table), hits, n_hits, gi, ge, params, max_identity,
+                 min_overlap, w_max, q_begin, align_type, want_purge, want_weights, want_raw, want_counts, want_covered)
+
+
+def hits_pssm_profiles(ctx, profiles, templates, hits, n_hits, gi, ge, params, consensus=None, max_identity=90, min_overlap=50,
+                       w_max=1000, q_begin=0, align_type=LOCAL, want_purge=True, want_weights=True, want_raw=True, want_counts=True,
+                       want_covered=True):
+    """aln_hits_pssm_profiles: hits_pssm for the hits of a profile search (profiles: a QueryProfiles, whose alphabet the letters
+    are; consensus as in hits_align_profiles — it only enters the records' identity); a row without counts keeps the profile's
+    own row.  -> the 8-tuple of hits_pssm."""
+    return _pssm(ctx, _ProfileSide("aln_hits_pssm_profiles", profiles, templates, consensus), hits, n_hits, gi, ge, params,
+                 max_identity, min_overlap, w_max, q_begin, align_type, want_purge, want_weights, want_raw, want_counts, want_covered)
+
+
+def iterate_search(ctx, queries, templates, alphabet, table, gi, ge, K, rounds, params, max_identity=90, min_overlap=50, w_max=1000,
+                   min_score=-np.inf, align_type=LOCAL):
+    """An iterative profile search, every step on the device.  Round 1: search_topk, then hits_pssm makes the profiles; every
+    later round: search_topk_profiles with the profiles, then hits_pssm_profiles (the queries as consensus) makes the next ones.
+    Stops after `rounds` rounds, or after the first round in which every row's template list equals the previous round's (that
+    round's hits are reported, no profiles are made from them).  queries: a list of strings.
+    -> (per round (hits, n_hits), the last profiles made: a QueryProfiles)"""
+    assert rounds >= 1
+    quiet = dict(max_identity=max_identity, min_overlap=min_overlap, w_max=w_max, align_type=align_type, want_purge=False,
+                 want_weights=False, want_raw=False, want_counts=False, want_covered=False)
+    found, profiles, previous = [], None, None
+    for _ in range(int(rounds)):
+        if profiles is None:
+            hits, n_hits = search_topk(ctx, queries, templates, alphabet, table, gi, ge, K, min_score, align_type=align_type)
+        else:
+            hits, n_hits = search_topk_profiles(ctx, profiles, templates, gi, ge, K, min_score, align_type=align_type)
+        lists = [hits["t"][r, :n_hits[r]].tolist() for r in range(len(n_hits))]
+        found.append((hits, n_hits))
+        if lists == previous:
+            break
+        previous = lists
+        if profiles is None:
+            res = hits_pssm(ctx, queries, templates, hits, n_hits, alphabet, table, gi, ge, params, **quiet)
+        else:
+            res = hits_pssm_profiles(ctx, profiles, templates, hits, n_hits, gi, ge, params, consensus=queries, **quiet)
+        if res[7] != 0:
+            _check(res[7], ctx.h)
+        profiles = QueryProfiles([rows[1:-1] for rows in res[1]], alphabet)
+    return found, profiles
 
 
 def hits_align_routes(ctx):

@@ -190,10 +190,11 @@ __global__ __launch_bounds__(64) void mute_rows_kernel(char* __restrict__ stack,
 }
 
 // The shared body of aln_hits_purge and aln_hits_purge_profiles (run: prepared; `queries`: the pool the query lengths are read
-// from — hit_entry's pool, search_align.h).
-static int purge_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const aln_hit* hits, const int32_t* n_hits,
-                       int32_t max_identity, int32_t min_overlap, int32_t w_max, aln_hit_alignment* out, aln_hit_purge* purge,
-                       int32_t* weights, int64_t* raw, int32_t* counts, int32_t* covered) {
+// from — hit_entry's pool, search_align.h).  after (search_stack.h; weights given): the weighted count rows stay on the device
+// and after(st, sw, group) runs over every group once its weights have come down — aln_hits_pssm (search_pssm.hip).
+int purge_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const aln_hit* hits, const int32_t* n_hits,
+                int32_t max_identity, int32_t min_overlap, int32_t w_max, aln_hit_alignment* out, aln_hit_purge* purge,
+                int32_t* weights, int64_t* raw, int32_t* counts, int32_t* covered, const StackHook* after) {
   static_assert(sizeof(PurgeRecord) == sizeof(aln_hit_purge) && sizeof(aln_hit_purge) == 16, "aln_hit_purge is 16 bytes");
   aln_ctx* ctx = run.ctx;
   if (!purge || max_identity < 1 || max_identity > 101 || min_overlap < 0 || min_overlap > 100) return ALN_E_ARG;
@@ -205,7 +206,7 @@ static int purge_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
   HitStack st(run, queries, K, out);
   int rc = st.route(hits, n_hits);                           // nothing written before
   if (rc != ALN_OK) return rc;
-  StackWeights sw(st, w_max, weights, raw, counts, covered);
+  StackWeights sw(st, w_max, weights, raw, counts, covered, after != nullptr);
   if (weights) sw.clear();
   st.ao.clear_unused(rows, K, n_hits);
 
@@ -234,7 +235,10 @@ static int purge_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
     hipLaunchKernelGGL(mute_rows_kernel, dim3(slots), wave, 0, ctx->stream, st.dstack, dw, (int)K, dkeep);
     STRY(hipGetLastError());
     STRY(hipMemcpyAsync(purge + g.slot0, dpur, (size_t)slots * sizeof(PurgeRecord), hipMemcpyDeviceToHost, ctx->stream));
-    if (weights) return sw.group(g);
+    if (weights) {
+      RTRY(sw.group(g));
+      return after ? (*after)(st, sw, g) : ALN_OK;
+    }
     STRY(hipStreamSynchronize(ctx->stream));
     return ALN_OK;
   });

@@ -7,11 +7,13 @@
 //   StackWeights   the buffers of the four weight launches over a complete group, the launches, the download and the filing of
 //                  weights, raw, counts and covered.
 // The kernels are instantiated ONCE, in search_weights.hip, behind two ordinary functions (launch_scatter_rows,
-// launch_weight_kernels), as the pileup kernels are behind launch_pileup_job.
+// launch_weight_kernels), as the pileup kernels are behind launch_pileup_job.  aln_hits_pssm (search_pssm.hip) runs
+// aln_hits_purge's body, purge_block, with a hook over every group's count rows (StackHook, below).
 #pragma once
 #include <algorithm>
 #include <climits>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -200,15 +202,19 @@ struct HitStack {
 
 // The weights of a complete group and the counts under them: buffers, the four launches, the download, the filing.  Outputs:
 // weights (required) and raw rows x K, counts and covered in aln_hits_column_counts' layout; each but weights may be nullptr.
+// keep_rows: the weighted count rows are made and stay on the device (dcnt, 32 int32 each, covered in column kSpareCol) also
+// when neither counts nor covered is downloaded — aln_hits_pssm reads them there.
 struct StackWeights {
   HitStack& st; int32_t w_max;
   int32_t* weights; int64_t* raw; int32_t* counts; int32_t* covered;
-  bool want_counts;
+  bool want_counts, keep_rows;
   int32_t *dnp = nullptr, *dcnt = nullptr, *dwt = nullptr; int64_t* draw = nullptr;
   std::vector<int32_t> hcnt;
 
-  StackWeights(HitStack& s, int32_t w_max_, int32_t* weights_, int64_t* raw_, int32_t* counts_, int32_t* covered_)
-      : st(s), w_max(w_max_), weights(weights_), raw(raw_), counts(counts_), covered(covered_), want_counts(counts_ || covered_) {}
+  StackWeights(HitStack& s, int32_t w_max_, int32_t* weights_, int64_t* raw_, int32_t* counts_, int32_t* covered_,
+               bool keep_rows_ = false)
+      : st(s), w_max(w_max_), weights(weights_), raw(raw_), counts(counts_), covered(covered_), want_counts(counts_ || covered_),
+        keep_rows(keep_rows_) {}
 
   // what a slot or count row nothing reaches holds
   void clear() {
@@ -221,7 +227,7 @@ struct StackWeights {
   int alloc() {
     aln_ctx* ctx = st.run.ctx;
     STRY(st.own.get(dnp, st.max_grows * 32));
-    if (want_counts) STRY(st.own.get(dcnt, st.max_grows * 32));
+    if (want_counts || keep_rows) STRY(st.own.get(dcnt, st.max_grows * 32));
     STRY(st.own.get(dwt, st.group * st.K));
     STRY(st.own.get(draw, st.group * st.K));
     hcnt.resize(want_counts ? st.max_grows * 32 : 0);
@@ -232,7 +238,7 @@ struct StackWeights {
     aln_ctx* ctx = st.run.ctx;
     const size_t K = (size_t)st.K;
     const WeightLaunch w = {st.dstack, (int64_t)st.dw, (int)st.K, g.gn, g.g_rows, st.dqr, st.didx, (int)w_max,
-                            dnp, dwt, want_counts ? dcnt : nullptr, draw};
+                            dnp, dwt, dcnt, draw};
     RTRY(launch_weight_kernels(ctx, w));
     if (want_counts) STRY(hipMemcpyAsync(hcnt.data(), dcnt, g.g_rows * 128, hipMemcpyDeviceToHost, ctx->stream));
     STRY(hipMemcpyAsync(weights + g.slot0, dwt, g.gn * K * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -248,5 +254,13 @@ struct StackWeights {
     return ALN_OK;
   }
 };
+
+// The shared body of aln_hits_purge and aln_hits_purge_profiles (search_purge.hip), which aln_hits_pssm (search_pssm.hip) runs
+// too: with `after` the weighted count rows of a group stay on the device (sw.dcnt) and after(st, sw, group) reads them there,
+// once the group's weights have come down; it leaves with the stream synchronised.
+using StackHook = std::function<int(HitStack&, StackWeights&, const StackGroup&)>;
+int purge_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const aln_hit* hits, const int32_t* n_hits,
+                int32_t max_identity, int32_t min_overlap, int32_t w_max, aln_hit_alignment* out, aln_hit_purge* purge,
+                int32_t* weights, int64_t* raw, int32_t* counts, int32_t* covered, const StackHook* after = nullptr);
 
 }  // namespace aln

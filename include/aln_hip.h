@@ -408,7 +408,9 @@ int aln_search_topk(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templ
  * has no residue string to send through a substitution table.  Where such rows come from is the caller's business; the step
  * from a search round to the next one's rows is on the device too: aln_hits_column_counts (below, after
  * aln_hits_align_profiles) tallies the aligned template letters of a round's hits per query position, and
- * aln_amd.pssm_from_counts turns such counts into integer log-odds rows. */
+ * aln_amd.pssm_from_counts turns such counts into integer log-odds rows on the host; aln_hits_pssm (below, after
+ * aln_hits_purge) goes from a round's hits to the next round's rows in one call, the log-odds made on the device by an exact
+ * integer rule. */
 typedef struct {
   int32_t n_seqs;
   const int64_t* offsets;       /* n_seqs + 1, in ROWS: profile s owns rows offsets[s] .. offsets[s+1); its first and last row stand
@@ -777,6 +779,82 @@ int aln_hits_purge_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, const a
                             const aln_hit* hits, const int32_t* n_hits, int32_t max_identity, int32_t min_overlap,
                             int32_t w_max, aln_hit_alignment* out, aln_hit_purge* purge, int32_t* weights, int64_t* raw,
                             int32_t* counts, int32_t* covered);
+/* ---- next-round profile rows from search hits: purge, weights, counts and log-odds in one call, on the device ------------- */
+/* The last step of a search round: the weighted counts become integer log-odds rows, the rows of the aln_qprofiles the next
+ * round searches with.  These entries go from a round's hits to those rows in one call — purge, weights, counts and log-odds on
+ * the device, no count row downloaded unless it is wanted.  The log-odds are defined in integers alone, so the rows are
+ * reproducible bit for bit: they depend on neither chunking, grouping, route nor launch order, nor on any libm.
+ * Parameters, n the call's alphabet size (sub->n, or profiles->n):
+ *   bg[a]      integer background weights, each in 1..1024, B = sum_a bg[a] <= 1024;
+ *   mix        n x n row-major, or NULL.  Every entry is >= 1 and every row sums to B.  mix[b][a] is the pseudo-count mass that
+ *              letter a receives per observation of letter b: a target-frequency row of the substitution model scaled to B.
+ *              NULL means mix[b][a] = bg[a], the background pseudo-counts of aln_amd.pssm_from_counts;
+ *   beta       1..2^26, the pseudo-count mass in the units of the weights (a caller thinks of it relative to w_max);
+ *   scale      one of 1, 2, 4, 8: scores are in 1/scale bits.
+ * Per count row r take c[a] = counts[r][a], the weighted counts aln_hits_purge defines for the same hits, max_identity,
+ * min_overlap and w_max, and N = sum_a c[a].  N is below 2^26: a slot adds at most one letter per position and the weights of
+ * a row's 1024 slots sum to at most 1024 * 65535.
+ * N == 0: row r of `rows` is the fallback row, copied bit for bit — sub->table[index(q[i]) * n + a] for position i of query q in
+ * aln_hits_pssm, the profile's own row in aln_hits_pssm_profiles.
+ * Otherwise, in unsigned 64-bit integers,
+ *   g[a]   = sum_b c[b] * mix[b][a]                    (at most N * B)
+ *   num[a] = c[a] * N * B + beta * g[a]
+ *   den[a] = (N + beta) * N * bg[a]
+ * Both are in [1, 2^63): c[a] * N * B < 2^26 * 2^26 * 2^10 and beta * g[a] <= 2^26 * 2^36, each at most 2^62; N + beta < 2^27,
+ * so den[a] < 2^27 * 2^26 * 2^10; g[a] >= N >= 1 because every mix entry is >= 1.  num[a] / den[a] is the smoothed frequency
+ * (c[a] + beta * g[a] / (N * B)) / (N + beta) over the background frequency bg[a] / B.
+ * lg16(x, y) for x >= y >= 1:  e is the largest e >= 0 with y * 2^e <= x;  mant = floor(x * 2^32 / (y * 2^e)), which lies in
+ * [2^32, 2^33);  lg16 = 16 * e + #{ m in 1..15 : T[m] <= mant }, with T[m] = floor(2^(32 + m/16)):
+ *   0x10b5586cf 0x1172b83c7 0x12387a6e7 0x1306fe0a3 0x13dea64c1
+ *   0x14bfdad53 0x15ab07dd4 0x16a09e667 0x17a11473e 0x18ace5422
+ *   0x19c49182a 0x1ae89f995 0x1c199bdd8 0x1d5818dcf 0x1ea4afa2a
+ * (four nested integer square roots of 2^(512 + m)).  lg16 is floor(16 * log2(x / y)) read off a 33-bit mantissa.
+ * The score:  s = floor((lg16(num, den) * scale + 8) / 16) when num >= den,  s = -floor((lg16(den, num) * scale + 8) / 16)
+ * otherwise; the row entry is (float)s.  |s| <= 8 * 37, so every derived row is integral.  This is rint(scale * log2(num / den))
+ * wherever the ratio is further than 2^-32 (relative) from a rounding threshold; the thresholds are irrational, so the
+ * real-valued rule has no ties.
+ * The implementation uses neither 128-bit arithmetic nor a 64-bit division: mant - 2^32 is one subtraction (r = x - y * 2^e)
+ * and 32 shift-and-subtract steps, in which 2r < 2 * y * 2^e <= 2x < 2^64 holds throughout (csrc/pssm_rule.h, one header for
+ * host and device).
+ * rows has the layout of counts with the entry's n: (offsets[q_end] - offsets[q_begin]) x n, the sentinel rows (first and last
+ * row of every query) zeros; aln_hits_pssm_profiles' rows are the rows of an aln_qprofiles for the next round, unchanged.
+ * out and rows are required.  purge, weights, raw, counts and covered may be NULL, each independently; every one that is given
+ * is byte for byte what aln_hits_purge(_profiles) returns for the same arguments (max_identity = 101 purges nothing).  w_max is
+ * always read.  A slot with a falsified local score gets ALN_E_ARG, does not contribute, and the call goes on.
+ * Device side (csrc/search_pssm.hip): aln_hits_purge's stack and launches; the group's weighted count rows stay on the device
+ * and one half-wave per count row (lane = letter) sums N by five xor-shuffles, makes g[a] from mix staged in LDS and the lanes'
+ * c[b] broadcast across the half-wave, applies the rule per lane and stores the row coalesced.  Only the rows come down, and
+ * the optional outputs that were asked for; the host copies the fallback rows in and zeroes the sentinel rows.
+ * aln_hits_align_last_routes reports this call's slots as it does aln_hits_purge's.
+ * Checks, in this order, nothing written when one fails: aln_hits_purge's up to and including w_max, without those on purge
+ * and weights — NULL hits / n_hits / out, K outside 1..1024 (ALN_E_ARG); aln_score_all_vs_all's, in its order; max_identity
+ * outside 1..101; min_overlap outside 0..100; w_max outside 1..65535 —; NULL par or rows; scale; beta; NULL bg, a bg[a] outside
+ * 1..1024, B above 1024; a mix entry below 1, a mix row that does not sum to B (all ALN_E_ARG); every n_hits[r] in 0..K, every
+ * used slot's t in [0, n_templates) and, local, its end cell in range; last, an alphabet that holds '.' or '-' (ALN_E_ARG).
+ * q_begin == q_end: ALN_OK, nothing written.  Returns the lowest per-slot status, ALN_OK when all are 0. */
+typedef struct { int32_t scale, beta; const int32_t* bg; const int32_t* mix; } aln_pssm_params;
+int aln_hits_pssm(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templates, const aln_submatrix* sub,
+                  const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K,
+                  const aln_hit* hits, const int32_t* n_hits,
+                  int32_t max_identity, int32_t min_overlap, int32_t w_max, const aln_pssm_params* par,
+                  aln_hit_alignment* out /* rows x K */,
+                  float* rows /* (offsets[q_end] - offsets[q_begin]) x sub->n */,
+                  aln_hit_purge* purge /* rows x K, may be NULL */, int32_t* weights /* rows x K, may be NULL */,
+                  int64_t* raw /* rows x K, may be NULL */,
+                  int32_t* counts /* (offsets[q_end] - offsets[q_begin]) x sub->n, may be NULL */,
+                  int32_t* covered /* offsets[q_end] - offsets[q_begin], may be NULL */);
+/* The same for the hits of a profile search: slots, records, routes, the consensus pool and the checks in front are
+ * aln_hits_purge_profiles', n and the alphabet are profiles', and a row without counts keeps the profile's own row.  For
+ * profiles derived from residue queries under an integral table every output is byte-identical to aln_hits_pssm's on those
+ * residues. */
+int aln_hits_pssm_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_seqs* consensus /* may be NULL */,
+                           const aln_seqs* templates, const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K,
+                           const aln_hit* hits, const int32_t* n_hits, int32_t max_identity, int32_t min_overlap,
+                           int32_t w_max, const aln_pssm_params* par, aln_hit_alignment* out, float* rows,
+                           aln_hit_purge* purge, int32_t* weights, int64_t* raw, int32_t* counts, int32_t* covered);
+/* The score of the rule above for one (num, den): needs no GPU, like aln_gapped_strings.  0 for num == 0, den == 0, a value of
+ * 2^63 or more, or a scale other than 1, 2, 4, 8. */
+int32_t aln_pssm_entry(uint64_t num, uint64_t den, int32_t scale);
 /* Several NON-INTERSECTING local alignments per hit (the second, third .. HSP of a hit; Waterman-Eggert's declumping restated on
  * the reference's recurrence).  ALN_LOCAL only.  For one pair — query of Q residues, template of T, sentinels counted — under a
  * table and constant affine gaps:
