@@ -40,6 +40,10 @@ class AlnQProfiles(C.Structure):
     _fields_ = [("n_seqs", C.c_int32), ("offsets", _lp), ("rows", _fp), ("n", C.c_int32), ("alphabet", C.c_char_p)]
 
 
+class AlnQGaps(C.Structure):
+    _fields_ = [("del_init", _fp), ("del_extn", _fp), ("ins_init", _fp), ("ins_extn", _fp)]
+
+
 class AlnProfiles(C.Structure):
     _fields_ = [("aa", _fp), ("sse", _fp), ("conf", _fp)]
 
@@ -132,6 +136,7 @@ EXPORTS = [
     "aln_hits_align_multi_profiles", "aln_hits_column_counts", "aln_hits_column_counts_profiles",
     "aln_hits_pileup", "aln_hits_pileup_profiles", "aln_hits_weights", "aln_hits_weights_profiles",
     "aln_hits_purge", "aln_hits_purge_profiles", "aln_hits_pssm", "aln_hits_pssm_profiles", "aln_pssm_entry",
+    "aln_score_profiles_gaps_vs_all", "aln_search_topk_profiles_gaps",
 ]
 COMM_ID_BYTES = 128
 
@@ -202,6 +207,10 @@ def lib():
                                                 _fp]
         L.aln_search_topk_profiles.argtypes = [C.c_void_p, C.POINTER(AlnQProfiles), C.POINTER(AlnSeqs), C.POINTER(AlnGap), C.c_int32, C.c_int32,
                                                C.c_int32, C.c_float, C.POINTER(AlnHit), _ip]
+        L.aln_score_profiles_gaps_vs_all.argtypes = [C.c_void_p, C.POINTER(AlnQProfiles), C.POINTER(AlnQGaps), C.POINTER(AlnSeqs), C.c_int32,
+                                                     C.c_int32, C.c_int32, _fp]
+        L.aln_search_topk_profiles_gaps.argtypes = [C.c_void_p, C.POINTER(AlnQProfiles), C.POINTER(AlnQGaps), C.POINTER(AlnSeqs), C.c_int32,
+                                                    C.c_int32, C.c_int32, C.c_int32, C.c_float, C.POINTER(AlnHit), _ip]
         L.aln_hits_zscores.argtypes = [C.c_void_p, C.POINTER(AlnSeqs), C.POINTER(AlnSeqs), C.POINTER(AlnSubmatrix), C.POINTER(AlnGap),
                                        C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.c_int32, C.c_uint32,
                                        C.POINTER(AlnHitStats)]
@@ -424,6 +433,58 @@ def score_profiles_vs_all(ctx, profiles, templates, gi, ge, q_begin=0, q_end=Non
 def search_topk_profiles(ctx, profiles, templates, gi, ge, K, min_score=-np.inf, q_begin=0, q_end=None, align_type=LOCAL):
     """aln_search_topk_profiles: search_topk for position-specific queries (a QueryProfiles) -> hits[rows, K], n_hits[rows]."""
     return _search(ctx, _ProfileSide("aln_search_topk_profiles", profiles, templates), gi, ge, K, min_score, q_begin, q_end, align_type)
+
+
+class QueryGaps:
+    """Position-specific gap penalties for a QueryProfiles pool (aln_qgaps).  Each of the four arguments is a list with one entry
+    per profile: L + 1 values for a profile of L interior rows — row 0 (the '^' row, whose del_* price the head deletion; its
+    ins_* are never read) followed by the interior rows 1 .. L.  They become four float32 pool arrays indexed like
+    QueryProfiles.rows (the '$' rows hold 0), which this object keeps alive."""
+
+    def __init__(self, del_init, del_extn, ins_init, ins_extn):
+        lists = [[np.asarray(v, dtype=np.float32).reshape(-1) for v in per_profile] for per_profile in (del_init, del_extn, ins_init, ins_extn)]
+        lengths = [len(v) for v in lists[0]]
+        assert all([len(v) for v in l] == lengths for l in lists) and all(n >= 1 for n in lengths), "L + 1 values per profile, in all four"
+        self.offsets = np.zeros(len(lengths) + 1, dtype=np.int64)
+        np.cumsum([n + 1 for n in lengths], out=self.offsets[1:])
+        pools = [np.zeros(int(self.offsets[-1]), dtype=np.float32) for _ in range(4)]
+        for a, l in zip(pools, lists):
+            for k, v in enumerate(l):
+                a[self.offsets[k]:self.offsets[k + 1] - 1] = v
+        self.del_init, self.del_extn, self.ins_init, self.ins_extn = pools
+        self.c = AlnQGaps(_f(self.del_init), _f(self.del_extn), _f(self.ins_init), _f(self.ins_extn))
+
+    @classmethod
+    def constant(cls, profiles, gi, ge):
+        """every row of the QueryProfiles priced gi / ge: what the constant-gap entries compute (the anchor of include/aln_hip.h)"""
+        i = [np.full(len(p) + 1, gi, np.float32) for p in profiles.profiles]
+        e = [np.full(len(p) + 1, ge, np.float32) for p in profiles.profiles]
+        return cls(i, e, i, e)
+
+
+def score_profiles_gaps_vs_all(ctx, profiles, gaps, templates, q_begin=0, q_end=None, align_type=LOCAL):
+    """aln_score_profiles_gaps_vs_all: score_profiles_vs_all with the gap penalties of `gaps` (a QueryGaps over `profiles`), which
+    every profile row carries for itself -> float32 [rows, n_templates]."""
+    tpool = _pool(templates)
+    if q_end is None:
+        q_end = len(profiles)
+    out = np.empty((max(q_end - q_begin, 0), len(tpool.seqs)), dtype=np.float32)
+    _check(lib().aln_score_profiles_gaps_vs_all(ctx.h, C.byref(profiles.c), C.byref(gaps.c), C.byref(tpool.c), int(align_type), q_begin,
+                                                q_end, _f(out)), ctx.h)
+    return out
+
+
+def search_topk_profiles_gaps(ctx, profiles, gaps, templates, K, min_score=-np.inf, q_begin=0, q_end=None, align_type=LOCAL):
+    """aln_search_topk_profiles_gaps: search_topk_profiles under the rows' own gap penalties -> hits[rows, K], n_hits[rows]."""
+    tpool = _pool(templates)
+    if q_end is None:
+        q_end = len(profiles)
+    rows = max(q_end - q_begin, 0)
+    hits = np.zeros((rows, max(int(K), 0)), dtype=HIT_DTYPE)
+    n_hits = np.zeros(rows, dtype=np.int32)
+    _check(lib().aln_search_topk_profiles_gaps(ctx.h, C.byref(profiles.c), C.byref(gaps.c), C.byref(tpool.c), int(align_type), q_begin,
+                                               q_end, int(K), float(min_score), _as(hits, AlnHit), _i(n_hits)), ctx.h)
+    return hits, n_hits
 
 
 # ---- what the search family's entries share ---------------------------------------------------------------------------------

@@ -162,6 +162,10 @@ struct ScoreRun {
   std::string ph_res; aln_seqs ph = {};         // ... and their placeholder pool
   const aln_seqs* consensus = nullptr;          // profiles, set before prepare(): a pool of query letters that must share the
                                                 // profiles' offsets (aln_hits_align_profiles); checked, never encoded or scored
+  const aln_qgaps* qgaps = nullptr;             // profiles, set before prepare(): the rows carry their own gap penalties
+  int32_t qgaps_align_type = 0;                 // (aln_score_profiles_gaps_vs_all).  prepare() then takes no `gap` but this align
+                                                // type, runs that entry's checks in its order, and the route is kFast or an error:
+                                                // never kAllFull, never long_t
   int32_t q_begin = 0, q_end = 0;
   int rows = 0, n_t = 0;
   bool local = false, packed = false;
@@ -218,6 +222,12 @@ struct DeviceBufs {
     return e;
   }
 };
+
+// The kernels of a run with gap rows (search_qgaps.hip), length class r = 1 .. 8: the scores of a grid of (template, query row)
+// pairs — local, or one of the four other align types — and the end cells of `cnt` listed local hits.  Enqueue only; the caller
+// reads hipGetLastError (launch_classes does).
+void launch_qgaps_score(int r, bool local, dim3 grid, hipStream_t stream, const ScoreArgs& s, int free_del, int free_ins);
+void launch_qgaps_end(int r, int cnt, hipStream_t stream, const ScoreArgs& s, const int32_t* list, aln_hit* hits, int K);
 
 // scores[(q - q_begin) * ld + col[t]] for the templates of `tlist` through resident batches of full builds
 // (col == nullptr: column t, ld == 0: n_t — the layout of aln_score_all_vs_all's result).  prof != nullptr: `queries` is the

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "score_common.h"
+#include "score_sweep_qgaps.h"   // kQGapWord: where a device row keeps its gap prices
 
 namespace aln {
 
@@ -307,12 +308,14 @@ int ScoreRun::prepare(aln_ctx* ctx_, const aln_seqs* queries_, const aln_seqs* t
                       const aln_gap* gap_, int32_t q_begin_, int32_t q_end_, const aln_qprofiles* prof_) {
   ctx = ctx_; queries = queries_; templates = templates_; sub = sub_; gap = gap_; q_begin = q_begin_; q_end = q_end_; prof = prof_;
   route = kNothing;
-  if (!ctx || !templates || !gap || (prof ? false : (!queries || !sub))) return ALN_E_ARG;
+  if (!ctx || !templates || (qgaps ? !prof : !gap) || (prof ? false : (!queries || !sub))) return ALN_E_ARG;
   if (q_begin < 0 || q_end > (prof ? prof->n_seqs : queries->n_seqs) || q_begin > q_end) return ALN_E_ARG;
-  if (gap->model != ALN_GAP_AFFINE_CONST || gap->align_type < 0 || gap->align_type > 4) return ALN_E_ARG;
-  local = gap->align_type == ALN_LOCAL;
-  free_del = (gap->align_type == ALN_LOCAL || gap->align_type == ALN_SEMI_LOCAL || gap->align_type == ALN_LOCAL_GLOBAL);
-  free_ins = (gap->align_type == ALN_LOCAL || gap->align_type == ALN_SEMI_LOCAL || gap->align_type == ALN_GLOBAL_LOCAL);
+  if (!qgaps && gap->model != ALN_GAP_AFFINE_CONST) return ALN_E_ARG;
+  const int32_t align_type = qgaps ? qgaps_align_type : gap->align_type;
+  if (align_type < 0 || align_type > 4) return ALN_E_ARG;
+  local = align_type == ALN_LOCAL;
+  free_del = (align_type == ALN_LOCAL || align_type == ALN_SEMI_LOCAL || align_type == ALN_LOCAL_GLOBAL);
+  free_ins = (align_type == ALN_LOCAL || align_type == ALN_SEMI_LOCAL || align_type == ALN_GLOBAL_LOCAL);
   if (prof) {
     if (prof->n < 1 || prof->n > 30 || !prof->alphabet || !prof->rows || !prof->offsets || prof->n_seqs < 0) return ALN_E_ARG;
     for (int s = 0; s < prof->n_seqs; ++s)
@@ -322,13 +325,15 @@ int ScoreRun::prepare(aln_ctx* ctx_, const aln_seqs* queries_, const aln_seqs* t
       for (int s = 0; s <= prof->n_seqs; ++s)
         if (consensus->offsets[s] != prof->offsets[s]) return ALN_E_ARG;
     }
+    // gap rows live in words 26 .. 29 of a device row (score_sweep_qgaps.h)
+    if (qgaps && (prof->n > 26 || !qgaps->del_init || !qgaps->del_extn || !qgaps->ins_init || !qgaps->ins_extn)) return ALN_E_ARG;
     ph_res.assign((size_t)prof->offsets[prof->n_seqs], prof->alphabet[0]);
     for (int s = 0; s < prof->n_seqs; ++s) { ph_res[(size_t)prof->offsets[s]] = '^'; ph_res[(size_t)prof->offsets[s + 1] - 1] = '$'; }
     ph.n_seqs = prof->n_seqs; ph.offsets = prof->offsets; ph.residues = ph_res.data();
     queries = &ph;
   } else if (!sub->alphabet || !sub->table || sub->n < 1 || sub->n > 30) return ALN_E_ARG;
   ALN_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const float gi = gap->gap_init, ge = gap->gap_extn;
+  const float gi = qgaps ? 0.f : gap->gap_init, ge = qgaps ? 0.f : gap->gap_extn;
   rows = q_end - q_begin; n_t = templates->n_seqs;
   every_t.resize((size_t)n_t);
   for (int t = 0; t < n_t; ++t) every_t[t] = t;
@@ -382,6 +387,26 @@ int ScoreRun::prepare(aln_ctx* ctx_, const aln_seqs* queries_, const aln_seqs* t
   if ((rc = encode(queries, qc, maxQ)) != ALN_OK) return rc;
   if ((rc = encode(templates, tc, maxT)) != ALN_OK) return rc;
   if (maxT > kMaxLen || maxQ > kMaxLen) return ALN_E_TOO_LONG;
+  if (qgaps) {
+    // Gap rows: no full-build route exists, so what the other entries send there is refused.  The entries READ of the whole
+    // pool are checked — del_* at rows 0 .. Q-2 and ins_* at rows 1 .. Q-2 of every profile — and no other: a negative one
+    // first (ALN_E_ARG), then a fractional row entry or gap value and the value bound with G, their maximum, in place of gi
+    // and ge (ALN_E_NOT_INTEGRAL).
+    if (maxT > 2048) return ALN_E_TOO_LONG;
+    const float* const arr[4] = {qgaps->del_init, qgaps->del_extn, qgaps->ins_init, qgaps->ins_extn};
+    double G = 0;
+    bool gaps_integral = true;
+    for (int s = 0; s < prof->n_seqs; ++s)
+      for (int w = 0; w < 4; ++w)
+        for (int64_t r = prof->offsets[s] + (w < 2 ? 0 : 1); r < prof->offsets[s + 1] - 1; ++r) {
+          const float v = arr[w][r];
+          if (v < 0) return ALN_E_ARG;
+          if (!(std::floor(v) == v)) gaps_integral = false;       // (a NaN included)
+          else G = std::max(G, (double)v);
+        }
+    if (!integral || !gaps_integral) return ALN_E_NOT_INTEGRAL;
+    if (!((maxs + G) * ((double)maxQ + std::min(maxT, 2048)) + G + maxs < 8388608.0)) return ALN_E_NOT_INTEGRAL;
+  }
   if (!integral) { route = kAllFull; return ALN_OK; }              // profiles: a fractional entry or gap
   if ((maxs + ge) * ((double)maxQ + std::min(maxT, 2048)) + gi + maxs >= 8388608.0) { route = kAllFull; return ALN_OK; }
   route = kFast;
@@ -438,6 +463,13 @@ int ScoreRun::upload_profile_rows(int32_t qa, int32_t qb) {
   for (int32_t s = qa; s < qb; ++s)
     for (int64_t r = prof->offsets[s] + 1; r < prof->offsets[s + 1] - 1; ++r)
       for (int k = 0; k < prof->n; ++k) hrows[(size_t)(r - r0) * 32 + k] = (int32_t)prof->rows[(size_t)r * prof->n + k];
+  if (qgaps)   // the rows' gap prices, words kQGapWord .. + 3: the entries read (prepare() checked them) and no other
+    for (int32_t s = qa; s < qb; ++s)
+      for (int64_t r = prof->offsets[s]; r < prof->offsets[s + 1] - 1; ++r) {
+        int32_t* w = &hrows[(size_t)(r - r0) * 32 + kQGapWord];
+        w[0] = (int32_t)qgaps->del_init[r]; w[1] = (int32_t)qgaps->del_extn[r];
+        if (r > prof->offsets[s]) { w[2] = (int32_t)qgaps->ins_init[r]; w[3] = (int32_t)qgaps->ins_extn[r]; }
+      }
   STRY(hipMemcpyAsync(dprows, hrows.data(), n_rows * 128, hipMemcpyHostToDevice, ctx->stream));
   a.qcodes = reinterpret_cast<const uint8_t*>(dprows) - r0 * 128;
   return ALN_OK;
@@ -454,7 +486,7 @@ int ScoreRun::upload() {
   if (!prof) STRY(hipMemcpyAsync(dtab, ti, sizeof ti, hipMemcpyHostToDevice, ctx->stream));
   a.qcodes = dq; a.qoff = dqo; a.tcodes = dt; a.toff = dto; a.table32 = dtab;
   if (prof && !rows_per_slab) RTRY(upload_profile_rows(q_begin, q_end));
-  a.q_begin = q_begin; a.n_t = n_t; a.gi = (int)gap->gap_init; a.ge = (int)gap->gap_extn;
+  a.q_begin = q_begin; a.n_t = n_t; a.gi = qgaps ? 0 : (int)gap->gap_init; a.ge = qgaps ? 0 : (int)gap->gap_extn;
   STRY(hipMalloc((void**)&dsel, (size_t)n_t * 4));
   if (!order.empty()) STRY(hipMemcpyAsync(dsel, order.data(), order.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   if (packed) STRY(hipMalloc((void**)&dqsel, (size_t)rows * 4));
@@ -495,7 +527,8 @@ int ScoreRun::launch(int row0, int nrows, float* dscores) {
       s.tsel = dsel + off;
       s.qsel = dqsel ? dqsel + row0 + r0 : nullptr;
       const dim3 grid(nc, packed ? (nr + 1) / 2 : nr);   // packed: two query rows per wave
-      if (packed) hipLaunchKernelGGL(score_local_pk_kernel<R>, grid, block, 0, ctx->stream, s, nr);   // (residues only: no side)
+      if (qgaps) launch_qgaps_score(R, local, grid, ctx->stream, s, free_del, free_ins);               // (profiles only, never packed)
+      else if (packed) hipLaunchKernelGGL(score_local_pk_kernel<R>, grid, block, 0, ctx->stream, s, nr);   // (residues only: no side)
       else if (local) hipLaunchKernelGGL((score_local_kernel<R, Side>), grid, block, 0, ctx->stream, s);
       else hipLaunchKernelGGL((score_global_kernel<R, Side>), grid, block, 0, ctx->stream, s, free_del, free_ins);
     }));
@@ -545,6 +578,17 @@ extern "C" int aln_score_profiles_vs_all(aln_ctx* ctx, const aln_qprofiles* prof
   if (!scores || !profiles) return ALN_E_ARG;
   ScoreRun run;
   int rc = run.prepare(ctx, nullptr, templates, nullptr, gap, q_begin, q_end, profiles);
+  if (rc != ALN_OK || run.route == ScoreRun::kNothing) return rc;
+  return score_block(run, scores);
+}
+
+// The same for profiles whose rows carry their own gap penalties (include/aln_hip.h): the kernels of search_qgaps.hip
+extern "C" int aln_score_profiles_gaps_vs_all(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_qgaps* gaps, const aln_seqs* templates,
+                                              int32_t align_type, int32_t q_begin, int32_t q_end, float* scores) {
+  if (!scores || !profiles || !gaps) return ALN_E_ARG;
+  ScoreRun run;
+  run.qgaps = gaps; run.qgaps_align_type = align_type;
+  int rc = run.prepare(ctx, nullptr, templates, nullptr, nullptr, q_begin, q_end, profiles);
   if (rc != ALN_OK || run.route == ScoreRun::kNothing) return rc;
   return score_block(run, scores);
 }

@@ -306,7 +306,8 @@ static int search_block(ScoreRun& run, int32_t K, float min_score, aln_hit* hits
       ScoreArgs s = run.a;
       s.q_begin = q_begin + r0;
       STRY(launch_classes(prof != nullptr, cls_cnt, [&](auto side, auto rc, int cnt, int off) {
-        hipLaunchKernelGGL((score_local_end_kernel<decltype(rc)::value, decltype(side)>), dim3(cnt), dim3(64), 0, ctx->stream, s, dlist + off, dhits, K);
+        if (run.qgaps) launch_qgaps_end(decltype(rc)::value, cnt, ctx->stream, s, dlist + off, dhits, K);
+        else hipLaunchKernelGGL((score_local_end_kernel<decltype(rc)::value, decltype(side)>), dim3(cnt), dim3(64), 0, ctx->stream, s, dlist + off, dhits, K);
         n_end += cnt;
       }));
     }
@@ -362,6 +363,17 @@ extern "C" int aln_search_topk_profiles(aln_ctx* ctx, const aln_qprofiles* profi
   int rc = run.prepare(ctx, nullptr, templates, nullptr, gap, q_begin, q_end, profiles);
   if (rc != ALN_OK) return rc;
   return search_block(run, K, min_score, hits, n_hits, "aln_search_topk_profiles");
+}
+
+extern "C" int aln_search_topk_profiles_gaps(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_qgaps* gaps, const aln_seqs* templates,
+                                             int32_t align_type, int32_t q_begin, int32_t q_end, int32_t K, float min_score,
+                                             aln_hit* hits, int32_t* n_hits) {
+  if (!hits || !n_hits || !profiles || !gaps || K < 1 || K > kSelKeep) return ALN_E_ARG;
+  ScoreRun run;
+  run.qgaps = gaps; run.qgaps_align_type = align_type;
+  int rc = run.prepare(ctx, nullptr, templates, nullptr, nullptr, q_begin, q_end, profiles);
+  if (rc != ALN_OK) return rc;
+  return search_block(run, K, min_score, hits, n_hits, "aln_search_topk_profiles_gaps");
 }
 
 #undef STRY

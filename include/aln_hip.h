@@ -209,9 +209,9 @@ int aln_has_gfx950(void);
  *                                   (allocating tens of GB costs seconds); 0: frees them when it returns
  *   "enum_pool_retries"             aln_batch_enumerate_all: how often a pair whose pools overflowed is searched again with four
  *                                   times the capacity (default 2)
- *   "search_slab_rows"              aln_search_topk, aln_search_topk_profiles: query rows whose scores are resident on the device at a time; 0 (default) = as many as
+ *   "search_slab_rows"              aln_search_topk, aln_search_topk_profiles(_gaps): query rows whose scores are resident on the device at a time; 0 (default) = as many as
  *                                   keep the slab's scores (4 B x n_templates per row) and hits (16 B x K per row) below 1 GiB each
- *   "search_debug"                  1: aln_search_topk / aln_search_topk_profiles report their slabs and the device time of scoring / selection / end cells on stderr
+ *   "search_debug"                  1: aln_search_topk / aln_search_topk_profiles(_gaps) report their slabs and the device time of scoring / selection / end cells on stderr
  *   "zscore_chunk_rows"             aln_hits_zscores, aln_hits_zscores_profiles: query rows whose shuffled strings (profiles: shuffle
  *                                   orders) and accumulators are resident on the device at a time; 0 (default) = as many as keep the
  *                                   shuffled pool (n_shuffles x |q| bytes per row with a hit; profiles: n_shuffles x 2 B per profile
@@ -410,7 +410,8 @@ int aln_search_topk(aln_ctx* ctx, const aln_seqs* queries, const aln_seqs* templ
  * aln_hits_align_profiles) tallies the aligned template letters of a round's hits per query position, and
  * aln_amd.pssm_from_counts turns such counts into integer log-odds rows on the host; aln_hits_pssm (below, after
  * aln_hits_purge) goes from a round's hits to the next round's rows in one call, the log-odds made on the device by an exact
- * integer rule. */
+ * integer rule.  Rows may also carry their own gap penalties: aln_qgaps and aln_score_profiles_gaps_vs_all /
+ * aln_search_topk_profiles_gaps (below, after aln_search_topk_profiles). */
 typedef struct {
   int32_t n_seqs;
   const int64_t* offsets;       /* n_seqs + 1, in ROWS: profile s owns rows offsets[s] .. offsets[s+1); its first and last row stand
@@ -446,6 +447,58 @@ int aln_score_profiles_vs_all(aln_ctx* ctx, const aln_qprofiles* profiles, const
 int aln_search_topk_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_seqs* templates, const aln_gap* gap,
                              int32_t q_begin, int32_t q_end, int32_t K, float min_score,
                              aln_hit* hits /* (q_end-q_begin) x K */, int32_t* n_hits /* q_end-q_begin */);
+
+/* ---- position-specific GAP PENALTIES: scoring and search for profiles whose rows carry their own gap prices --------- */
+/* A profile query is defined by where gaps are cheap (loops the hits disagree on) and where they are dear (conserved cores);
+ * the reference's own evaluators (HMAP, Gn2) are built around position-dependent gaps.  No batch gap model can say this:
+ * ALN_GAP_TABLES lets an insertion depend on (t1, q2 - q1), never on the query position. */
+typedef struct {
+  const float* del_init;   /* all four: one value per ROW of the profiles pool, indexed like aln_qprofiles.rows / n */
+  const float* del_extn;
+  const float* ins_init;
+  const float* ins_extn;
+} aln_qgaps;               /* 32 bytes */
+/* aln_score_profiles_vs_all and aln_search_topk_profiles under such rows.  Take a profile of Q rows at row offset `off` and a
+ * template of T residues, sentinels counted; S is the plane aln_score_profiles_vs_all defines.  Names follow the reference: a
+ * DELETION skips template residues, an INSERTION skips profile positions.
+ *   del(i, L), 0 <= i <= Q-2, L >= 1: the cost of L template residues skipped between profile positions i and i+1,
+ *     del_init[off+i] + del_extn[off+i] * (L-1).  The gap is priced by the row it LEAVES; row 0, the '^' row, prices the head
+ *     deletion and row Q-2 the tail deletion.
+ *   ins(a, b), 1 <= a <= b <= Q-2: the cost of skipping profile positions a..b,
+ *     ins_init[off+a] + sum_{p=a+1..b} ins_extn[off+p].  Every skipped position pays its own price.
+ * Entries read: del_* at rows 0..Q-2 and ins_* at rows 1..Q-2.  The other sentinel entries are never read — del_* at row Q-1,
+ * ins_* at rows 0 and Q-1: a NaN there changes nothing.
+ * The recurrence is the one aln_score_profiles_vs_all pins (dpmatrix.h:375-689) with every gap cost replaced:
+ *   D[i][j] = S[i][j] + max( D[i-1][j-1], max_{1<=k<j-1} D[i-1][k] - del(i-1, j-1-k), max_{1<=k<i-1} D[k][j-1] - ins(k+1, i-1) )
+ * for interior cells, clipped at 0 under ALN_LOCAL; the head deletion into (1, j) costs del(0, j-1), the head insertion into
+ * (i, 1) costs ins(1, i-1); into the final cell from (Q-2, k) the cost is del(Q-2, T-2-k), from (k, T-2) it is ins(k+1, Q-2);
+ * each of these is 0 where the align type makes that end gap free (deletions: ALN_LOCAL, ALN_SEMI_LOCAL, ALN_LOCAL_GLOBAL;
+ * insertions: ALN_LOCAL, ALN_SEMI_LOCAL, ALN_GLOBAL_LOCAL).  Degenerate shapes: Q = 2 costs del(0, T-2) and T = 2 costs
+ * ins(1, Q-2), unless free.  The score is find_max for local alignments and the final cell for the four other align types.
+ * THE ANCHOR: with all four arrays constant (del_init = ins_init = gi, del_extn = ins_extn = ge) every output of both entries
+ * is byte-identical to aln_score_profiles_vs_all / aln_search_topk_profiles under { ALN_GAP_AFFINE_CONST, gi, ge, align_type },
+ * for all five align types.
+ * The result layouts, the hit order (score descending, ties by template index, -0.0 = +0.0), min_score and the padding
+ * { -1, 0, -1, -1 }, K in 1..1024, the end-cell rule with its (Q-2, T-2) seed and strict-improvement order, q_begin == q_end,
+ * n_templates == 0 and the slabs (hint "search_slab_rows") are aln_search_topk_profiles', word for word.
+ * INTEGER SCORING ONLY, and there is no full-build fallback, because no batch gap model can express this: a fractional row
+ * entry or gap value is refused with ALN_E_NOT_INTEGRAL, a gap value below 0 with ALN_E_ARG, a template of more than 2048
+ * columns with ALN_E_TOO_LONG, and profiles->n above 26 with ALN_E_ARG (a row's four prices travel in words 26..29 of its
+ * 128-byte device image).  The value bound is aln_score_all_vs_all's with the gaps' maximum in place of gi and ge: with G the
+ * maximum of the entries read (of the whole pool), (maxs + G) * (maxQ + min(maxT, 2048)) + G + maxs < 2^23, else
+ * ALN_E_NOT_INTEGRAL.
+ * Order of the checks, nothing written when one fails: NULL arguments, and K for the search; the row range; align_type outside
+ * 0..4; aln_score_profiles_vs_all's descriptor checks; n > 26, or a NULL array in aln_qgaps (all ALN_E_ARG); template letters
+ * (ALN_E_RESIDUE); lengths (ALN_E_TOO_LONG, the 2048 columns included); a negative gap value (ALN_E_ARG); fractional values
+ * and the bound (ALN_E_NOT_INTEGRAL).
+ * Kernels: csrc/search_qgaps.hip over csrc/score_sweep_qgaps.h, register-resident like the constant-gap ones.  The hits of
+ * such a search cannot yet be aligned, z-scored or piled up under the same rows: those entries still take one gap_init /
+ * gap_extn; the end cells reported here are what they will start from. */
+int aln_score_profiles_gaps_vs_all(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_qgaps* gaps, const aln_seqs* templates,
+                                   int32_t align_type, int32_t q_begin, int32_t q_end, float* scores);
+int aln_search_topk_profiles_gaps(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_qgaps* gaps, const aln_seqs* templates,
+                                  int32_t align_type, int32_t q_begin, int32_t q_end, int32_t K, float min_score,
+                                  aln_hit* hits /* (q_end-q_begin) x K */, int32_t* n_hits /* q_end-q_begin */);
 
 /* ---- shuffle z-scores of search hits: the background of every hit scored and reduced on the device ------------------- */
 /* The reference has the hook (AlignedPairList::calcSignificance takes a Significance<Model> functor, significance.h) and ships
