@@ -137,6 +137,7 @@ EXPORTS = [
     "aln_hits_pileup", "aln_hits_pileup_profiles", "aln_hits_weights", "aln_hits_weights_profiles",
     "aln_hits_purge", "aln_hits_purge_profiles", "aln_hits_pssm", "aln_hits_pssm_profiles", "aln_pssm_entry",
     "aln_score_profiles_gaps_vs_all", "aln_search_topk_profiles_gaps",
+    "aln_hits_align_profiles_gaps", "aln_hits_column_counts_profiles_gaps",
 ]
 COMM_ID_BYTES = 128
 
@@ -236,6 +237,12 @@ def lib():
         L.aln_hits_column_counts_profiles.argtypes = [C.c_void_p, C.POINTER(AlnQProfiles), C.POINTER(AlnSeqs), C.POINTER(AlnSeqs),
                                                       C.POINTER(AlnGap), C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, _ip,
                                                       C.POINTER(AlnHitAlignment), _ip, _ip]
+        L.aln_hits_align_profiles_gaps.argtypes = [C.c_void_p, C.POINTER(AlnQProfiles), C.POINTER(AlnQGaps), C.POINTER(AlnSeqs),
+                                                   C.POINTER(AlnSeqs), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip,
+                                                   C.POINTER(AlnHitAlignment), _ip, C.c_int32, C.c_char_p, C.c_char_p, C.c_int32, _ip]
+        L.aln_hits_column_counts_profiles_gaps.argtypes = [C.c_void_p, C.POINTER(AlnQProfiles), C.POINTER(AlnQGaps), C.POINTER(AlnSeqs),
+                                                           C.POINTER(AlnSeqs), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                           C.POINTER(AlnHit), _ip, _ip, C.POINTER(AlnHitAlignment), _ip, _ip]
         L.aln_hits_pileup.argtypes = [C.c_void_p, C.POINTER(AlnSeqs), C.POINTER(AlnSeqs), C.POINTER(AlnSubmatrix), C.POINTER(AlnGap),
                                       C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlnHit), _ip, C.POINTER(AlnHitAlignment),
                                       C.POINTER(AlnHitSpan), C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), C.c_int32]
@@ -529,6 +536,19 @@ class _ProfileSide(_Side):
         self.offsets, self.n_letters = profiles.offsets, len(profiles.alphabet)
 
 
+class _GapRowSide(_ProfileSide):
+    """a profile side whose rows carry their own gap penalties (gaps: a QueryGaps over `profiles`): the entry takes the gap rows
+    after the profiles and, where its twin takes the gap, the align type alone"""
+
+    def __init__(self, entry, profiles, gaps, templates, consensus):
+        _ProfileSide.__init__(self, entry, profiles, templates, consensus)
+        self.gaps = gaps
+        self.lead = self.lead[:1] + (C.byref(gaps.c),) + self.lead[1:]
+
+    def call(self, ctx, gap, *tail):
+        return getattr(lib(), self.entry)(ctx.h, *(self.lead + (int(gap.align_type),) + tail))
+
+
 def _as(a, struct):
     return a.ctypes.data_as(C.POINTER(struct))
 
@@ -688,6 +708,14 @@ def hits_align_profiles(ctx, profiles, templates, hits, n_hits, gi, ge, consensu
                   want_pairs, want_lines, pair_stride, line_stride)
 
 
+def hits_align_profiles_gaps(ctx, profiles, gaps, templates, hits, n_hits, consensus=None, q_begin=0, align_type=LOCAL, want_pairs=True,
+                             want_lines=True, pair_stride=None, line_stride=None):
+    """aln_hits_align_profiles_gaps: hits_align_profiles for the hits of search_topk_profiles_gaps, aligned under the rows' own
+    gap penalties (gaps: the QueryGaps of the search).  -> the 6-tuple of hits_align."""
+    return _align(ctx, _GapRowSide("aln_hits_align_profiles_gaps", profiles, gaps, templates, consensus), hits, n_hits, 0, 0, q_begin,
+                  align_type, want_pairs, want_lines, pair_stride, line_stride)
+
+
 def hits_align_multi(ctx, queries, templates, hits, n_hits, alphabet, table, gi, ge, max_alignments, min_score=-np.inf, q_begin=0,
                      align_type=LOCAL, want_pairs=True, want_lines=True, pair_stride=None, line_stride=None):
     """aln_hits_align_multi: up to N = max_alignments non-intersecting local alignments of every used slot of hits[rows, K]
@@ -826,6 +854,14 @@ def hits_column_counts_profiles(ctx, profiles, templates, hits, n_hits, gi, ge, 
     -> the 4-tuple of hits_column_counts."""
     return _counts(ctx, _ProfileSide("aln_hits_column_counts_profiles", profiles, templates, consensus), hits, n_hits, gi, ge, weights,
                    q_begin, align_type, want_covered)
+
+
+def hits_column_counts_profiles_gaps(ctx, profiles, gaps, templates, hits, n_hits, consensus=None, weights=None, q_begin=0,
+                                     align_type=LOCAL, want_covered=True):
+    """aln_hits_column_counts_profiles_gaps: hits_column_counts_profiles over the alignments hits_align_profiles_gaps reports
+    (gaps: the QueryGaps of the search).  -> the 4-tuple of hits_column_counts."""
+    return _counts(ctx, _GapRowSide("aln_hits_column_counts_profiles_gaps", profiles, gaps, templates, consensus), hits, n_hits, 0, 0,
+                   weights, q_begin, align_type, want_covered)
 
 
 def _pileup(ctx, side, hits, n_hits, gi, ge, q_begin, align_type, want_letters, want_tpos, want_spans, line_stride):

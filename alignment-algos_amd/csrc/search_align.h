@@ -1,13 +1,13 @@
 // search_align.h — what the fused hit-alignment entries share.  Device: how a hit is described to a kernel (HitDesc), the two
 // observers that turn a row sweep into the strip bytes and the final cell's pointer, strip_walk, the walk back through the
 // strip, and the ONE pair of kernels around them, hit_local_kernel / hit_global_kernel<R, Side, Job>: what becomes of a walk
-// entry is the job's — ListJob here (search_align.hip: the pair list), CountJob in search_counts.hip (the column counts),
+// entry is the job's — ListJob here (search_align.hip: the pair list), CountJob in search_counts.h (the column counts),
 // PileupJob in search_pileup.h (the query-anchored rows: search_pileup.hip downloads them, search_weights.hip keeps them).
 // search_align_multi.hip (several rounds per hit) has a kernel of its own around the same walk.  Host: where a slot's record,
 // list and lines go (AlignOut, put_fused, pair_desc), the routing of slots (route_slots) and the fused route's driver that
 // the four entries run their chunks through (FusedRoute, over score_common.h's DeviceBufs, STRY / RTRY and launch_classes).
 // Around the driver, what the entries over HitDesc share: a hit's strip bytes (hit_strip_bytes), the launch of the kernel pair
-// over a job (launch_hit_job), the owner of the per-hit records (HitRecords), the batch route of the jobs that read pair lists
+// over a job (launch_hit_job), the owner of the per-hit records (HitRecords), the chunks of the entries that list (list_fused_hits), the batch route of the jobs that read pair lists
 // on the host (for_list_groups) and what an extern "C" entry does before its body (hit_list_ok, hit_entry).
 // The strip byte is defined at the head of search_align.hip.  DESIGN 4.8 found that a helper which takes a kernel's ROW ARRAYS by reference costs
 // registers; the walk and the jobs run after the sweep on scalar state only, and sharing them costs none.
@@ -611,6 +611,70 @@ struct HitRecords {
     }
   }
 };
+
+// The chunks of fused hits of the entries that list (aln_hits_align, aln_hits_align_profiles, aln_hits_align_profiles_gaps):
+// one list each, and the two lines where ao wants them; every record is filed through put_fused.  launch(fr, c, g): the
+// caller's kernel pair over ListJob for one chunk (launch_hit_job<ListJob>; search_align_qgaps.h: launch_hit_qgaps_job<ListJob>).
+template <class Launch>
+int list_fused_hits(ScoreRun& run, const aln_seqs* queries, SlotRoutes& sr, AlignOut& ao, Launch&& launch) {
+  aln_ctx* ctx = run.ctx;
+  const aln_seqs* templates = run.templates;
+  std::vector<HitDesc>& fast = sr.fast;
+  const std::vector<size_t>& fast_slot = sr.fast_slot;
+  const bool want_lines = ao.tlines != nullptr;
+  const int32_t line_stride = ao.line_stride;
+  // the most entries a fused hit's list can have
+  auto list_cap = [&](const HitDesc& d) {
+    if (run.local) return std::min(d.q_end, d.t_end) + 3;
+    return (int)std::min(queries->offsets[d.q + 1] - queries->offsets[d.q], templates->offsets[d.t + 1] - templates->offsets[d.t]) + 1;
+  };
+  FusedRoute<HitDesc> fr(run, queries, fast);
+  fr.cut(1, want_lines, line_stride, [&](const HitDesc& d) {
+    return HitNeed{hit_strip_bytes(run, queries, d), 0, list_cap(d)};
+  });
+  const size_t max_n = fr.max_n, max_trav = fr.max_trav;
+  int32_t* dtrav = nullptr; PairDesc* dpd = nullptr; StrOut* dso = nullptr; char* dlines = nullptr;
+  HitRecords rec;
+  RTRY(fr.begin());
+  STRY(fr.bufs.get(dtrav, max_trav));
+  RTRY(rec.alloc(fr.bufs, max_n));
+  std::vector<int32_t> htrav(max_trav);
+  std::vector<PairDesc> hpd;
+  std::vector<StrOut> hso;
+  std::vector<char> hlines;
+  if (want_lines || run.prof) RTRY(fr.upload_pools());
+  if (want_lines) {
+    STRY(fr.bufs.get(dpd, max_n));
+    STRY(fr.bufs.get(dso, max_n));
+    STRY(fr.bufs.get(dlines, max_n * 2 * (size_t)line_stride));
+    hpd.resize(max_n); hso.resize(max_n); hlines.resize(max_n * 2 * (size_t)line_stride);
+  }
+  for (const FusedChunk& c : fr.chunks) {
+    const int n = (int)c.n;
+    RTRY(fr.stage(c));
+    AlignArgs g = {};
+    g.desc = fr.ddesc; g.strip = fr.dstrip; g.trav = dtrav; g.trav_stride = c.trav_stride; g.res = rec.dres; g.same = rec.dsame;
+    RTRY(launch(fr, c, g));
+    if (want_lines) {
+      for (int h = 0; h < n; ++h) hpd[h] = pair_desc(queries, templates, fast[c.h0 + h].q, fast[c.h0 + h].t);
+      STRY(hipMemcpyAsync(dpd, hpd.data(), (size_t)n * sizeof(PairDesc), hipMemcpyHostToDevice, ctx->stream));
+      StrParams prm = {c.trav_stride, 1, 0, line_stride};
+      RTRY(launch_gapped_strings(ctx, n, dpd, rec.dres, dtrav, fr.dqch, fr.dtch, dlines, dso, prm));
+      STRY(hipMemcpyAsync(hso.data(), dso, (size_t)n * sizeof(StrOut), hipMemcpyDeviceToHost, ctx->stream));
+      STRY(hipMemcpyAsync(hlines.data(), dlines, (size_t)n * 2 * (size_t)line_stride, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    RTRY(rec.enqueue_download(ctx, c.n));
+    if (ao.pairs) STRY(hipMemcpyAsync(htrav.data(), dtrav, (size_t)n * c.trav_stride * 8, hipMemcpyDeviceToHost, ctx->stream));
+    STRY(hipStreamSynchronize(ctx->stream));                 // the host vectors above are read by the copies until here
+    for (int h = 0; h < n; ++h) {
+      const HitDesc& d = fast[c.h0 + h];
+      const int64_t Q = queries->offsets[d.q + 1] - queries->offsets[d.q], T = templates->offsets[d.t + 1] - templates->offsets[d.t];
+      put_fused(ao, fast_slot[c.h0 + h], rec.hres[h], rec.hsame[h], Q, T, htrav.data() + (size_t)h * c.trav_stride * 2,
+                want_lines ? &hso[h] : nullptr, want_lines ? hlines.data() + (size_t)h * 2 * line_stride : nullptr, line_stride);
+    }
+  }
+  return ALN_OK;
+}
 
 // The batch route of a job that reads pair lists on the host: the slots of sr.bq / bt / bslot go through
 // align_through_batches a group at a time, records and lists into buffers of the group — at most kListGroupBytes of lists,

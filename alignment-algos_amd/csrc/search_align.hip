@@ -88,21 +88,13 @@ static int align_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
   aln_ctx* ctx = run.ctx;
   const aln_seqs* templates = run.templates;
   const aln_qprofiles* prof = run.prof;
-  const bool want_lines = tlines || qlines;
   int rc;
   const int rows = run.rows;
   if (rows == 0) return ALN_OK;
-  // the most entries a fused hit's list can have
-  auto list_cap = [&](const HitDesc& d) {
-    if (run.local) return std::min(d.q_end, d.t_end) + 3;
-    return (int)std::min(queries->offsets[d.q + 1] - queries->offsets[d.q], templates->offsets[d.t + 1] - templates->offsets[d.t]) + 1;
-  };
-
   // one walk: every used slot validated and described for its route (nothing is written before it ends)
   SlotRoutes sr;
   if ((rc = route_slots(run, queries, K, hits, n_hits, hit_kernel_classes(run), run.local, sr)) != ALN_OK) return rc;
   std::vector<HitDesc>& fast = sr.fast;
-  const std::vector<size_t>& fast_slot = sr.fast_slot;
   const std::vector<int32_t>&bq = sr.bq, &bt = sr.bt;
   const std::vector<size_t>& bslot = sr.bslot;
   ctx->align_routes[0] = (int64_t)fast.size(); ctx->align_routes[1] = (int64_t)bq.size();
@@ -111,51 +103,10 @@ static int align_block(ScoreRun& run, const aln_seqs* queries, int32_t K, const 
 
   // chunks of fused hits: one list each, and the two lines where wanted
   if (!fast.empty()) {
-    FusedRoute<HitDesc> fr(run, queries, fast);
-    fr.cut(1, want_lines, line_stride, [&](const HitDesc& d) {
-      return HitNeed{hit_strip_bytes(run, queries, d), 0, list_cap(d)};
+    rc = list_fused_hits(run, queries, sr, ao, [](FusedRoute<HitDesc>& fr, const FusedChunk& c, AlignArgs& g) {
+      return launch_hit_job<ListJob>(fr, c, g);
     });
-    const size_t max_n = fr.max_n, max_trav = fr.max_trav;
-    int32_t* dtrav = nullptr; PairDesc* dpd = nullptr; StrOut* dso = nullptr; char* dlines = nullptr;
-    HitRecords rec;
-    RTRY(fr.begin());
-    STRY(fr.bufs.get(dtrav, max_trav));
-    RTRY(rec.alloc(fr.bufs, max_n));
-    std::vector<int32_t> htrav(max_trav);
-    std::vector<PairDesc> hpd;
-    std::vector<StrOut> hso;
-    std::vector<char> hlines;
-    if (want_lines || prof) RTRY(fr.upload_pools());
-    if (want_lines) {
-      STRY(fr.bufs.get(dpd, max_n));
-      STRY(fr.bufs.get(dso, max_n));
-      STRY(fr.bufs.get(dlines, max_n * 2 * (size_t)line_stride));
-      hpd.resize(max_n); hso.resize(max_n); hlines.resize(max_n * 2 * (size_t)line_stride);
-    }
-    for (const FusedChunk& c : fr.chunks) {
-      const int n = (int)c.n;
-      RTRY(fr.stage(c));
-      AlignArgs g = {};
-      g.desc = fr.ddesc; g.strip = fr.dstrip; g.trav = dtrav; g.trav_stride = c.trav_stride; g.res = rec.dres; g.same = rec.dsame;
-      RTRY(launch_hit_job<ListJob>(fr, c, g));
-      if (want_lines) {
-        for (int h = 0; h < n; ++h) hpd[h] = pair_desc(queries, templates, fast[c.h0 + h].q, fast[c.h0 + h].t);
-        STRY(hipMemcpyAsync(dpd, hpd.data(), (size_t)n * sizeof(PairDesc), hipMemcpyHostToDevice, ctx->stream));
-        StrParams prm = {c.trav_stride, 1, 0, line_stride};
-        RTRY(launch_gapped_strings(ctx, n, dpd, rec.dres, dtrav, fr.dqch, fr.dtch, dlines, dso, prm));
-        STRY(hipMemcpyAsync(hso.data(), dso, (size_t)n * sizeof(StrOut), hipMemcpyDeviceToHost, ctx->stream));
-        STRY(hipMemcpyAsync(hlines.data(), dlines, (size_t)n * 2 * (size_t)line_stride, hipMemcpyDeviceToHost, ctx->stream));
-      }
-      RTRY(rec.enqueue_download(ctx, c.n));
-      if (pairs) STRY(hipMemcpyAsync(htrav.data(), dtrav, (size_t)n * c.trav_stride * 8, hipMemcpyDeviceToHost, ctx->stream));
-      STRY(hipStreamSynchronize(ctx->stream));                 // the host vectors above are read by the copies until here
-      for (int h = 0; h < n; ++h) {
-        const HitDesc& d = fast[c.h0 + h];
-        const int64_t Q = queries->offsets[d.q + 1] - queries->offsets[d.q], T = templates->offsets[d.t + 1] - templates->offsets[d.t];
-        put_fused(ao, fast_slot[c.h0 + h], rec.hres[h], rec.hsame[h], Q, T, htrav.data() + (size_t)h * c.trav_stride * 2,
-                  want_lines ? &hso[h] : nullptr, want_lines ? hlines.data() + (size_t)h * 2 * line_stride : nullptr, line_stride);
-      }
-    }
+    if (rc != ALN_OK) return rc;
   }
   if (!bq.empty()) {
     rc = align_through_batches(ctx, queries, templates, run.sub, prof, run.gap, bq, bt, bslot, ao);

@@ -492,8 +492,21 @@ typedef struct {
  * (ALN_E_RESIDUE); lengths (ALN_E_TOO_LONG, the 2048 columns included); a negative gap value (ALN_E_ARG); fractional values
  * and the bound (ALN_E_NOT_INTEGRAL).
  * Kernels: csrc/search_qgaps.hip over csrc/score_sweep_qgaps.h, register-resident like the constant-gap ones.  The hits of
- * such a search cannot yet be aligned, z-scored or piled up under the same rows: those entries still take one gap_init /
- * gap_extn; the end cells reported here are what they will start from. */
+ * such a search are aligned under the same rows by aln_hits_align_profiles_gaps and tallied by
+ * aln_hits_column_counts_profiles_gaps (below, after aln_hits_column_counts_profiles), which start from the end cells reported
+ * here.  They cannot yet be z-scored, piled up, weighted, purged, turned into the next round's rows or aligned into several
+ * alignments under the same rows: those entries still take one gap_init / gap_extn.
+ * THE ALIGNMENT under gap rows (what aln_hits_align_profiles_gaps reports).  The planes are those above.  The POINTER of a cell
+ * is the reference's rule (dpmatrix.h:447-486 for an interior cell, 505-534 for the final cell, 607-649 under ALN_LOCAL) with
+ * every cost replaced by del(.,.) / ins(.,.): the candidates of cell (i, j) are tried in the order
+ *   match from (i-1, j-1); deletions from (i-1, k), k ascending; insertions from (k, j-1), k ascending,
+ * and a later candidate wins only when it is STRICTLY greater than the best so far, so of equal candidates the first in that
+ * order is the pointer.  A cell of row 1 or column 1 points at (0, 0).  The same order holds for the final cell (Q-1, T-1):
+ * match from (Q-2, T-2), then (Q-2, k) with k ascending at del(Q-2, T-2-k), then (k, T-2) with k ascending at ins(k+1, Q-2); a
+ * free end gap costs 0.  The LIST is Optimal's (optimal.h:56-74): (Q-1, T-1), then the pointers back to (0, 0), reported from
+ * (0, 0) on.  Under ALN_LOCAL it is optimal.h:79-105: (Q-1, T-1), the end cell, then the pointers while the cell pointed at has
+ * a score > 0 — the walk stops BEFORE a cell whose score is <= 0 — and (0, 0) in front when it stopped at a cell with both
+ * indices > 0. */
 int aln_score_profiles_gaps_vs_all(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_qgaps* gaps, const aln_seqs* templates,
                                    int32_t align_type, int32_t q_begin, int32_t q_end, float* scores);
 int aln_search_topk_profiles_gaps(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_qgaps* gaps, const aln_seqs* templates,
@@ -668,6 +681,52 @@ int aln_hits_column_counts_profiles(aln_ctx* ctx, const aln_qprofiles* profiles,
                                     const aln_seqs* templates, const aln_gap* gap, int32_t q_begin, int32_t q_end, int32_t K,
                                     const aln_hit* hits, const int32_t* n_hits, const int32_t* weights,
                                     aln_hit_alignment* out, int32_t* counts /* ... x profiles->n */, int32_t* covered);
+/* ---- the hits of a search under position-specific GAP PENALTIES (aln_qgaps), aligned and tallied under the same rows ---- */
+/* aln_hits_align_profiles for the hits of aln_search_topk_profiles_gaps.  The alignment of a slot is the one defined with
+ * aln_qgaps above (THE ALIGNMENT under gap rows): the planes of aln_score_profiles_gaps_vs_all, the pointer rule with its
+ * order of candidates — match, deletions k ascending, insertions k ascending, a later one only when strictly greater —, the
+ * final cell under the same order, Optimal's list.
+ * Taken from aln_hits_align_profiles, word for word: the hit layout and which slots are used; out, pairs, the line group and
+ * lengths; the consensus and placeholder pools; the identity counted over characters; the per-slot statuses and the return
+ * value; q_begin == q_end (ALN_OK, nothing written); the local rule (the slot's end cell is trusted; a sweep score that differs
+ * from .score gives the slot ALN_E_ARG, n_pairs 0, and the call goes on); non-local slots ignoring q_end / t_end / score; the
+ * hints "align_chunk_hits" and "align_rows_per_chunk"; aln_hits_align_last_routes.
+ * THE ANCHOR: with all four arrays constant (del_init = ins_init = gi, del_extn = ins_extn = ge) every output byte — records,
+ * lists, lines, lengths — equals aln_hits_align_profiles under { ALN_GAP_AFFINE_CONST, gi, ge, align_type }, for all five
+ * align types.
+ * INTEGER SCORING ONLY: the descriptor and gap checks, their status codes, their order and the value bound are those of
+ * aln_search_topk_profiles_gaps (n <= 26, a NULL array, a negative or fractional value, templates beyond 2048 columns ->
+ * ALN_E_TOO_LONG).
+ * Routes: there is no batch route, because no batch gap model prices a gap by the query position.  Every pair with an interior
+ * (Q >= 3 and T >= 3; T <= 2048 by the checks) goes through one wave per hit over the gap-row sweeps
+ * (csrc/search_align_qgaps.h: the 1 B/cell strip and the walk of aln_hits_align_profiles), for all eight length classes and all
+ * five align types.  A pair without an interior (Q = 2 or T = 2) is filed on the host: its list is the one
+ * aln_hits_align_profiles reports for such a pair, its score is the definition's — Q = 2: -del(0, T-2), T = 2: -ins(1, Q-2), 0
+ * where that end gap is free or nothing is skipped, 0 under ALN_LOCAL.  aln_hits_align_last_routes counts the host-filed slots
+ * in its second number.  Hint "align_fused_nonlocal" has nothing to switch to and is ignored.
+ * Checks, in this order, nothing written when one fails: NULL profiles / gaps / templates / hits / n_hits / out; K outside
+ * 1..1024; pairs with pair_stride < 2; the line group given in part or line_stride < 1 (ALN_E_ARG);
+ * aln_search_topk_profiles_gaps', in its order, with the consensus pool — a wrong n_seqs, a NULL member, any differing offset:
+ * ALN_E_ARG — directly after the profile descriptor, where aln_hits_align_profiles checks it; every n_hits[r] in 0..K; every
+ * used slot's t in [0, n_templates); local, its end cell in range (ALN_E_ARG). */
+int aln_hits_align_profiles_gaps(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_qgaps* gaps,
+                                 const aln_seqs* consensus /* may be NULL */, const aln_seqs* templates, int32_t align_type,
+                                 int32_t q_begin, int32_t q_end, int32_t K, const aln_hit* hits, const int32_t* n_hits,
+                                 aln_hit_alignment* out, int32_t* pairs, int32_t pair_stride,
+                                 char* tlines, char* qlines, int32_t line_stride, int32_t* lengths);
+/* aln_hits_column_counts_profiles for the same hits: its arguments with `gaps` and `align_type` in place of `gap`.  The
+ * alignment of a slot is the list aln_hits_align_profiles_gaps reports for it, and out[s] is, byte for byte, the record that
+ * entry writes when called with pairs == NULL and no line group.  The weights (0..65535), counts (x profiles->n) and covered —
+ * both written in full by every successful call —, the contribution rule and the independence of the chunking are
+ * aln_hits_column_counts_profiles'.  A pair without an interior has no interior entry and contributes nothing.  With all four
+ * arrays constant every output byte equals aln_hits_column_counts_profiles'.  Routes: those of aln_hits_align_profiles_gaps
+ * (csrc/search_counts_qgaps.hip: the same kernels over the job that counts).  Checks: NULL profiles / gaps / templates / hits /
+ * n_hits / out / counts and K; then those of aln_hits_align_profiles_gaps from aln_search_topk_profiles_gaps' on; the weights. */
+int aln_hits_column_counts_profiles_gaps(aln_ctx* ctx, const aln_qprofiles* profiles, const aln_qgaps* gaps,
+                                         const aln_seqs* consensus /* may be NULL */, const aln_seqs* templates,
+                                         int32_t align_type, int32_t q_begin, int32_t q_end, int32_t K,
+                                         const aln_hit* hits, const int32_t* n_hits, const int32_t* weights,
+                                         aln_hit_alignment* out, int32_t* counts /* ... x profiles->n */, int32_t* covered);
 /* ---- the query-anchored pileup of search hits: one fixed-width row per hit, column = query position -------------------- */
 /* The a3m / pileup form of a search round: for every used slot one row whose index is the query position and whose entry is
  * the template residue aligned to that position, or a gap — what per-hit weights, purging of near-identical hits, gap
@@ -979,7 +1038,9 @@ int aln_hits_align_multi_profiles(aln_ctx* ctx, const aln_qprofiles* profiles, c
                                   int32_t* n_found /* rows x K */, aln_hit_alignment* out /* rows x K x N */,
                                   int32_t* pairs, int32_t pair_stride, char* tlines, char* qlines, int32_t line_stride, int32_t* lengths);
 /* out[0]: the used slots the last aln_hits_align / aln_hits_align_profiles / aln_hits_align_multi / aln_hits_align_multi_profiles / aln_hits_column_counts(_profiles) / aln_hits_purge(_profiles) / aln_hits_weights(_profiles) / aln_hits_pileup(_profiles) call on this context sent through a fused kernel,
- * out[1]: through resident batches; { 0, 0 } before any call and after a call that failed its checks.  NULL argument: ALN_E_ARG. */
+ * out[1]: through resident batches; { 0, 0 } before any call and after a call that failed its checks.  NULL argument: ALN_E_ARG.
+ * aln_hits_align_profiles_gaps and aln_hits_column_counts_profiles_gaps report here too: out[1] counts the slots the host filed
+ * (pairs without an interior; those entries have no batch route). */
 int aln_hits_align_last_routes(const aln_ctx* ctx, int64_t out[2]);
 
 /* ---- multi-GPU: a length-sorted deal of independent units + ONE collective (RCCL all-gather of scores) ----------- */
